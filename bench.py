@@ -3,6 +3,9 @@
 
   python bench.py --gpus N --steps K --warmup W
       N > 1 is launched by the driver as  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+  python bench.py ... --dump-outputs DIR
+      also writes what the last timed step computed to DIR/*.npy (float32, seeded samples of the large arrays), with the draws
+      pinned (--seed, default 0 when dumping), so that two builds can be compared output for output
 
 One "step" = the whole optimisation step on every rank's own 256 synthetic clips (32 white-noise 10 s sources x 8
 random 2.01 s crops @16 kHz): crop + normalise, conv encoder, student ViT, predictor, EMA-teacher targets, masked MSE,
@@ -164,6 +167,39 @@ def build_model(device, seed: int, seconds: float = 2.01, nat: bool = False):
                  adam_weight_decay=0.04, resample_sr=16000, process_audio_seconds=seconds, nr_samples_per_audio=8,
                  average_top_k_layers=8, size="base")
     return model.to(device)
+
+
+DUMP_MAX_ELEMENTS = 1 << 21      # per array (8 MB of float32); larger arrays are dumped as a fixed, seeded sample of their elements
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, out, flat) -> dict:
+    """--dump-outputs: what the timed step handed its caller in the last timed step -- the forward's ForwardReturn (loss,
+    local_features, contextual_features, targets, preds) and the parameters it left behind (student fp32 master weights and EMA
+    teacher) -- as <path>/<name>.npy in float32.  An array of more than DUMP_MAX_ELEMENTS elements is written as the 1-D sample
+    flat[idx] at sorted indices idx drawn without replacement by PCG64(crc32(name)): the same positions in every run of the same
+    configuration.  Returns {name: (shape, elements written)}."""
+    import zlib
+    import numpy as np
+    arrays = dict(dict.items(out))
+    arrays["preds"] = out["preds"]                      # materialised on first read (jepa._StepOutputs)
+    arrays["student_params"] = flat.p32
+    arrays["teacher_params"] = flat.t32
+    os.makedirs(path, exist_ok=True)
+    written, total = {}, 0
+    for name, t in arrays.items():
+        v = t.detach().reshape(-1)
+        if v.numel() > DUMP_MAX_ELEMENTS:
+            rng = np.random.Generator(np.random.PCG64(zlib.crc32(name.encode())))
+            idx = np.sort(rng.choice(v.numel(), size=DUMP_MAX_ELEMENTS, replace=False))
+            v = v[torch.from_numpy(idx).to(v.device)]
+        a = v.float().cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB at '{name}'")
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        written[name] = (tuple(t.shape), int(a.size))
+    return written
 
 
 def gemm_kernel_name(f) -> str:
@@ -421,7 +457,15 @@ def main():
                     help="one GPU: at every gradient-bucket hook a copy kernel confined to the CUs a data-parallel run leaves free moves 2 x the "
                          "bucket's bytes on a communication stream (the HBM + CU footprint of reduce-scatter + all-gather); an EMULATION, "
                          "reported as `allreduce_emulated`, never part of a scaling record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what the last timed step computed (its ForwardReturn and the updated student / "
+                         "teacher parameters) as DIR/<name>.npy, float32, larger arrays as a fixed seeded sample (<= 64 MB in all); "
+                         "without --seed the draws are pinned with seed 0, so that runs with the same arguments see the same inputs")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.dump_outputs is not None and args.seed is None:
+        args.seed = 0
 
     from wavjepa_amd.data import SyntheticAudioSource
     from wavjepa_amd.masking import TimeInverseBlockMasker
@@ -554,6 +598,10 @@ def main():
     runner.reducer.timing = False
     allreduce = runner.reducer.timing_summary()
     peak_timed_gb = torch.cuda.max_memory_allocated(device) / 1e9      # before the optional dense-shape block grows the arena
+    if args.dump_outputs is not None and rank == 0:                  # before any later launch reuses the step's arena
+        note(f"dumping the last timed step's outputs to {args.dump_outputs}")
+        for name, (shape, n) in dump_outputs(args.dump_outputs, out, model._flat).items():
+            print(f"[bench] dumped {name}: shape {list(shape)}, {n} elements written", file=sys.stderr, flush=True)
     if not args.no_calibration:
         note("calibration launches (after)")
         calib_after = optional("calibration (after)", lambda: run_calibration(device))
@@ -724,15 +772,19 @@ def main():
             note("cpu baseline done")
         print(json.dumps(line), flush=True)
         if classes:
-            top = sorted(classes.items(), key=lambda kv: -kv[1]["ms"])[:25]
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            with open(os.path.join(ROOT, "gpurun_out", "bench_kernel_classes.json"), "w") as fh:
-                json.dump({k: dict(ms=round(v["ms"], 3), launches=v["launches"],
-                                   tflops=round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1) if v["flops"] else None) for k, v in top}, fh, indent=1)
-            shapes = sorted(getattr(profile_one_step, "shapes", {}).items(), key=lambda kv: -kv[1]["ms"])
-            with open(os.path.join(ROOT, "gpurun_out", "bench_gemm_shapes.json"), "w") as fh:
-                json.dump({k: dict(ms=round(v["ms"], 3), launches=v["launches"], us_per_launch=round(v["ms"] / v["launches"] * 1e3, 1),
-                                   tflops=round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1)) for k, v in shapes}, fh, indent=1)
+            # per-class and per-shape tables of the instrumented step (tools/prof_step.sh collects them); a side product like every
+            # leg after the timed region -- a tree the run may not write to costs the tables, not the run
+            def write_tables():
+                top = sorted(classes.items(), key=lambda kv: -kv[1]["ms"])[:25]
+                os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
+                with open(os.path.join(ROOT, "gpurun_out", "bench_kernel_classes.json"), "w") as fh:
+                    json.dump({k: dict(ms=round(v["ms"], 3), launches=v["launches"],
+                                       tflops=round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1) if v["flops"] else None) for k, v in top}, fh, indent=1)
+                shapes = sorted(getattr(profile_one_step, "shapes", {}).items(), key=lambda kv: -kv[1]["ms"])
+                with open(os.path.join(ROOT, "gpurun_out", "bench_gemm_shapes.json"), "w") as fh:
+                    json.dump({k: dict(ms=round(v["ms"], 3), launches=v["launches"], us_per_launch=round(v["ms"] / v["launches"] * 1e3, 1),
+                                       tflops=round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1)) for k, v in shapes}, fh, indent=1)
+            optional("kernel tables", write_tables)
     if dist.is_initialized():
         optional("final barrier", lambda: (dist.barrier(), dist.destroy_process_group()), collective=True)
     if diverged:

@@ -1575,6 +1575,10 @@ def test_pair_and_persistent_gemms_finish_beside_a_long_lived_cu_holding_kernel(
     beside = [c for c, r in zip(pool, ratios) if r < 1.5]
     assert len(beside) >= 2, ("no two streams that run beside the holder's stream", single, ratios)
     s_pair, s_pers = beside[0], beside[1]
+    # the NaN fills run on the default stream, which may share the holder's hardware queue: they must be done before the holder starts,
+    # or they land ~2 s later on top of the GEMMs' results
+    outs_pair = [torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=dev()) for _ in range(4)]
+    outs_pers = [torch.full((Mp, Np), float("nan"), dtype=torch.bfloat16, device=dev()) for _ in range(4)]
     torch.cuda.synchronize()
     done_hold = torch.cuda.Event()
     with torch.cuda.stream(s_hold):
@@ -1582,8 +1586,6 @@ def test_pair_and_persistent_gemms_finish_beside_a_long_lived_cu_holding_kernel(
         done_hold.record(s_hold)
     import time
     time.sleep(0.05)                                  # the holder is resident before the GEMMs are queued
-    outs_pair = [torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=dev()) for _ in range(4)]
-    outs_pers = [torch.full((Mp, Np), float("nan"), dtype=torch.bfloat16, device=dev()) for _ in range(4)]
     for rep in range(24):
         with torch.cuda.stream(s_pair):
             run_pair(outs_pair[rep % 4])
@@ -1635,6 +1637,7 @@ def test_gemm_persistent_counter_slots_are_recycled(ops):
         fresh = [torch.cuda.Stream() for _ in range(8)]
         for st in fresh:
             C = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=dev())
+            st.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(st):
                 ops.gemm(A, W, C, M=M, N=N, K=K, lda=K, ldb=K, ldc=N)
             st.synchronize()
