@@ -3,6 +3,11 @@
 
   python bench.py --gpus N --steps K --warmup W
       N > 1 is launched by the driver as  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+      A plain run does what the headline figure needs and nothing else: set-up, W warm-up steps, the K timed steps, the outputs of
+      --dump-outputs, the JSON line.
+  python bench.py ... --full
+      also every measurement and check listed below (calibration, dense-shape block, replica check, instrumented step, CPU baseline);
+      --no-calibration, --dense-steps, --no-profile and --no-cpu-baseline then leave single legs out
   python bench.py ... --dump-outputs DIR
       also writes what the last timed step computed to DIR/*.npy (float32, seeded samples of the large arrays), with the draws
       pinned (--seed, default 0 when dumping), so that two builds can be compared output for output
@@ -12,7 +17,7 @@ random 2.01 s crops @16 kHz): crop + normalise, conv encoder, student ViT, predi
 EMA update, full backward, gradient all-reduce (N > 1), global-norm clip, AdamW.  WavJEPA-base (12 x d768 student and
 teacher, 12 x d384 predictor, 512-ch conv stack), bf16 compute with fp32 master weights, random-init weights.
 
-Prints ONE JSON line (rank 0).  Besides the contract fields it carries
+Prints ONE JSON line (rank 0).  Besides the contract fields it carries, with --full (null in a plain run, `cpu_baseline` absent)
   roofline     the dominant kernel of the step (the bf16 MFMA GEMM family), ALGORITHMIC flops / measured duration, both
                taken live from an instrumented step of this very run (HIP events on the launch stream around every
                C-ABI call), against the dense bf16 MFMA peak of MI355X (2.5 PFLOP/s);
@@ -22,7 +27,8 @@ Prints ONE JSON line (rank 0).  Besides the contract fields it carries
   calibration  two fixed launches from the library (an MFMA-bound GEMM, an HBM-bound stream) before the warm-up and after the timed
                region: how fast THIS box is, the committed reference box's figures, and `ms_per_step_at_reference_box`;
   dense_ms_per_step  the same step with the reference's dense key-masked shapes, timed in this run (5 steps);
-  replicas_equal     (N > 1) every rank ends the run with bit-identical parameters;
+  replicas_equal     (N > 1) every rank ends the run with bit-identical parameters (`param_checksum`: the sums it compares);
+and in every run
   allreduce          (N > 1, or one rank under torch.distributed.run) how long the gradient buckets had to travel while the
                      backward still ran, and how long the optimiser then still waited for them (HIP events, median over the
                      timed steps).
@@ -446,10 +452,13 @@ def main():
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="2s-bf16",
                     help="2s-bf16 = the headline metric (BASELINE config 2/3); 4s-fp8 = BASELINE config 5 (400 tokens, MX fp8 forward GEMMs); "
                          "2s-nat = BASELINE config 4 (device-side scene augmentation + 2-channel front-end)")
-    ap.add_argument("--dense-steps", type=int, default=5, help="extra timed steps with the dense (non-ragged) shapes; 0 = skip")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--no-calibration", action="store_true", help="skip the box-speed calibration launches around the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the measurements and checks that the headline figure does not need: calibration "
+                         "launches around the timed region, dense-shape block, replica check (N > 1), instrumented step, CPU baseline")
+    ap.add_argument("--dense-steps", type=int, default=5, help="--full: extra timed steps with the dense (non-ragged) shapes; 0 = skip")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the instrumented step")
+    ap.add_argument("--no-calibration", action="store_true", help="--full: skip the box-speed calibration launches around the timed region")
     ap.add_argument("--seed", type=int, default=None,
                     help="pin the masks (the maskers draw from OS entropy, as upstream) and the crop starts / shuffles: two runs with the same "
                          "seed see the same batches (A/B comparisons of a loss; the default run stays unpinned)")
@@ -466,6 +475,9 @@ def main():
         raise SystemExit("--steps must be at least 1")
     if args.dump_outputs is not None and args.seed is None:
         args.seed = 0
+    if not args.full:            # a plain run: every leg that --full adds is left out (the replica check below asks args.full itself)
+        args.no_calibration = args.no_profile = args.no_cpu_baseline = True
+        args.dense_steps = 0
 
     from wavjepa_amd.data import SyntheticAudioSource
     from wavjepa_amd.masking import TimeInverseBlockMasker
@@ -647,7 +659,9 @@ def main():
             note(f"dense-shape block done: {dense_ms:.1f} ms/step")
     # data-parallel self-check: after the same number of identical optimiser steps every rank must hold the same parameters
     flat = model._flat
-    checksum = torch.stack([flat.p32.double().sum(), flat.p32.double().abs().sum(), flat.t32.double().abs().sum()])
+    checksum = None
+    if args.full:
+        checksum = torch.stack([flat.p32.double().sum(), flat.p32.double().abs().sum(), flat.t32.double().abs().sum()])
     replicas_equal = None
     diverged = None
 
@@ -656,7 +670,7 @@ def main():
         dist.all_gather(gathered, checksum)
         return gathered
 
-    if dist.is_initialized():
+    if args.full and dist.is_initialized():
         note("replica check")
         gathered = optional("replica check", replica_check, collective=True)
         if gathered is not None:
@@ -753,7 +767,7 @@ def main():
                 allreduce, emulation=True, workgroups=runner.reducer._emu_wgs, assumed_busbw_gbps=runner.reducer._emu_gbps or None,
                 assumed_world=runner.reducer._emu_world,
                 note="one GPU; a copy kernel reads and rewrites every gradient bucket twice on a communication stream; nothing crosses xGMI"),
-            "replicas_equal": replicas_equal, "param_checksum": [float(v) for v in checksum.tolist()],
+            "replicas_equal": replicas_equal, "param_checksum": None if checksum is None else [float(v) for v in checksum.tolist()],
             "final_loss": round(loss, 5),
             "peak_hbm_gb": round(peak_timed_gb, 1),                     # warm-up + timed region (the arena follows the ragged row counts)
             "peak_hbm_gb_after_dense_block": round(torch.cuda.max_memory_allocated(device) / 1e9, 1),

@@ -486,7 +486,7 @@ def test_bench_runs_under_torch_distributed_run_with_one_rank():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(launch.free_port()), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--clips-per-gpu", "16",
-           "--dense-steps", "1", "--no-cpu-baseline", "--no-profile"]
+           "--dense-steps", "1", "--no-cpu-baseline", "--no-profile", "--full"]
     rc, out, err = launch.run(cmd, cwd=root, timeout=300)
     assert rc == 0, err[-4000:]
     line = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1])
@@ -504,7 +504,7 @@ def test_bench_one_rank_gradient_buckets_through_the_librarys_rccl_binding():
     for direct in ("0", "1"):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                "--master-port", str(launch.free_port()), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-               "--clips-per-gpu", "16", "--dense-steps", "0", "--no-cpu-baseline", "--no-profile", "--seed", "4242"]
+               "--clips-per-gpu", "16", "--dense-steps", "0", "--no-cpu-baseline", "--no-profile", "--seed", "4242", "--full"]
         rc, out, err = launch.run(cmd, cwd=root, env=dict(os.environ, WJ_RCCL_DIRECT=direct), timeout=300)
         assert rc == 0, err[-4000:]
         lines[direct] = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1])
@@ -544,6 +544,35 @@ def test_bench_emulated_allreduce_footprint_on_one_gpu():
     assert abs(a["final_loss"] - b["final_loss"]) < 2e-4 * abs(a["final_loss"]), (a["final_loss"], b["final_loss"])
 
 
+def test_bench_plain_run_leaves_the_full_legs_out():
+    """A plain bench.py run is set-up, warm-up, timed steps and the line: the legs that --full adds (calibration launches, dense-shape
+    block, instrumented step, CPU baseline) never start and their fields are null.  With --full they run and fill them, and the timed
+    steps are the same: same seed, same loss up to the fp32-atomic noise of the weight gradients."""
+    import json
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, errs = {}, {}
+    for full in (False, True):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--clips-per-gpu", "16", "--seed", "99"]
+        cmd += ["--full", "--dense-steps", "1", "--no-cpu-baseline"] if full else []
+        env = dict(os.environ)
+        for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+            env.pop(k, None)
+        rc, out, err = launch.run(cmd, cwd=root, env=env, timeout=300)
+        assert rc == 0, err[-4000:]
+        lines[full], errs[full] = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1]), err
+    a, b = lines[False], lines[True]
+    for stage in ("calibration launches", "dense-shape block", "instrumented step"):
+        assert stage not in errs[False] and stage in errs[True], stage
+    assert "CPU oracle" not in errs[False]
+    for k in ("roofline", "calibration", "ms_per_step_at_reference_box", "dense_ms_per_step", "model_tflops_per_gpu", "param_checksum"):
+        assert a[k] is None and b[k] is not None, k
+    assert "cpu_baseline" not in a
+    assert a["metric"] == "jepa_pretrain_clips_per_sec" and a["unit"] == "clips/s" and a["dtype"] == "bf16" and a["higher_is_better"] is True
+    assert a["steps"] == 2 and a["warmup"] == 1 and abs(a["value"] - 16 / (a["ms_per_step"] * 1e-3)) < 1e-2 * a["value"]
+    assert abs(a["final_loss"] - b["final_loss"]) < 2e-4 * abs(a["final_loss"]), (a["final_loss"], b["final_loss"])
+
+
 def test_bench_two_ranks_share_the_gpu_over_gloo():
     """The N = 2 launch of the bench end to end on the 1-GPU box: RCCL refuses two ranks on one device, so the collectives go over
     gloo (WJ_DIST_BACKEND, a development switch of init_distributed); everything else -- per-rank sources, broadcast, bucketed
@@ -553,7 +582,7 @@ def test_bench_two_ranks_share_the_gpu_over_gloo():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(launch.free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--clips-per-gpu", "16",
-           "--dense-steps", "0", "--no-cpu-baseline", "--no-profile"]
+           "--dense-steps", "0", "--no-cpu-baseline", "--no-profile", "--full"]
     rc, out, err = launch.run(cmd, cwd=root, env=dict(os.environ, WJ_DIST_BACKEND="gloo"), timeout=300)
     assert rc == 0, err[-4000:]
     lines = [ln for ln in out.splitlines() if ln.startswith("{")]

@@ -23,7 +23,7 @@ for cfg in "$@"; do
     [ -n "$f" ] && cp "$f" "$out/run_kernel_stats.csv" && python3 tools/serial_sum.py "$out/run_kernel_stats.csv" > "$out/serial_sum.txt"
     rm -rf "$out/prof"                      # the per-launch trace is not needed; keep the merged-back payload small
     WJ_SIDE_STREAM=0 python3 bench.py --steps 20 --warmup 5 --no-profile $common > "$out/step_1s.json" 2> "$out/step_1s.err"
-    python3 bench.py --steps 20 --warmup 5 $common > "$out/step_2s.json" 2> "$out/step_2s.err"
+    python3 bench.py --full --steps 20 --warmup 5 $common > "$out/step_2s.json" 2> "$out/step_2s.err"
     cp gpurun_out/bench_gemm_shapes.json "$out/gemm_shapes.json" 2>/dev/null
     cp gpurun_out/bench_kernel_classes.json "$out/kernel_classes.json" 2>/dev/null
   )

@@ -15,7 +15,7 @@ rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $out/pmc_write -o runc --output-for
 python3 tools/pmc_traffic.py $out/pmc_fetch $out/pmc_write $out/pmc_traffic.json > $out/pmc_traffic.txt 2>&1; rm -rf $out/pmc_fetch $out/pmc_write
 cp $out/pmc_traffic.json profiles/r04_pmc_traffic.json; cp $out/bench_kernel_stats_serial.csv profiles/r04_bench_kernel_stats_serial.csv   # what the bench line reads
 # 3. the default bench line (with the CPU baseline), and one stream only
-python3 bench.py > $out/bench.json 2> $out/bench.err
+python3 bench.py --full > $out/bench.json 2> $out/bench.err
 cp gpurun_out/bench_gemm_shapes.json $out/bench_gemm_shapes.json; cp gpurun_out/bench_kernel_classes.json $out/bench_kernel_classes.json
 WJ_SIDE_STREAM=0 python3 bench.py $common --no-profile > $out/bench_one_stream.json 2> $out/bench_one_stream.err
 # 4. GEMM screens

@@ -18,7 +18,7 @@ WJ_PERSIST_WBLOCK=0 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $out/pmc_fetch0
 python3 tools/pmc_traffic.py $out/pmc_fetch0 $out/pmc_fetch0 $out/pmc_traffic_wblock_off.json > /dev/null 2>&1; rm -rf $out/pmc_fetch0
 cp $out/pmc_traffic.json profiles/r05_pmc_traffic.json      # what the bench line's `traffic` reads
 # 3. the default bench line (with the CPU baseline), and one stream only
-python3 bench.py > $out/bench.json 2> $out/bench.err
+python3 bench.py --full > $out/bench.json 2> $out/bench.err
 cp gpurun_out/bench_gemm_shapes.json $out/bench_gemm_shapes.json; cp gpurun_out/bench_kernel_classes.json $out/bench_kernel_classes.json
 WJ_SIDE_STREAM=0 python3 bench.py $common --no-profile > $out/bench_one_stream.json 2> $out/bench_one_stream.err
 # 4. GEMM screens

@@ -14,10 +14,10 @@ rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $out/pmc_fetch -o runc --output-for
 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $out/pmc_write -o runc --output-format csv -- python3 bench.py --steps 3 --warmup 2 --no-profile --no-calibration $common > $out/pmc_write.log 2>&1
 python3 tools/pmc_traffic.py $out/pmc_fetch $out/pmc_write $out/pmc_traffic.json > $out/pmc_traffic.txt 2>&1; rm -rf $out/pmc_fetch $out/pmc_write
 # 3. the default bench line (with calibration and the CPU baseline), three more without the baseline, and one stream only
-python3 bench.py > $out/bench.json 2> $out/bench.err
+python3 bench.py --full > $out/bench.json 2> $out/bench.err
 cp gpurun_out/bench_gemm_shapes.json $out/bench_gemm_shapes.json; cp gpurun_out/bench_kernel_classes.json $out/bench_kernel_classes.json
-for i in 1 2 3; do python3 bench.py --no-cpu-baseline --no-profile --dense-steps 0 2>/dev/null | tail -1; done > $out/bench_same_box_x3.json
-WJ_SIDE_STREAM=0 python3 bench.py $common --no-profile > $out/bench_one_stream.json 2> $out/bench_one_stream.err
+for i in 1 2 3; do python3 bench.py --full --no-cpu-baseline --no-profile --dense-steps 0 2>/dev/null | tail -1; done > $out/bench_same_box_x3.json
+WJ_SIDE_STREAM=0 python3 bench.py --full $common --no-profile > $out/bench_one_stream.json 2> $out/bench_one_stream.err
 # 4. GEMM screens (laboratory library)
 timeout 600 python3 tools/gemm_check.py 3 4 4 > $out/gemm_check_3_4.log 2>&1
 timeout 200 python3 tools/panel_bench.py > $out/panel_bench.log 2>&1
@@ -25,6 +25,6 @@ timeout 200 python3 tools/panel_bench.py > $out/panel_bench.log 2>&1
 timeout 1500 python3 -m pytest tests -m gpu -q > $out/gputest.log 2>&1; tail -3 $out/gputest.log
 WJ_ARENA_FILL=nan timeout 1500 python3 -m pytest tests -m gpu -q > $out/gputest_nan_arena.log 2>&1; tail -3 $out/gputest_nan_arena.log
 # 6. the other workloads and the trainer
-for w in 4s-bf16 4s-fp8 2s-nat; do python3 bench.py --workload $w --steps 10 --no-cpu-baseline --no-profile --dense-steps 0 2>/dev/null | tail -1; done > $out/other_workloads.json
+for w in 4s-bf16 4s-fp8 2s-nat; do python3 bench.py --full --workload $w --steps 10 --no-cpu-baseline --no-profile --dense-steps 0 2>/dev/null | tail -1; done > $out/other_workloads.json
 timeout 600 python3 train.py trainer.steps=3000 trainer.warmup_steps=500 trainer.log_every_n_steps=250 save_dir=/tmp/r6_runs > $out/train_3000steps.log 2>&1
 head -2 $out/serial_sum.txt; tail -1 $out/bench.json | cut -c1-300; cat $out/bench_same_box_x3.json | cut -c1-120; tail -1 $out/bench_one_stream.json | cut -c1-200
