@@ -126,7 +126,8 @@ def gemm(A: Ptr, B: Ptr, C: Ptr, *, M: int, N: int, K: int, lda: int, ldb: int, 
          workspace: Optional[torch.Tensor] = None, schedule: Optional[int] = None, persist_cus: Optional[int] = None,
          stream: Optional[int] = None) -> None:
     """workspace: a zero-initialised byte tensor the library may use for K-split pairs (see include/wavjepa_hip.h: wj_gemm_args).
-    schedule: force tile / schedule variant 0..4 for this call (None: this binding's default, gemm_set_variant; -1: the library picks);
+    schedule: force tile / schedule variant 0..6 for this call (None: this binding's default, gemm_set_variant; -1: the library picks;
+    a variant that cannot run the shape falls back, see the header);
     persist_cus: resident persistent-GEMM workgroups per XCD (None: this binding's default, gemm_set_persist_cus)."""
     sched = _GEMM_SCHEDULE if schedule is None else int(schedule)
     _run("wj_gemm_bf16", "wj_gemm_args", stream, A=_p(A), B=_p(B), C=_p(C), C2=_p(C2), bias=_p(bias), aux=_p(aux), colsum=_p(colsum),
@@ -179,7 +180,7 @@ def wgrad_grouped(problems, stream: Optional[int] = None) -> None:
 
 # Defaults this BINDING fills into wj_gemm_args.schedule / .persist_cus of every gemm() call that does not name them.  The library itself
 # keeps no such state (round 5's wj_gemm_set_variant / wj_gemm_set_persist_cus were process-global setters behind a re-entrant ABI).
-_GEMM_SCHEDULE = -1      # -1: the library picks; 0..4: force that variant (tests, tools/gemm_check.py)
+_GEMM_SCHEDULE = -1      # -1: the library picks; 0..6: force that variant (tests, tools/gemm_check.py)
 _PERSIST_CUS = 0         # 0: the library's default (32, or WJ_PERSIST_CUS); 1..32: resident persistent-GEMM workgroups per XCD
 
 
