@@ -262,6 +262,10 @@ int wj_ln_bwd_partial_rows(int M, int D);
  * of qkv / out / dout / dqkv, every key attended (key_mask must be NULL), T = upper bound of the lengths, and
  * lse: f32 [rows][H].  This is how the student / predictor run on their visible tokens only: a key-masked query row
  * that nobody reads (jepa.py:399 keeps ~ctx_masks rows; the loss keeps target rows, jepa.py:356) is never computed.
+ * A query row ALL of whose keys are masked (a fully masked sequence): out = 0 and lse = +inf (softmax math yields NaN there), and
+ * the backward gives it dq = 0 and takes nothing from it into dk, dv or dbias.  Masked keys get dk = dv = 0 exactly.
+ * wj_attn_bwd recomputes p = exp(score - lse) from the stored lse; masked and padding keys are removed inside the exponent, so the
+ * gradient stays finite however far such a key's score lies above its row's lse (tests/test_attention_census_gpu.py, extreme regime).
  * -----------------------------------------------------------------------------------------------------------*/
 typedef struct {
     const void* qkv;

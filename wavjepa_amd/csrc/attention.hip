@@ -240,6 +240,14 @@ __global__ __launch_bounds__(NWF * 64, MT == 14 ? 4 : (MT == 8 ? (HD == 64 ? 4 :
 }
 
 // ------------------------------------------------------------------------------------------------ backward
+// Masked and padding keys in the backward.  Every backward kernel recomputes p = exp(s * scale - lse).  An attended key has
+// s * scale <= lse, so p <= 1; a masked key may score above its row's lse, and a padding key (zero K row, score 0) sits above a negative
+// lse: from a gap of 88.7 on exp overflows fp32.  Zeroing such a key by a PRODUCT with 0, or relying on its zero K / V rows, then gives
+// 0 * inf or inf * 0 = NaN (measured: NaN in dq / dk / dv from |q|, |k| elements of 3.5 aligned over a 64-wide head, 4.25 over 32).
+// So the mask goes INTO the exponent: kvalid holds 0 for an attended key and -inf for a masked or padding one and is added in front of
+// the exp2 (a v_sub_f32 for the v_mul_f32; the general kernel works in the exp2 domain as the frag kernels do).  Without a key mask the frag kernels have no
+// kvalid in their loop; there the exponent is clamped at 0 (one v_min_f32), which an attended key never exceeds by more than its
+// last place, and the finite p of a padding key meets the zero K / V rows as before.
 template <int HD, int NWB, int MT, int HG = HD>
 __global__ __launch_bounds__(NWB * 64, MT > 14 ? 2 : (HD == 64 ? 3 : 4)) void attn_bwd_kernel(wj_attn_bwd_args a) {
     constexpr int RS = Img<HD>::RS, KS = HD / 32, DT = HG / 16;
@@ -256,9 +264,9 @@ __global__ __launch_bounds__(NWB * 64, MT > 14 ? 2 : (HD == 64 ? 3 : 4)) void at
     const int nt = (T + 15) / 16, KP = ((T + 31) / 32) * 32, nch = KP / 32;
     char* img0 = smem;                // phase A: K      phase B: Q
     char* img1 = smem + KP * RS;      // phase A: V      phase B: dO
-    float* lse_s = reinterpret_cast<float*>(smem + 2 * KP * RS);  // [KP]  (+inf for rows >= T)
+    float* lse_s = reinterpret_cast<float*>(smem + 2 * KP * RS);  // [KP]  lse * log2 e (+inf for rows >= T)
     float* delta = lse_s + KP;                                     // [KP]
-    float* kvalid = delta + KP;                                    // [KP]  1 = key attended, 0 = masked / padding
+    float* kvalid = delta + KP;                                    // [KP]  0 = key attended, -inf = masked / padding (added to the exponent)
     float* bsum = kvalid + KP;                                     // [3*HD] column sums of dq | dk | dv (in_proj_bias grad)
     for (int x = threadIdx.x; x < 3 * HD; x += blockDim.x) bsum[x] = 0.f;
 
@@ -277,10 +285,10 @@ __global__ __launch_bounds__(NWB * 64, MT > 14 ? 2 : (HD == 64 ? 3 : 4)) void at
     RowRegs<HD, NWB, MT, HG> nxt;
     if constexpr (EARLY) nxt.load(qkv, ld, dO, D, T);
     for (int r = threadIdx.x; r < KP; r += blockDim.x) {
-        float l = INFINITY, dl = 0.f, kv = 0.f;
+        float l = INFINITY, dl = 0.f, kv = -INFINITY;
         if (r < T) {
-            l = a.lse[a.seq_off ? (row0 + r) * H + h : ((long)b * H + h) * T + r];
-            kv = (km && km[r]) ? 0.f : 1.f;
+            l = a.lse[a.seq_off ? (row0 + r) * H + h : ((long)b * H + h) * T + r] * LOG2E;   // exp2 domain, as the frag kernels
+            kv = (km && km[r]) ? -INFINITY : 0.f;
 #pragma unroll
             for (int c = 0; c < HG / 8; ++c) {
                 const bf16x8 x = *reinterpret_cast<const bf16x8*>(dO + (long)r * D + c * 8);
@@ -292,7 +300,7 @@ __global__ __launch_bounds__(NWB * 64, MT > 14 ? 2 : (HD == 64 ? 3 : 4)) void at
         lse_s[r] = l; delta[r] = dl; kvalid[r] = kv;
     }
     __syncthreads();
-    const float scale = rsqrtf((float)HG);
+    const float scale = rsqrtf((float)HG), scale2 = scale * LOG2E;
     const f32x4 zero4 = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // ---- phase A: dQ for 16 queries per wave iteration (queries on the lane, keys on the accumulator rows)
@@ -334,7 +342,7 @@ __global__ __launch_bounds__(NWB * 64, MT > 14 ? 2 : (HD == 64 ? 3 : 4)) void at
                         const f32x4 kv = *reinterpret_cast<const f32x4*>(kvalid + kt * 16 + 4 * g);
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            const float p = kv[r] * __expf(s[r] * scale - my_lse);
+                            const float p = __builtin_amdgcn_exp2f(fmaf(s[r], scale2, kv[r] - my_lse));   // kv: 0 / -inf, see the note above
                             ds2[u][r] = p * (dp[r] - my_delta) * scale;
                         }
                     }
@@ -413,7 +421,7 @@ __global__ __launch_bounds__(NWB * 64, MT > 14 ? 2 : (HD == 64 ? 3 : 4)) void at
                         const f32x4 d4 = *reinterpret_cast<const f32x4*>(delta + qt * 16 + 4 * g);
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            const float p = my_kv * __expf(s[r] * scale - l4[r]);
+                            const float p = __builtin_amdgcn_exp2f(fmaf(s[r], scale2, my_kv - l4[r]));
                             p2[u][r] = p;
                             ds2[u][r] = p * (dp[r] - d4[r]) * scale;
                         }
@@ -524,10 +532,10 @@ __global__ __launch_bounds__(NWB * 64, HD == 64 ? 3 : 4) void attn_bwd_frag_kern
                 dofr[t][ks] = row_frag_global(dO, D, rb, T, ks, lane, HG);
                 ofr[t][ks] = row_frag_global(O, D, rb, T, ks, lane, HG);
             }
-            lse_r[t] = INFINITY; kv_r[t] = 0.f;
+            lse_r[t] = INFINITY; kv_r[t] = -INFINITY;
             if (row < T) {
                 lse_r[t] = a.lse[a.seq_off ? (row0 + row) * H + h : ((long)b * H + h) * T + row] * LOG2E;
-                kv_r[t] = (km && km[row]) ? 0.f : 1.f;
+                kv_r[t] = (km && km[row]) ? -INFINITY : 0.f;
             }
         }
 #pragma unroll
@@ -587,8 +595,9 @@ __global__ __launch_bounds__(NWB * 64, HD == 64 ? 3 : 4) void attn_bwd_frag_kern
                             if constexpr (MASKED) kv = *reinterpret_cast<const f32x4*>(kvalid + kt * 16 + 4 * g);
 #pragma unroll
                             for (int r = 0; r < 4; ++r) {
-                                float p = __builtin_amdgcn_exp2f(fmaf(s[r], scale2, -lse_r[t]));
-                                if constexpr (MASKED) p *= kv[r];
+                                float p;
+                                if constexpr (MASKED) p = __builtin_amdgcn_exp2f(fmaf(s[r], scale2, kv[r] - lse_r[t]));
+                                else p = __builtin_amdgcn_exp2f(fminf(fmaf(s[r], scale2, -lse_r[t]), 0.f));
                                 ds2[u][r] = p * (dp[r] - delta_r[t]);
                             }
                         }
@@ -667,8 +676,9 @@ __global__ __launch_bounds__(NWB * 64, HD == 64 ? 3 : 4) void attn_bwd_frag_kern
                             const f32x4 d4 = *reinterpret_cast<const f32x4*>(delta + qt * 16 + 4 * g);
 #pragma unroll
                             for (int r = 0; r < 4; ++r) {
-                                float p = __builtin_amdgcn_exp2f(fmaf(s[r], scale2, -l4[r]));
-                                if constexpr (MASKED) p *= kv_r[t];
+                                float p;
+                                if constexpr (MASKED) p = __builtin_amdgcn_exp2f(fmaf(s[r], scale2, kv_r[t] - l4[r]));
+                                else p = __builtin_amdgcn_exp2f(fminf(fmaf(s[r], scale2, -l4[r]), 0.f));
                                 p2[u][r] = p;
                                 ds2[u][r] = p * (dp[r] - d4[r]);
                             }
