@@ -44,6 +44,7 @@ def setup_trainer(cfg) -> Trainer:
     return Trainer(accelerator=cfg.trainer.accelerator, max_epochs=cfg.trainer.epochs, max_steps=cfg.trainer.steps,
                    precision=cfg.trainer.precision, devices=int(cfg.trainer.num_gpus), gradient_clip_val=1.0, gradient_clip_algorithm="norm",
                    log_every_n_steps=cfg.trainer.get("log_every_n_steps", 1),
+                   deterministic=bool(cfg.trainer.get("deterministic", False)),
                    default_root_dir=checkpoint_dir(cfg, "saved_models_jepa_denoised", get_identity_from_cfg_denoise(cfg)),
                    checkpoint_every_n_steps=2500)
 

@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define WJ_ABI_VERSION 16
+#define WJ_ABI_VERSION 17
 int wj_abi_version(void);
 /* Number of HIP devices visible (0 on a CPU-only host); never initialises a context beyond hipGetDeviceCount. */
 int wj_device_count(void);
@@ -90,6 +90,19 @@ typedef struct {
                                 WJ_PERSIST_CUS environment variable read once at the first launch).  A data-parallel run (train.py:174-179:
                                 DDP over 8 GPUs) passes 28 so that the RCCL channel kernels of the gradient all-reduce find free CUs while a
                                 persistent GEMM of the backward is resident -- a 150-KiB-LDS workgroup on every CU leaves them none. */
+    int32_t deterministic;   /* ABI 17.  0: as before.  1: WJ_EPI_ATOMIC_F32 with a_trans = b_trans = 1 (rowmap form included) adds its K slices
+                                in a FIXED order instead of by float atomics.  The launch splits K into S slices exactly as the atomic form does
+                                (S follows from M, N, K, split_k and the build only -- never from arrival order, the stream, persist_cus or what
+                                else is resident).  With S > 1 every slice s STORES its fp32 tile into slab s of `workspace`, laid out
+                                [S][M][ldc] floats, and a second launch on the same stream forms t = P_0; t += P_s (s = 1 .. S-1) in fp32, in
+                                that order, and writes C = C + alpha * t: no workgroup waits for another.  With S == 1 the atomic epilogue has
+                                one adder per element (stream-ordered) and runs as it is.  `workspace` holds
+                                wj_workspace_bytes("wj_gemm_bf16", args) = S * M * ldc * 4 bytes (0 for S == 1; query and launch agree on S),
+                                16-byte aligned; it need NOT be zero-filled or preserved between launches, and two launches in flight must not
+                                share it.  Missing or too small: WJ_ERR_ARG, never a fall-back to atomics.  Results are bit-identical from run
+                                to run on one build and GPU model (not across builds).  `schedule` is ignored in this form; row-form wgrads
+                                with split_k > 1: WJ_ERR_UNSUPPORTED.  The fused `colsum` is a float atomic per row tile: WJ_ERR_ARG with
+                                deterministic (use wj_colsum_bf16's deterministic form on the output instead). */
 } wj_gemm_args;
 int wj_gemm_bf16(const wj_gemm_args*, void* stream);
 /* Optional: tell the library that `stream` is being retired (call before hipStreamDestroy, with none of its GEMMs in flight).  The persistent
@@ -144,6 +157,14 @@ typedef struct {
     int64_t lda[8], ldb[8], ldc[8];
     int32_t M[8], N[8], K[8];
     int32_t n;
+    void* workspace;         /* ABI 17, deterministic form only: wj_workspace_bytes("wj_wgrad_grouped", args) bytes, 16-byte aligned; need not be */
+    int64_t workspace_bytes; /* zero-filled or preserved; one per launch in flight                                                                */
+    int32_t deterministic;   /* ABI 17.  0: as before (atomics).  1: the store-and-sum form of wj_gemm_args.deterministic for the whole group: the
+                                launch picks its split factors S_x as before (from the shapes of the group and the build only).  If every
+                                S_x == 1 the atomic epilogue has one adder per element and runs as it is (need 0).  Otherwise every problem x
+                                stores its slices into slabs [S_x][M_x][ldc_x] floats, laid out back to back in `workspace` (need = the sum of
+                                S_x * M_x * ldc_x * 4), and ONE second launch on the same stream adds each problem's slabs in slice order into
+                                C_x.  Missing / short workspace: WJ_ERR_ARG. */
 } wj_wgrad_group_args;
 int wj_wgrad_grouped(const wj_wgrad_group_args*, void* stream);
 
@@ -226,6 +247,11 @@ typedef struct {
     float* out;
     int64_t ldx;
     int32_t M, N;
+    float* workspace;        /* ABI 17, deterministic wj_colsum_bf16 only: wj_workspace_bytes("wj_colsum_bf16", args) bytes ([row ranges][N] f32 */
+    int64_t workspace_bytes; /* partial rows, plain stores; need not be zero-filled or preserved)                                                */
+    int32_t deterministic;   /* ABI 17.  0: as before.  1: every column has ONE adder that walks the rows (wj_colsum_f32) or the partial rows of
+                                the row ranges (wj_colsum_bf16: two launches on the same stream) in ascending order: bit-identical from run to
+                                run.  wj_colsum_bf16 without / with a short workspace: WJ_ERR_ARG.  wj_colsum_f32 needs no workspace. */
 } wj_colsum_args;
 int wj_colsum_bf16(const wj_colsum_args*, void* stream);
 /* same for an f32 matrix (x: f32 [M][N], ldx in elements): folds per-workgroup partial sums */
@@ -245,6 +271,8 @@ typedef struct {
     int64_t ldx[WJ_COLSUM_GROUP_MAX];
     int32_t M[WJ_COLSUM_GROUP_MAX], N[WJ_COLSUM_GROUP_MAX], n_each[WJ_COLSUM_GROUP_MAX];
     int32_t n;
+    int32_t deterministic;   /* ABI 17.  1: one adder per column walks all M rows in ascending order (the partial matrices are a few hundred rows)
+                                instead of 8 row ranges meeting in a float atomic */
 } wj_colsum_group_args;
 int wj_colsum_f32_group(const wj_colsum_group_args*, void* stream);
 /* rows of partials wj_layernorm_bwd writes for M token rows of width D (its workgroup count); no stream, no device work */
@@ -291,6 +319,9 @@ typedef struct {
     int32_t B, T, H, hd;
     int32_t mask_group;
     int32_t defer_fold; /* 1: leave the partials in dbias_ws (rows = B, width 3*H*hd) for a later wj_colsum_f32_group into dbias */
+    int32_t deterministic; /* ABI 17.  1: the per-(b, h) column sums of dq / dk / dv are added across the waves of a workgroup in wave order
+                              (per-wave partials in LDS) instead of by LDS float atomics, and the fold into dbias (without defer_fold) has one
+                              adder per column: dbias_ws and dbias are bit-identical from run to run.  dqkv is the same either way. */
 } wj_attn_bwd_args;
 int wj_attn_bwd(const wj_attn_bwd_args*, void* stream);
 
@@ -515,7 +546,8 @@ int wj_masked_mse(const wj_mse_args*, void* stream);
 /* ------------------------------------------------------------------------------------------------------------
  * Workspace sizes.  The library never allocates: entry points that need scratch take a `workspace` pointer, and this
  * query tells the caller how many BYTES the call described by the SAME argument struct needs (pointers in it are
- * ignored).  `fn` is the entry point's name: "wj_layernorm_bwd", "wj_attn_bwd" (its dbias_ws), "wj_conv0_gn_gelu_fwd",
+ * ignored).  `fn` is the entry point's name: "wj_gemm_bf16" / "wj_wgrad_grouped" / "wj_colsum_bf16" (the K-split pair scratch, or with
+ * `deterministic` the slabs / partial rows of the store-and-sum forms), "wj_layernorm_bwd", "wj_attn_bwd" (its dbias_ws), "wj_conv0_gn_gelu_fwd",
  * "wj_conv0_gn_gelu_bwd", "wj_masked_mse", "wj_grad_sumsq".  Returns 0 for entry points without scratch, -1 for an unknown
  * name or NULL arguments.
  * -----------------------------------------------------------------------------------------------------------*/

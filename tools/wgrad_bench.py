@@ -54,3 +54,31 @@ for tag, d, m, nl in (("student", 768, 10300, 2), ("predictor", 384, 87916, 1), 
         t2 = timeit(all_layers)
         line += f" | grouped {nl} layers {t2 * 1e3:7.1f} us {fl / t2 / 1e9:6.1f} TF"
     print(line)
+
+
+# ---- deterministic (store-and-sum) against atomic form, in isolation: one predictor layer's grouped launch, one sparse conv gather wgrad
+def det_vs_atomic():
+    L = layer(384, 87071)
+    need = ops.wgrad_grouped_workspace_bytes(L)
+    ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    ta = timeit(lambda: ops.wgrad_grouped(L))
+    td = timeit(lambda: ops.wgrad_grouped(L, workspace=ws, deterministic=True))
+    print(f"predictor layer grouped wgrad (d=384, 87071 rows): atomic {ta * 1e3:7.1f} us | deterministic {td * 1e3:7.1f} us | slabs {need / 2**20:.1f} MiB")
+    C, k, s, n_act, rows = 512, 3, 2, 91506, 410000
+    dpre = torch.randn(rows, C, device=dev).to(bf)
+    post = torch.randn(rows * s + k, C, device=dev).to(bf)        # (the gather reads row r of dpre and rows s r .. of the layer below: here a flat buffer)
+    act = torch.sort(torch.randperm(rows // s - 2, device=dev)[:n_act])[0].to(torch.int32)
+    act = torch.cat([act, act[-1:].expand(256)]).contiguous()
+    dw = torch.zeros(C, k * C, device=dev)
+    kw = dict(M=C, N=k * C, K=n_act, lda=C, ldb=s * C, ldc=k * C, a_trans=1, b_trans=1, epilogue=ops.EPI_ATOMIC_F32,
+              split_k=ops.pick_split_k(C, k * C, n_act), rowmap=act)
+    need = ops.workspace_bytes("wj_gemm_bf16", M=C, N=k * C, K=n_act, ldc=k * C, a_trans=1, b_trans=1, epilogue=ops.EPI_ATOMIC_F32,
+                               split_k=kw["split_k"], deterministic=1)
+    ws2 = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    ta = timeit(lambda: ops.gemm(dpre, post, dw, **kw))
+    td = timeit(lambda: ops.gemm(dpre, post, dw, workspace=ws2, deterministic=True, **kw))
+    print(f"sparse conv wgrad (512 x 1536, {n_act} listed rows, split {kw['split_k']}): atomic {ta * 1e3:7.1f} us | deterministic {td * 1e3:7.1f} us | "
+          f"slabs {need / 2**20:.1f} MiB")
+
+
+det_vs_atomic()

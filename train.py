@@ -83,6 +83,7 @@ def setup_trainer(cfg) -> Trainer:
                    precision=cfg.trainer.precision, devices=int(cfg.trainer.num_gpus), gradient_clip_val=5,
                    gradient_clip_algorithm="norm", strategy="ddp" if int(cfg.trainer.num_gpus) > 1 else "auto",
                    log_every_n_steps=cfg.trainer.get("log_every_n_steps", 50),
+                   deterministic=bool(cfg.trainer.get("deterministic", False)),     # the reference passes deterministic=False (train.py:170)
                    checkpoint_every_n_steps=25000,      # ModelCheckpoint(every_n_train_steps=25000, save_last=True), reference train.py:146-153
                    default_root_dir=checkpoint_dir(cfg, "saved_models_jepa_new_masking", get_identity_from_cfg(cfg)))
 
@@ -122,7 +123,14 @@ def main(argv=None):
         trainer = setup_trainer(cfg)
         model, patches = build_model(cfg)
         device = torch.device("cuda", trainer.local_rank)
-        source = create_data_source(cfg, patches, device, trainer.rank)
+        if trainer.deterministic:
+            # a repeatable run also needs repeatable masks: the synthetic sources draw their mask sets once, here, from seeded generators
+            # (the maskers otherwise use OS entropy, as upstream; shard loaders draw per batch in their workers and are not pinned)
+            from wavjepa_amd.data import pinned_mask_draws
+            with pinned_mask_draws(int(cfg.seed) + trainer.rank):
+                source = create_data_source(cfg, patches, device, trainer.rank)
+        else:
+            source = create_data_source(cfg, patches, device, trainer.rank)
         if trainer.rank == 0:
             print(f"Effective Batch Size is: {cfg.trainer.batch_size * cfg.data.samples_per_audio * cfg.trainer.num_gpus}")
         trainer.fit(model, train_dataloaders=source)

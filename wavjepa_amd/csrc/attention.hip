@@ -248,7 +248,10 @@ __global__ __launch_bounds__(NWF * 64, MT == 14 ? 4 : (MT == 8 ? (HD == 64 ? 4 :
 // the exp2 (a v_sub_f32 for the v_mul_f32; the general kernel works in the exp2 domain as the frag kernels do).  Without a key mask the frag kernels have no
 // kvalid in their loop; there the exponent is clamped at 0 (one v_min_f32), which an attended key never exceeds by more than its
 // last place, and the finite p of a padding key meets the zero K / V rows as before.
-template <int HD, int NWB, int MT, int HG = HD>
+// DET (wj_attn_bwd_args.deterministic; a separate instantiation, the default one is untouched): the column sums of dq / dk / dv are kept
+// per WAVE in LDS (bsum [NWB][3*HD], plain stores) and added in wave order when the workgroup stores its dbias_ws row, instead of meeting
+// in LDS float atomics whose order follows wave timing.
+template <int HD, int NWB, int MT, int HG = HD, bool DET = false>
 __global__ __launch_bounds__(NWB * 64, MT > 14 ? 2 : (HD == 64 ? 3 : 4)) void attn_bwd_kernel(wj_attn_bwd_args a) {
     constexpr int RS = Img<HD>::RS, KS = HD / 32, DT = HG / 16;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -268,7 +271,7 @@ __global__ __launch_bounds__(NWB * 64, MT > 14 ? 2 : (HD == 64 ? 3 : 4)) void at
     float* delta = lse_s + KP;                                     // [KP]
     float* kvalid = delta + KP;                                    // [KP]  0 = key attended, -inf = masked / padding (added to the exponent)
     float* bsum = kvalid + KP;                                     // [3*HD] column sums of dq | dk | dv (in_proj_bias grad)
-    for (int x = threadIdx.x; x < 3 * HD; x += blockDim.x) bsum[x] = 0.f;
+    for (int x = threadIdx.x; x < (DET ? NWB : 1) * 3 * HD; x += blockDim.x) bsum[x] = 0.f;
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
     const long ld = 3L * D;
@@ -373,7 +376,10 @@ __global__ __launch_bounds__(NWB * 64, MT > 14 ? 2 : (HD == 64 ? 3 : 4)) void at
             for (int r = 0; r < 4; ++r) {
                 float v = csq[dt][r];
                 v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64);
-                if (i == 0) atomicAdd(bsum + dt * 16 + 4 * g + r, v);
+                if (i == 0) {
+                    if constexpr (DET) bsum[wave * 3 * HD + dt * 16 + 4 * g + r] = v;
+                    else atomicAdd(bsum + dt * 16 + 4 * g + r, v);
+                }
             }
     }
     __syncthreads();
@@ -464,8 +470,13 @@ __global__ __launch_bounds__(NWB * 64, MT > 14 ? 2 : (HD == 64 ? 3 : 4)) void at
                 v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64);
                 u += __shfl_xor(u, 1, 64); u += __shfl_xor(u, 2, 64); u += __shfl_xor(u, 4, 64); u += __shfl_xor(u, 8, 64);
                 if (i == 0) {
-                    atomicAdd(bsum + HD + dt * 16 + 4 * g + r, v);
-                    atomicAdd(bsum + 2 * HD + dt * 16 + 4 * g + r, u);
+                    if constexpr (DET) {
+                        bsum[wave * 3 * HD + HD + dt * 16 + 4 * g + r] = v;
+                        bsum[wave * 3 * HD + 2 * HD + dt * 16 + 4 * g + r] = u;
+                    } else {
+                        atomicAdd(bsum + HD + dt * 16 + 4 * g + r, v);
+                        atomicAdd(bsum + 2 * HD + dt * 16 + 4 * g + r, u);
+                    }
                 }
             }
         __syncthreads();
@@ -473,7 +484,12 @@ __global__ __launch_bounds__(NWB * 64, MT > 14 ? 2 : (HD == 64 ? 3 : 4)) void at
         // into the same 3*D addresses cost 70-80 us per launch)
         for (int x = threadIdx.x; x < 3 * HD; x += blockDim.x) {
             const int part = x / HD, d = x - part * HD;
-            if (d < HG) a.dbias_ws[(long)b * 3 * D + part * D + h * HG + d] = bsum[x];
+            float tot = bsum[x];
+            if constexpr (DET) {
+#pragma unroll
+                for (int w = 1; w < NWB; ++w) tot += bsum[w * 3 * HD + x];
+            }
+            if (d < HG) a.dbias_ws[(long)b * 3 * D + part * D + h * HG + d] = tot;
         }
     }
 }
@@ -486,7 +502,7 @@ __global__ __launch_bounds__(NWB * 64, MT > 14 ? 2 : (HD == 64 ? 3 : 4)) void at
 //   * the K / V fragments are written to the LDS images for phase A and stay in registers as phase B's own-tile operands,
 //   * the Q / dO fragments are phase A's own-tile operands and are written to the images once phase A is done,
 //   * delta = rowsum(dO . O) falls out of the dO / O fragments with two cross-lane adds.
-template <int HD, int NWB, int MT, bool MASKED, int HG = HD>
+template <int HD, int NWB, int MT, bool MASKED, int HG = HD, bool DET = false>
 __global__ __launch_bounds__(NWB * 64, HD == 64 ? 3 : 4) void attn_bwd_frag_kernel(wj_attn_bwd_args a) {
     constexpr int RS = Img<HD>::RS, KS = HD / 32, DT = HG / 16, TPW = MT / NWB;
     static_assert(MT % NWB == 0, "tiles are dealt to waves round-robin");
@@ -507,7 +523,7 @@ __global__ __launch_bounds__(NWB * 64, HD == 64 ? 3 : 4) void attn_bwd_frag_kern
     float* delta = lse_s + KP;
     float* kvalid = delta + KP;
     float* bsum = kvalid + KP;
-    for (int x = threadIdx.x; x < 3 * HD; x += blockDim.x) bsum[x] = 0.f;
+    for (int x = threadIdx.x; x < (DET ? NWB : 1) * 3 * HD; x += blockDim.x) bsum[x] = 0.f;
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
     const long ld = 3L * D;
@@ -629,7 +645,10 @@ __global__ __launch_bounds__(NWB * 64, HD == 64 ? 3 : 4) void attn_bwd_frag_kern
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float v = row16_sum(csq[dt][r]);
-                if (i == 0) atomicAdd(bsum + dt * 16 + 4 * g + r, v);
+                if (i == 0) {
+                    if constexpr (DET) bsum[wave * 3 * HD + dt * 16 + 4 * g + r] = v;
+                    else atomicAdd(bsum + dt * 16 + 4 * g + r, v);
+                }
             }
     }
     __syncthreads();
@@ -719,14 +738,24 @@ __global__ __launch_bounds__(NWB * 64, HD == 64 ? 3 : 4) void attn_bwd_frag_kern
             for (int r = 0; r < 4; ++r) {
                 const float v = row16_sum(csk[dt][r]), u = row16_sum(csv[dt][r]);
                 if (i == 0) {
-                    atomicAdd(bsum + HD + dt * 16 + 4 * g + r, v);
-                    atomicAdd(bsum + 2 * HD + dt * 16 + 4 * g + r, u);
+                    if constexpr (DET) {
+                        bsum[wave * 3 * HD + HD + dt * 16 + 4 * g + r] = v;
+                        bsum[wave * 3 * HD + 2 * HD + dt * 16 + 4 * g + r] = u;
+                    } else {
+                        atomicAdd(bsum + HD + dt * 16 + 4 * g + r, v);
+                        atomicAdd(bsum + 2 * HD + dt * 16 + 4 * g + r, u);
+                    }
                 }
             }
         __syncthreads();
         for (int x = threadIdx.x; x < 3 * HD; x += blockDim.x) {
             const int part = x / HD, d = x - part * HD;
-            if (d < HG) a.dbias_ws[(long)b * 3 * D + part * D + h * HG + d] = bsum[x];
+            float tot = bsum[x];
+            if constexpr (DET) {
+#pragma unroll
+                for (int w = 1; w < NWB; ++w) tot += bsum[w * 3 * HD + x];
+            }
+            if (d < HG) a.dbias_ws[(long)b * 3 * D + part * D + h * HG + d] = tot;
         }
     }
 }
@@ -794,41 +823,86 @@ extern "C" int wj_attn_bwd(const wj_attn_bwd_args* a, void* stream) {
                       set_lds(attn_bwd_kernel<64, NWB64, 26>, 2 * 416 * 160 + 3 * 416 * 4 + 3 * 64 * 4) |
                       set_lds(attn_bwd_kernel<32, NWB32, 26>, 2 * 416 * 96 + 3 * 416 * 4 + 3 * 32 * 4);
     (void)once;
-    if (a->hd == 16) {
-        if (a->T <= 128) {
-            if (a->key_mask) hipLaunchKernelGGL((attn_bwd_frag_kernel<32, NWB32, 8, true, 16>), grid, dim3(NWB32 * 64), lds, st, *a);
-            else hipLaunchKernelGGL((attn_bwd_frag_kernel<32, NWB32, 8, false, 16>), grid, dim3(NWB32 * 64), lds, st, *a);
-        } else if (a->T <= 192) {
-            if (a->key_mask) hipLaunchKernelGGL((attn_bwd_frag_kernel<32, NWB32, 12, true, 16>), grid, dim3(NWB32 * 64), lds, st, *a);
-            else hipLaunchKernelGGL((attn_bwd_frag_kernel<32, NWB32, 12, false, 16>), grid, dim3(NWB32 * 64), lds, st, *a);
+    if (a->deterministic) {
+        // the same dispatch table over the DET twins (per-wave bsum rows: NW - 1 more rows of LDS)
+        static int once_det = set_lds(attn_bwd_kernel<64, NWB64, 14, 64, true>, 2 * 224 * 160 + 3 * 224 * 4 + NWB64 * 3 * 64 * 4) |
+                              set_lds(attn_bwd_kernel<32, NWB32, 14, 32, true>, 2 * 224 * 96 + 3 * 224 * 4 + NWB32 * 3 * 32 * 4) |
+                              set_lds(attn_bwd_kernel<64, NWB64, 26, 64, true>, 2 * 416 * 160 + 3 * 416 * 4 + NWB64 * 3 * 64 * 4) |
+                              set_lds(attn_bwd_kernel<32, NWB32, 26, 32, true>, 2 * 416 * 96 + 3 * 416 * 4 + NWB32 * 3 * 32 * 4);
+        (void)once_det;
+#define WJ_BWD_DET(NW, K) hipLaunchKernelGGL(K, grid, dim3(NW * 64), lds + (NW - 1) * 3 * hdk * 4, st, *a)
+        if (a->hd == 16) {
+            if (a->T <= 128) {
+                if (a->key_mask) WJ_BWD_DET(NWB32, (attn_bwd_frag_kernel<32, NWB32, 8, true, 16, true>));
+                else WJ_BWD_DET(NWB32, (attn_bwd_frag_kernel<32, NWB32, 8, false, 16, true>));
+            } else if (a->T <= 192) {
+                if (a->key_mask) WJ_BWD_DET(NWB32, (attn_bwd_frag_kernel<32, NWB32, 12, true, 16, true>));
+                else WJ_BWD_DET(NWB32, (attn_bwd_frag_kernel<32, NWB32, 12, false, 16, true>));
+            } else {
+                WJ_BWD_DET(NWB32, (attn_bwd_kernel<32, NWB32, 14, 16, true>));
+            }
+        } else if (a->T > MAX_TILES * 16) {     // 225 .. 416 tokens
+            if (a->hd == 64) WJ_BWD_DET(NWB64, (attn_bwd_kernel<64, NWB64, 26, 64, true>));
+            else WJ_BWD_DET(NWB32, (attn_bwd_kernel<32, NWB32, 26, 32, true>));
+        } else if (a->T <= 128) {          // ragged student / predictor: at most 8 tiles (6 or 8 waves per workgroup measured 1.5-2x slower)
+            static const int frag = wj_lab_env_int("WJ_ATTN_BWD_FRAG", 3);   // bit 0: hd 32, bit 1: hd 64 (A/B switch)
+            const bool masked = a->key_mask != nullptr;
+            if (a->hd == 64) {
+                if (!(frag & 2)) WJ_BWD_DET(NWB64, (attn_bwd_kernel<64, NWB64, 8, 64, true>));
+                else if (masked) WJ_BWD_DET(NWB64, (attn_bwd_frag_kernel<64, NWB64, 8, true, 64, true>));
+                else WJ_BWD_DET(NWB64, (attn_bwd_frag_kernel<64, NWB64, 8, false, 64, true>));
+            } else {
+                if (!(frag & 1)) WJ_BWD_DET(NWB32, (attn_bwd_kernel<32, NWB32, 8, 32, true>));
+                else if (masked) WJ_BWD_DET(NWB32, (attn_bwd_frag_kernel<32, NWB32, 8, true, 32, true>));
+                else WJ_BWD_DET(NWB32, (attn_bwd_frag_kernel<32, NWB32, 8, false, 32, true>));
+            }
+        } else if (a->hd == 64) {
+            WJ_BWD_DET(NWB64, (attn_bwd_kernel<64, NWB64, 14, 64, true>));
+        } else if (a->T <= 192) {          // 129 .. 192 tokens, head dim 32: the single-round-trip kernel with three tiles per wave
+            if (a->key_mask) WJ_BWD_DET(NWB32, (attn_bwd_frag_kernel<32, NWB32, 12, true, 32, true>));
+            else WJ_BWD_DET(NWB32, (attn_bwd_frag_kernel<32, NWB32, 12, false, 32, true>));
         } else {
-            hipLaunchKernelGGL((attn_bwd_kernel<32, NWB32, 14, 16>), grid, dim3(NWB32 * 64), lds, st, *a);
+            WJ_BWD_DET(NWB32, (attn_bwd_kernel<32, NWB32, 14, 32, true>));
         }
-    } else if (a->T > MAX_TILES * 16) {     // 225 .. 416 tokens
-        if (a->hd == 64) hipLaunchKernelGGL((attn_bwd_kernel<64, NWB64, 26>), grid, dim3(NWB64 * 64), lds, st, *a);
-        else hipLaunchKernelGGL((attn_bwd_kernel<32, NWB32, 26>), grid, dim3(NWB32 * 64), lds, st, *a);
-    } else if (a->T <= 128) {          // ragged student / predictor: at most 8 tiles (6 or 8 waves per workgroup measured 1.5-2x slower)
-        static const int frag = wj_lab_env_int("WJ_ATTN_BWD_FRAG", 3);   // bit 0: hd 32, bit 1: hd 64 (A/B switch)
-        const bool masked = a->key_mask != nullptr;
-        if (a->hd == 64) {
-            if (!(frag & 2)) hipLaunchKernelGGL((attn_bwd_kernel<64, NWB64, 8>), grid, dim3(NWB64 * 64), lds, st, *a);
-            else if (masked) hipLaunchKernelGGL((attn_bwd_frag_kernel<64, NWB64, 8, true>), grid, dim3(NWB64 * 64), lds, st, *a);
-            else hipLaunchKernelGGL((attn_bwd_frag_kernel<64, NWB64, 8, false>), grid, dim3(NWB64 * 64), lds, st, *a);
-        } else {
-            if (!(frag & 1)) hipLaunchKernelGGL((attn_bwd_kernel<32, NWB32, 8>), grid, dim3(NWB32 * 64), lds, st, *a);
-            else if (masked) hipLaunchKernelGGL((attn_bwd_frag_kernel<32, NWB32, 8, true>), grid, dim3(NWB32 * 64), lds, st, *a);
-            else hipLaunchKernelGGL((attn_bwd_frag_kernel<32, NWB32, 8, false>), grid, dim3(NWB32 * 64), lds, st, *a);
-        }
-    } else if (a->hd == 64) {
-        hipLaunchKernelGGL((attn_bwd_kernel<64, NWB64, 14>), grid, dim3(NWB64 * 64), lds, st, *a);
-    } else if (a->T <= 192) {          // 129 .. 192 tokens, head dim 32: the single-round-trip kernel with three tiles per wave
-        if (a->key_mask) hipLaunchKernelGGL((attn_bwd_frag_kernel<32, NWB32, 12, true>), grid, dim3(NWB32 * 64), lds, st, *a);
-        else hipLaunchKernelGGL((attn_bwd_frag_kernel<32, NWB32, 12, false>), grid, dim3(NWB32 * 64), lds, st, *a);
+#undef WJ_BWD_DET
     } else {
-        hipLaunchKernelGGL((attn_bwd_kernel<32, NWB32, 14>), grid, dim3(NWB32 * 64), lds, st, *a);
+        if (a->hd == 16) {
+            if (a->T <= 128) {
+                if (a->key_mask) hipLaunchKernelGGL((attn_bwd_frag_kernel<32, NWB32, 8, true, 16>), grid, dim3(NWB32 * 64), lds, st, *a);
+                else hipLaunchKernelGGL((attn_bwd_frag_kernel<32, NWB32, 8, false, 16>), grid, dim3(NWB32 * 64), lds, st, *a);
+            } else if (a->T <= 192) {
+                if (a->key_mask) hipLaunchKernelGGL((attn_bwd_frag_kernel<32, NWB32, 12, true, 16>), grid, dim3(NWB32 * 64), lds, st, *a);
+                else hipLaunchKernelGGL((attn_bwd_frag_kernel<32, NWB32, 12, false, 16>), grid, dim3(NWB32 * 64), lds, st, *a);
+            } else {
+                hipLaunchKernelGGL((attn_bwd_kernel<32, NWB32, 14, 16>), grid, dim3(NWB32 * 64), lds, st, *a);
+            }
+        } else if (a->T > MAX_TILES * 16) {     // 225 .. 416 tokens
+            if (a->hd == 64) hipLaunchKernelGGL((attn_bwd_kernel<64, NWB64, 26>), grid, dim3(NWB64 * 64), lds, st, *a);
+            else hipLaunchKernelGGL((attn_bwd_kernel<32, NWB32, 26>), grid, dim3(NWB32 * 64), lds, st, *a);
+        } else if (a->T <= 128) {          // ragged student / predictor: at most 8 tiles (6 or 8 waves per workgroup measured 1.5-2x slower)
+            static const int frag = wj_lab_env_int("WJ_ATTN_BWD_FRAG", 3);   // bit 0: hd 32, bit 1: hd 64 (A/B switch)
+            const bool masked = a->key_mask != nullptr;
+            if (a->hd == 64) {
+                if (!(frag & 2)) hipLaunchKernelGGL((attn_bwd_kernel<64, NWB64, 8>), grid, dim3(NWB64 * 64), lds, st, *a);
+                else if (masked) hipLaunchKernelGGL((attn_bwd_frag_kernel<64, NWB64, 8, true>), grid, dim3(NWB64 * 64), lds, st, *a);
+                else hipLaunchKernelGGL((attn_bwd_frag_kernel<64, NWB64, 8, false>), grid, dim3(NWB64 * 64), lds, st, *a);
+            } else {
+                if (!(frag & 1)) hipLaunchKernelGGL((attn_bwd_kernel<32, NWB32, 8>), grid, dim3(NWB32 * 64), lds, st, *a);
+                else if (masked) hipLaunchKernelGGL((attn_bwd_frag_kernel<32, NWB32, 8, true>), grid, dim3(NWB32 * 64), lds, st, *a);
+                else hipLaunchKernelGGL((attn_bwd_frag_kernel<32, NWB32, 8, false>), grid, dim3(NWB32 * 64), lds, st, *a);
+            }
+        } else if (a->hd == 64) {
+            hipLaunchKernelGGL((attn_bwd_kernel<64, NWB64, 14>), grid, dim3(NWB64 * 64), lds, st, *a);
+        } else if (a->T <= 192) {          // 129 .. 192 tokens, head dim 32: the single-round-trip kernel with three tiles per wave
+            if (a->key_mask) hipLaunchKernelGGL((attn_bwd_frag_kernel<32, NWB32, 12, true>), grid, dim3(NWB32 * 64), lds, st, *a);
+            else hipLaunchKernelGGL((attn_bwd_frag_kernel<32, NWB32, 12, false>), grid, dim3(NWB32 * 64), lds, st, *a);
+        } else {
+            hipLaunchKernelGGL((attn_bwd_kernel<32, NWB32, 14>), grid, dim3(NWB32 * 64), lds, st, *a);
+        }
     }
     if (a->dbias && !a->defer_fold) {
-        wj_colsum_args c;
+        wj_colsum_args c = {};
+        c.deterministic = a->deterministic;
         c.x = a->dbias_ws; c.out = a->dbias; c.ldx = 3L * a->H * a->hd; c.M = a->B; c.N = 3 * a->H * a->hd;
         const int rc = wj_colsum_f32(&c, stream);
         if (rc != WJ_OK) return rc;

@@ -240,6 +240,10 @@ __device__ __forceinline__ void load_frags2(bf16x8* f, const char* tile, int rba
     }
 }
 
+// Internal epilogue (not part of the ABI): the deterministic form of WJ_EPI_ATOMIC_F32 (wj_gemm_args.deterministic).  K slice `ksl` STORES
+// its fp32 tile into slab ksl of a scratch laid out [split][M][ldc] (EpiArgs.C = slab 0); slab_reduce_kernel adds the slabs in slice order.
+constexpr int EPI_SLAB_F32 = 64;
+
 struct EpiArgs {
     void* C;
     void* C2;
@@ -955,8 +959,8 @@ __device__ __forceinline__ void gemm3_body(const bf16_t* __restrict__ A, const b
         }
     }
     __syncthreads();
-    constexpr bool F32_TILE = (EPI == WJ_EPI_ADD_F32 || EPI == WJ_EPI_ATOMIC_F32);
-    static_assert(BMT == 256 || EPI == WJ_EPI_ATOMIC_F32, "384-row tiles: the split-K weight-gradient epilogue (three 128-row chunks)");
+    constexpr bool F32_TILE = (EPI == WJ_EPI_ADD_F32 || EPI == WJ_EPI_ATOMIC_F32 || EPI == EPI_SLAB_F32);
+    static_assert(BMT == 256 || EPI == WJ_EPI_ATOMIC_F32 || EPI == EPI_SLAB_F32, "384-row tiles: the split-K weight-gradient epilogue (three 128-row chunks)");
     constexpr int RC = F32_TILE ? C_::RC_F32 : C_::RC_BF16;
     constexpr int CP = F32_TILE ? C_::CP_F32 : C_::CP_BF16;
     constexpr int NCHUNK = BM / RC;
@@ -1003,6 +1007,21 @@ __device__ __forceinline__ void gemm3_body(const bf16_t* __restrict__ A, const b
                         const float v = *reinterpret_cast<const float*>(smem + r * CP + col * 4);
                         atomicAdd((float*)e.C + (long)m * e.ldc + n, v * e.alpha);
                     }
+                }
+            }
+        } else if constexpr (EPI == EPI_SLAB_F32) {
+            // plain 16-byte stores, a wave-instruction = whole 1-KiB (BN 256) / two 512-B (BN 128) row segments of this slice's slab.  Every
+            // element of the slab inside [M][N] is written by exactly one workgroup (a slice without K tiles stores zeros).
+            constexpr int TPR = BN / 4;
+            constexpr int RPP = NT / TPR;
+            const int c4 = (t % TPR) * 4, rr = t / TPR;
+            const int n = n0 + c4;
+            float* slab = (float*)e.C + (long)ksl * M * e.ldc;
+            if (n < N) {
+#pragma unroll 8
+                for (int r = rr; r < RC; r += RPP) {
+                    const int m = mh + r;
+                    if (m < M) *reinterpret_cast<f32x4*>(slab + (long)m * e.ldc + n) = *reinterpret_cast<const f32x4*>(smem + r * CP + c4 * 4);
                 }
             }
         } else if constexpr (EPI == WJ_EPI_ADD_F32) {
@@ -1216,7 +1235,7 @@ struct GroupTable {
     int n;
 };
 
-template <int BN, int BMT = 256, int SCHED = 0>
+template <int BN, int BMT = 256, int SCHED = 0, int EPI = WJ_EPI_ATOMIC_F32>
 __global__ __launch_bounds__(NT, (BN == 256 || BMT == 384) ? 1 : 2) void gemm3_grouped_wgrad_kernel(GroupTable g) {
     // XCD-grouped order over the WHOLE group (blocks b, b + 8, ... share an XCD and get a contiguous run of the group's work list:
     // neighbours inside a problem, i.e. tiles that stream the same K slice).  No padding between problems: a group sized for the
@@ -1232,7 +1251,60 @@ __global__ __launch_bounds__(NT, (BN == 256 || BMT == 384) ? 1 : 2) void gemm3_g
     e.C = P.C; e.C2 = nullptr; e.bias = nullptr; e.aux = nullptr; e.colsum = nullptr; e.ldc = P.ldc; e.seg_rows = 1; e.seg_valid = 1;
     e.alpha = 1.f; e.rowmap = nullptr; e.sa = nullptr; e.sb = nullptr; e.lds_a = 0; e.lds_b = 0; e.q_out = nullptr; e.q_scales = nullptr; e.ld_q = 0;
     e.pair_ws = nullptr; e.pair_flags = nullptr;
-    gemm3_body<true, true, WJ_EPI_ATOMIC_F32, BN, SCHED, 0, BMT>(P.A, P.B, P.lda, P.ldb, P.M, P.N, P.K, P.tiles_n, P.split, P.kps, e, bid, P.nwg, true);
+    gemm3_body<true, true, EPI, BN, SCHED, 0, BMT>(P.A, P.B, P.lda, P.ldb, P.M, P.N, P.K, P.tiles_n, P.split, P.kps, e, bid, P.nwg, true);
+}
+
+// ---- deterministic split-K: the reduction of the slabs (second launch of the store-and-sum form) ------------------------------------
+// Item x: C[m][n] = C[m][n] + alpha * (((P_0 + P_1) + P_2) + ... + P_{split-1})[m][n] over its [M][N] region (row stride ldc), the slabs
+// `stride` = M * ldc floats apart.  One thread per 16-byte chunk, grid-stride; every chunk has one adder and the order is the slice order.
+struct SlabItem {
+    const float* ws;
+    float* C;
+    long ldc, stride, begin;     // begin: first chunk of this item in the launch's chunk list
+    int n4, split;               // n4 = N / 4 chunks per row
+    float alpha;
+};
+struct SlabTable {
+    SlabItem p[GROUP_MAX];
+    int n;
+    long total;
+};
+__global__ __launch_bounds__(256) void slab_reduce_kernel(SlabTable g) {
+    for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < g.total; c += (long)gridDim.x * 256) {
+        int q = 0;
+#pragma unroll 1
+        for (int x = 1; x < g.n; ++x)
+            if (c >= g.p[x].begin) q = x;
+        const SlabItem& P = g.p[q];
+        const long local = c - P.begin;
+        const long m = local / P.n4;
+        const long off = m * P.ldc + (local - m * P.n4) * 4;
+        const float* src = P.ws + off;
+        f32x4 t = *reinterpret_cast<const f32x4*>(src);
+#pragma unroll 4
+        for (int s = 1; s < P.split; ++s) t += *reinterpret_cast<const f32x4*>(src + s * P.stride);
+        f32x4* dst = reinterpret_cast<f32x4*>(P.C + off);
+        *dst = *dst + t * P.alpha;
+    }
+}
+int launch_slab_reduce(SlabTable& g, hipStream_t s) {
+    long blocks = (g.total + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, g);
+    WJ_CHECK_LAUNCH();
+    return WJ_OK;
+}
+
+// K slices of a split-K launch: slices of a multiple of 64 k, none empty.  ONE place for the launch and the workspace query.
+void split_plan(int K, int want, int& split, int& kps) {
+    split = want < 1 ? 1 : want;
+    kps = ((K + split - 1) / split + 63) / 64 * 64;
+    split = (K + kps - 1) / kps;
+}
+long slab_need(const wj_gemm_args* a) {     // bytes of slabs the deterministic form of this call stores (0: one slice, no slabs)
+    int split, kps;
+    split_plan(a->K, a->split_k, split, kps);
+    return split > 1 ? (long)split * a->M * a->ldc * 4 : 0;
 }
 
 // K-split pairs (gemm3_body): which problems, and the scratch they need: [tiles][2] flags (padded to 4 KiB), then per tile and role
@@ -1253,9 +1325,8 @@ bool pair_shape(const wj_gemm_args* a) {
 template <bool AT, bool BT, int EPI, int BN, int SCHED, int GATHER = 0>
 int launch(const wj_gemm_args* a, hipStream_t s) {
     const int tiles_m = (a->M + BM - 1) / BM, tiles_n = (a->N + BN - 1) / BN;
-    int split = a->split_k < 1 ? 1 : a->split_k;
-    int kps = ((a->K + split - 1) / split + 63) / 64 * 64;
-    split = (a->K + kps - 1) / kps;
+    int split, kps;
+    split_plan(a->K, a->split_k, split, kps);
     bool pair = false;
     if constexpr (SCHED == 2 && EPI == WJ_EPI_BF16 && GATHER == 0 && BN == 256) {
         pair = pair_shape(a) && a->workspace && a->workspace_bytes >= pair_ws_need(tiles_m * tiles_n) && !((uintptr_t)a->workspace & 255);
@@ -1282,6 +1353,33 @@ int launch(const wj_gemm_args* a, hipStream_t s) {
                        (long)a->ldb, a->M, a->N, a->K, tiles_n, split, kps, e);
     WJ_CHECK_LAUNCH();
     return WJ_OK;
+}
+
+// Deterministic form of the split-K weight gradient (col-form A and B; GATHER 2: the sparse conv wgrad over its row list): the K slices
+// store their tiles into the caller's slabs, a second launch adds them in slice order into C.  The tile follows N alone (256 wide where N
+// fills it, else 128), the plain schedule: nothing here depends on `schedule`, the stream or the machine's state.
+template <int BN, int GATHER>
+int launch_slab(const wj_gemm_args* a, hipStream_t s) {
+    const int tiles_m = (a->M + BM - 1) / BM, tiles_n = (a->N + BN - 1) / BN;
+    int split, kps;
+    split_plan(a->K, a->split_k, split, kps);
+    EpiArgs e;
+    e.C = a->workspace; e.C2 = nullptr; e.bias = nullptr; e.aux = nullptr; e.ldc = a->ldc; e.colsum = nullptr; e.seg_rows = 1; e.seg_valid = 1;
+    e.alpha = 1.f; e.rowmap = a->rowmap;
+    e.sa = nullptr; e.sb = nullptr; e.lds_a = 0; e.lds_b = 0; e.q_out = nullptr; e.q_scales = nullptr; e.ld_q = 0;
+    e.pair_ws = nullptr; e.pair_flags = nullptr;
+    auto kern = gemm3_kernel<true, true, EPI_SLAB_F32, BN, 0, GATHER>;
+    constexpr int lds = Cfg<BN>::LDS_BYTES;
+    static int attr = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (attr != hipSuccess) return WJ_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n * split), dim3(NT), lds, s, (const bf16_t*)a->A, (const bf16_t*)a->B, (long)a->lda,
+                       (long)a->ldb, a->M, a->N, a->K, tiles_n, split, kps, e);
+    WJ_CHECK_LAUNCH();
+    SlabTable g;
+    g.n = 1;
+    g.p[0] = SlabItem{(const float*)a->workspace, (float*)a->C, (long)a->ldc, (long)a->M * a->ldc, 0, a->N / 4, split, a->alpha};
+    g.total = (long)a->M * (a->N / 4);
+    return launch_slab_reduce(g, s);
 }
 
 // Variant selection, from tools/gemm_bench.py / tools/gemm_overhead.py on MI355X:
@@ -1423,10 +1521,11 @@ extern "C" int wj_gemm_mxfp8(const wj_gemm_fp8_args* a, void* stream) {
     }
 }
 
-template <int BN, int BMT = 256, int SCHED = 0>
-int launch_grouped(const wj_wgrad_group_args* a, hipStream_t s) {
+// The work list of a grouped launch (split factors, K slices, workgroup ranges): from the shapes of the group and the tile variant only.
+// Returns the number of workgroups.  ONE place for the launch and the workspace query.
+template <int BN, int BMT>
+int plan_group(const wj_wgrad_group_args* a, GroupTable& g) {
     constexpr int BM = BMT;
-    GroupTable g;
     g.n = a->n;
     long tiles_total = 0;
     for (int x = 0; x < a->n; ++x)
@@ -1451,6 +1550,44 @@ int launch_grouped(const wj_wgrad_group_args* a, hipStream_t s) {
         P.wg_begin = begin;
         begin += P.nwg;
     }
+    return begin;
+}
+// slab bytes of the deterministic form of a planned group: 0 when no problem is split (the atomic epilogue then has one adder per element)
+long group_slab_need(const GroupTable& g) {
+    bool any = false;
+    long need = 0;
+    for (int x = 0; x < g.n; ++x) {
+        any = any || g.p[x].split > 1;
+        need += (long)g.p[x].split * g.p[x].M * g.p[x].ldc * 4;
+    }
+    return any ? need : 0;
+}
+
+template <int BN, int BMT = 256, int SCHED = 0>
+int launch_grouped(const wj_wgrad_group_args* a, hipStream_t s) {
+    GroupTable g;
+    const int begin = plan_group<BN, BMT>(a, g);
+    if (a->deterministic && group_slab_need(g) > 0) {
+        // store-and-sum form: problem x's slices go to slabs [split_x][M_x][ldc_x], back to back in the workspace; one reduction launch
+        SlabTable r;
+        r.n = g.n;
+        r.total = 0;
+        float* ws = (float*)a->workspace;
+        for (int x = 0; x < g.n; ++x) {
+            GroupProblem& P = g.p[x];
+            r.p[x] = SlabItem{ws, P.C, P.ldc, (long)P.M * P.ldc, r.total, P.N / 4, P.split, 1.f};
+            r.total += (long)P.M * (P.N / 4);
+            P.C = ws;
+            ws += (long)P.split * P.M * P.ldc;
+        }
+        auto kern = gemm3_grouped_wgrad_kernel<BN, BMT, SCHED, EPI_SLAB_F32>;
+        constexpr int lds = Cfg<BN, BMT>::LDS_BYTES;
+        static int attr = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (attr != hipSuccess) return WJ_ERR_LAUNCH;
+        hipLaunchKernelGGL(kern, dim3(begin), dim3(NT), lds, s, g);
+        WJ_CHECK_LAUNCH();
+        return launch_slab_reduce(r, s);
+    }
     auto kern = gemm3_grouped_wgrad_kernel<BN, BMT, SCHED>;
     constexpr int lds = Cfg<BN, BMT>::LDS_BYTES;
     static int attr = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -1458,6 +1595,23 @@ int launch_grouped(const wj_wgrad_group_args* a, hipStream_t s) {
     hipLaunchKernelGGL(kern, dim3(begin), dim3(NT), lds, s, g);
     WJ_CHECK_LAUNCH();
     return WJ_OK;
+}
+
+// slab bytes of the deterministic form of this group (0: not deterministic, malformed, or no problem is split) --
+// wj_workspace_bytes("wj_wgrad_grouped", args).  Mirrors the tile choice of wj_wgrad_grouped below.
+int64_t wj_wgrad_group_ws_bytes(const wj_wgrad_group_args* a) {
+    if (!a || !a->deterministic || a->n < 1 || a->n > GROUP_MAX) return 0;
+    bool wide = true, m384 = true;
+    for (int x = 0; x < a->n; ++x) {
+        if (a->M[x] <= 0 || a->N[x] <= 0 || a->K[x] <= 0) return 0;
+        wide = wide && a->N[x] % 256 == 0;
+        m384 = m384 && a->M[x] % 384 == 0 && a->N[x] % 128 == 0;
+    }
+    GroupTable g;
+    if (wide) plan_group<256, 256>(a, g);
+    else if (m384 && wj_lab_env_int("WJ_WGRAD_384", 1) != 0) plan_group<128, 384>(a, g);
+    else plan_group<128, 256>(a, g);
+    return group_slab_need(g);
 }
 
 extern "C" int wj_wgrad_grouped(const wj_wgrad_group_args* a, void* stream) {
@@ -1471,11 +1625,16 @@ extern "C" int wj_wgrad_grouped(const wj_wgrad_group_args* a, void* stream) {
         wide = wide && a->N[x] % 256 == 0;
         m384 = m384 && a->M[x] % 384 == 0 && a->N[x] % 128 == 0;
     }
-    if (wide) return launch_grouped<256>(a, (hipStream_t)stream);
     // every problem a multiple of 384 rows x 128 columns (the predictor: d = 384): the 384 x 128 tile has no half-empty row tiles
     // (WJ_WGRAD_384=0: the 256 x 128 tile, round 4; =2: the ping-pong schedule on the 384 x 128 tile)
     static int m384_mode = -1;
     if (m384_mode < 0) m384_mode = wj_lab_env_int("WJ_WGRAD_384", 1);
+    if (a->deterministic) {
+        // the need follows from the plan the launch below makes (same tile variant, same split factors)
+        const long need = wj_wgrad_group_ws_bytes(a);
+        if (need > 0 && (!a->workspace || a->workspace_bytes < need || ((uintptr_t)a->workspace & 15))) return WJ_ERR_ARG;
+    }
+    if (wide) return launch_grouped<256>(a, (hipStream_t)stream);
     if (m384 && m384_mode == 1) return launch_grouped<128, 384, 0>(a, (hipStream_t)stream);
     if (m384 && m384_mode == 2) return launch_grouped<128, 384, 1>(a, (hipStream_t)stream);
     return launch_grouped<128>(a, (hipStream_t)stream);
@@ -1483,6 +1642,7 @@ extern "C" int wj_wgrad_grouped(const wj_wgrad_group_args* a, void* stream) {
 
 // scratch bytes wj_gemm_bf16 can use for this problem (0: none) -- wj_workspace_bytes("wj_gemm_bf16", args)
 int64_t wj_gemm_ws_bytes(const wj_gemm_args* a) {
+    if (a && a->deterministic && a->epilogue == WJ_EPI_ATOMIC_F32 && a->M > 0 && a->N > 0 && a->K > 0) return slab_need(a);
     if (!a || a->M <= 0 || a->N <= 0 || a->K <= 0 || !pair_shape(a)) return 0;
     return pair_ws_need(((a->M + BM - 1) / BM) * (a->N / 256));
 }
@@ -1502,7 +1662,17 @@ extern "C" int wj_gemm_bf16(const wj_gemm_args* a, void* stream) {
     if (a->split_k > 1 && a->epilogue != WJ_EPI_ATOMIC_F32) return WJ_ERR_ARG;
     if (a->colsum && a->epilogue != WJ_EPI_BF16 && a->epilogue != WJ_EPI_MUL_GELU_GRAD) return WJ_ERR_ARG;
     if (a->schedule < 0 || a->schedule > 7 || a->persist_cus < 0 || a->persist_cus > 32) return WJ_ERR_ARG;
+    if (a->deterministic && a->colsum) return WJ_ERR_ARG;            // the fused column sums are float atomics
     hipStream_t s = (hipStream_t)stream;
+    if (a->deterministic && a->epilogue == WJ_EPI_ATOMIC_F32) {
+        const long need = slab_need(a);
+        if (need > 0) {
+            if (!a->a_trans || !a->b_trans) return WJ_ERR_UNSUPPORTED;
+            if (!a->workspace || a->workspace_bytes < need || ((uintptr_t)a->workspace & 15)) return WJ_ERR_ARG;
+            if (a->rowmap) return launch_slab<256, 2>(a, s);
+            return a->N % 256 == 0 ? launch_slab<256, 0>(a, s) : launch_slab<128, 0>(a, s);
+        }
+    }
     if (a->rowmap) {
         // gather forms (sparse conv backward), one instantiation each
         if (!a->a_trans && a->b_trans && a->epilogue == WJ_EPI_BF16 && !a->colsum && !a->bias)

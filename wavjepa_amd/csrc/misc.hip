@@ -609,6 +609,8 @@ extern "C" int wj_struct_size(const char* name) {
 }
 
 int64_t wj_gemm_ws_bytes(const wj_gemm_args* a);              // csrc/gemm.hip
+int64_t wj_wgrad_group_ws_bytes(const wj_wgrad_group_args* a);
+int64_t wj_colsum_bf16_ws_bytes(const wj_colsum_args* a);     // csrc/norm.hip
 int64_t wj_conv0_fwd_ws_bytes(const wj_conv0_fwd_args* a);   // csrc/conv0.hip
 int64_t wj_conv0_bwd_ws_bytes(const wj_conv0_bwd_args* a);
 int64_t wj_rir_conv_ws_bytes(const wj_rir_conv_args* a);      // csrc/scene.hip
@@ -618,6 +620,8 @@ int64_t wj_mse_groups_ws_bytes(const wj_mse_groups_args* a);  // csrc/denoise.hi
 extern "C" int64_t wj_workspace_bytes(const char* fn, const void* args) {
     if (!fn || !args) return -1;
     if (!strcmp(fn, "wj_gemm_bf16")) return wj_gemm_ws_bytes((const wj_gemm_args*)args);
+    if (!strcmp(fn, "wj_wgrad_grouped")) return wj_wgrad_group_ws_bytes((const wj_wgrad_group_args*)args);
+    if (!strcmp(fn, "wj_colsum_bf16")) return wj_colsum_bf16_ws_bytes((const wj_colsum_args*)args);
     if (!strcmp(fn, "wj_mask_scatter_fill_pos_bwd")) {           // `partials`: one row of D floats per workgroup
         const wj_scatter_fill_bwd_args* a = (const wj_scatter_fill_bwd_args*)args;
         return (int64_t)wj_scatter_fill_bwd_partial_rows(a->B, a->T) * a->D * 4;
@@ -637,10 +641,10 @@ extern "C" int64_t wj_workspace_bytes(const char* fn, const void* args) {
     if (!strcmp(fn, "wj_rir_convolve")) return wj_rir_conv_ws_bytes((const wj_rir_conv_args*)args);
     if (!strcmp(fn, "wj_snr_mix")) return wj_snr_mix_ws_bytes((const wj_snr_mix_args*)args);
     if (!strcmp(fn, "wj_mse_groups")) return wj_mse_groups_ws_bytes((const wj_mse_groups_args*)args);
-    static const char* const none[] = {"wj_layernorm_fwd", "wj_colsum_bf16", "wj_colsum_f32", "wj_attn_fwd", "wj_gelu_bwd_bf16",
+    static const char* const none[] = {"wj_layernorm_fwd", "wj_colsum_f32", "wj_attn_fwd", "wj_gelu_bwd_bf16",
         "wj_conv_weight_layout", "wj_add_pos", "wj_mask_gather_rows", "wj_mask_scatter_fill_pos",
         "wj_unmask_rows_f32", "wj_instnorm_accumulate", "wj_instnorm_mean", "wj_ema_update", "wj_adamw_step", "wj_cast_f32_to_bf16",
-        "wj_crop_normalize_bf16", "wj_zero_rows", "wj_spin", "wj_gemm_mxfp8", "wj_quantize_mxfp8", "wj_wgrad_grouped", "wj_resample_fir", "wj_transpose_bf16", "wj_colsum_f32_group", "wj_rccl_bucket_allreduce_launch", "wj_rccl_bucket_allreduce_wait", "wj_collective_footprint"};
+        "wj_crop_normalize_bf16", "wj_zero_rows", "wj_spin", "wj_gemm_mxfp8", "wj_quantize_mxfp8", "wj_resample_fir", "wj_transpose_bf16", "wj_colsum_f32_group", "wj_rccl_bucket_allreduce_launch", "wj_rccl_bucket_allreduce_wait", "wj_collective_footprint"};
     for (const char* n : none)
         if (!strcmp(fn, n)) return 0;
     return -1;

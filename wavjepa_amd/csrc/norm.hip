@@ -482,7 +482,92 @@ __global__ __launch_bounds__(256) void colsum_kernel(wj_colsum_args a, int rows_
     }
 }
 
+// ---- deterministic column sums (wj_colsum_args.deterministic / wj_colsum_group_args.deterministic) -------------------------------
+// One workgroup per 128 columns walks ALL rows of its item: thread (cc, rl) adds rows rl, rl + 8, ... in ascending order, the eight row
+// lanes are added in lane order, and the single adder of a column does out += s with a plain read-modify-write (stream-ordered behind
+// whatever wrote `out` before).  No float atomics: the result is a function of the inputs.  Meant for partial matrices of a few hundred
+// rows (the LayerNorm / attention / scatter-fill partials, the second stage of the bf16 column sums below).
+__device__ __forceinline__ void colsum_f32_ordered(const float* __restrict__ x, long ldx, int M, int N, int cb, float* o0, float* o1, float* o2,
+                                                   int n_each, float (*red)[132]) {
+    const int t = threadIdx.x, cc = t & 31, rl = t >> 5;
+    const int col = cb * 128 + cc * 4;
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (col < N)
+        for (int r = rl; r < M; r += 8) acc += *reinterpret_cast<const f32x4*>(x + (long)r * ldx + col);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) red[rl][cc * 4 + e] = acc[e];
+    __syncthreads();
+    if (t < 128) {
+        float s = 0.f;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) s += red[r][t];
+        const int c = cb * 128 + t;
+        if (c < N) {
+            const int which = c / n_each, cc2 = c - which * n_each;
+            float* o = which == 0 ? o0 : (which == 1 ? o1 : o2);
+            if (o) o[cc2] += s;
+        }
+    }
+}
+__global__ __launch_bounds__(256) void colsum_f32_det_kernel(const float* __restrict__ x, long ldx, int M, int N, float* o0, float* o1, float* o2,
+                                                             int n_each) {
+    __shared__ float red[8][132];
+    colsum_f32_ordered(x, ldx, M, N, blockIdx.x, o0, o1, o2, n_each, red);
+}
+__global__ __launch_bounds__(256) void colsum_f32_group_det_kernel(wj_colsum_group_args a) {
+    __shared__ float red[8][132];
+    const int item = blockIdx.x / GROUP_CB, cb = blockIdx.x - item * GROUP_CB;
+    if (cb * 128 >= a.N[item]) return;
+    colsum_f32_ordered(a.x[item], a.ldx[item], a.M[item], a.N[item], cb, a.o0[item], a.o1[item], a.o2[item], a.n_each[item], red);
+}
+// first stage of the deterministic bf16 column sums: colsum_kernel's walk, but row range y STORES its sums as row y of `part` [gridDim.y][N]
+__global__ __launch_bounds__(256) void colsum_partial_kernel(wj_colsum_args a, int rows_per_wg) {
+    __shared__ float red[32][65];
+    const int t = threadIdx.x, cc = t & 7, rl = t >> 3;
+    const int col = blockIdx.x * 64 + cc * 8;
+    const int r0 = blockIdx.y * rows_per_wg;
+    const int r1 = min(a.M, r0 + rows_per_wg);
+    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (col < a.N) {
+        for (int r = r0 + rl; r < r1; r += 32) {
+            const bf16x8 v = *reinterpret_cast<const bf16x8*>((const bf16_t*)a.x + (long)r * a.ldx + col);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] += bf2f(v[e]);
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) red[rl][cc * 8 + e] = acc[e];
+    __syncthreads();
+    if (t < 64) {
+        float s = 0.f;
+#pragma unroll 8
+        for (int r = 0; r < 32; ++r) s += red[r][t];
+        const int c = blockIdx.x * 64 + t;
+        if (c < a.N) a.workspace[(long)blockIdx.y * a.N + c] = s;
+    }
+}
+void launch_colsum_f32_det(const float* x, long ldx, int M, int N, float* o0, float* o1, float* o2, int n_each, hipStream_t s) {
+    hipLaunchKernelGGL(colsum_f32_det_kernel, dim3((N + 127) / 128), dim3(256), 0, s, x, ldx, M, N, o0, o1, o2, n_each);
+}
+// row ranges of wj_colsum_bf16 (both forms): from M and N only
+void colsum_bf16_plan(int M, int N, int& gx, int& gy, int& rows) {
+    gx = (N + 63) / 64;
+    gy = 2048 / gx;
+    if (gy < 1) gy = 1;
+    rows = (M + gy - 1) / gy;
+    rows = (rows + 31) / 32 * 32;
+    gy = (M + rows - 1) / rows;
+}
+
 }  // namespace
+
+// partial-row bytes of the deterministic wj_colsum_bf16 -- wj_workspace_bytes("wj_colsum_bf16", args)
+int64_t wj_colsum_bf16_ws_bytes(const wj_colsum_args* a) {
+    if (!a || !a->deterministic || a->M <= 0 || a->N <= 0) return 0;
+    int gx, gy, rows;
+    colsum_bf16_plan(a->M, a->N, gx, gy, rows);
+    return (int64_t)gy * a->N * 4;
+}
 
 extern "C" int wj_layernorm_fwd(const wj_ln_fwd_args* a, void* stream) {
     WJ_CLEAR_STALE_ERROR();
@@ -562,7 +647,8 @@ extern "C" int wj_colsum_f32_group(const wj_colsum_group_args* a, void* stream) 
         if (!a->x[x] || a->M[x] <= 0 || a->N[x] <= 0 || (a->N[x] & 3) || (a->ldx[x] & 3) || a->n_each[x] <= 0) return WJ_ERR_ARG;
         if (a->N[x] > GROUP_CB * 128 || a->N[x] > 3 * a->n_each[x]) return WJ_ERR_ARG;
     }
-    hipLaunchKernelGGL(colsum_f32_group_kernel, dim3(a->n * GROUP_CB * GROUP_RB), dim3(256), 0, (hipStream_t)stream, *a);
+    if (a->deterministic) hipLaunchKernelGGL(colsum_f32_group_det_kernel, dim3(a->n * GROUP_CB), dim3(256), 0, (hipStream_t)stream, *a);
+    else hipLaunchKernelGGL(colsum_f32_group_kernel, dim3(a->n * GROUP_CB * GROUP_RB), dim3(256), 0, (hipStream_t)stream, *a);
     WJ_CHECK_LAUNCH();
     return WJ_OK;
 }
@@ -597,7 +683,8 @@ extern "C" int wj_layernorm_bwd(const wj_ln_bwd_args* a, void* stream) {
 extern "C" int wj_colsum_f32(const wj_colsum_args* a, void* stream) {
     WJ_CLEAR_STALE_ERROR();
     if (!a || !a->x || !a->out || a->M <= 0 || a->N <= 0 || (a->N & 3) || (a->ldx & 3)) return WJ_ERR_ARG;
-    launch_colsum_f32((const float*)a->x, a->ldx, a->M, a->N, a->out, nullptr, nullptr, a->N, (hipStream_t)stream);
+    if (a->deterministic) launch_colsum_f32_det((const float*)a->x, a->ldx, a->M, a->N, a->out, nullptr, nullptr, a->N, (hipStream_t)stream);
+    else launch_colsum_f32((const float*)a->x, a->ldx, a->M, a->N, a->out, nullptr, nullptr, a->N, (hipStream_t)stream);
     WJ_CHECK_LAUNCH();
     return WJ_OK;
 }
@@ -605,12 +692,16 @@ extern "C" int wj_colsum_f32(const wj_colsum_args* a, void* stream) {
 extern "C" int wj_colsum_bf16(const wj_colsum_args* a, void* stream) {
     WJ_CLEAR_STALE_ERROR();
     if (!a || !a->x || !a->out || a->M <= 0 || a->N <= 0 || (a->N & 7) || (a->ldx & 7)) return WJ_ERR_ARG;
-    const int gx = (a->N + 63) / 64;
-    int gy = 2048 / gx;
-    if (gy < 1) gy = 1;
-    int rows = (a->M + gy - 1) / gy;
-    rows = (rows + 31) / 32 * 32;
-    gy = (a->M + rows - 1) / rows;
+    int gx, gy, rows;
+    colsum_bf16_plan(a->M, a->N, gx, gy, rows);
+    if (a->deterministic) {
+        // two launches on the same stream: partial rows (plain stores), then one adder per column over them in row-range order
+        if (!a->workspace || a->workspace_bytes < (int64_t)gy * a->N * 4 || ((uintptr_t)a->workspace & 15)) return WJ_ERR_ARG;
+        hipLaunchKernelGGL(colsum_partial_kernel, dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *a, rows);
+        launch_colsum_f32_det(a->workspace, a->N, gy, a->N, a->out, nullptr, nullptr, a->N, (hipStream_t)stream);
+        WJ_CHECK_LAUNCH();
+        return WJ_OK;
+    }
     hipLaunchKernelGGL(colsum_kernel, dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, *a, rows);
     WJ_CHECK_LAUNCH();
     return WJ_OK;

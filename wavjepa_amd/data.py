@@ -5,10 +5,28 @@ Stands in for reference data_modules/WebAudioDataModule.py:43-142 (webdataset sh
 10 s pad -> masker); the batch layout is the same: (audio [B,1,L_full] f32, ctx [B,S,T], tgt [B,S,G,T], vis [B,S,G,T])."""
 from __future__ import annotations
 
+import contextlib
 from typing import List, Tuple
 
 import torch
 
+
+
+@contextlib.contextmanager
+def pinned_mask_draws(seed: int):
+    """The maskers draw from np.random.default_rng(None) -- OS entropy, as upstream -- on every call.  Inside this context the k-th
+    default_rng() call returns default_rng(seed + k): a run that must be repeatable (trainer.deterministic) builds its mask sets here."""
+    import numpy as np
+    orig, k = np.random.default_rng, [0]
+
+    def pinned(_seed=None):
+        k[0] += 1
+        return orig(seed + k[0] - 1)
+    np.random.default_rng = pinned
+    try:
+        yield
+    finally:
+        np.random.default_rng = orig
 
 
 class SyntheticAudioSource:

@@ -68,13 +68,15 @@ class DenoiserEngine(JepaEngine):
         c, f = self.cfg, self.flat
         De, M, N2 = c.d_enc, self.M, self.N
         f.g32.zero_()
+        if self.deterministic:
+            self._det_ws()
         self.refresh_wt()
         bw = self.bw["enc"]
         ops.mse_groups(self.enc_out, self.dn_targets, self.dn_w, self.dn_loss, self.dn_ws, n=self.dn_n, G=2, dpreds=bw["dx1"],
                        gscale=gscale_ptr if gscale_ptr else None)
         last = self.enc_acts[-1]
-        ops.layernorm_bwd(bw["dx1"], last.x2, f.ptr32("encoder.norm.weight"), self.enc_fm, self.enc_fr, M=M, D=De, ds_f32=bw["dy"],
-                          dgamma=f.gptr("encoder.norm.weight"), dbeta=f.gptr("encoder.norm.bias"), workspace=self.red_ws)
+        self._ln_bwd_direct(bw["dx1"], last.x2, f.ptr32("encoder.norm.weight"), self.enc_fm, self.enc_fr, M=M, D=De, ds_f32=bw["dy"],
+                            dgamma=f.gptr("encoder.norm.weight"), dbeta=f.gptr("encoder.norm.bias"), workspace=self.red_ws)
         dy, dyb = bw["dy"], None
         for i in range(c.l_enc - 1, -1, -1):
             x_in, xb_in = (self.lf, self.lf_b) if i == 0 else (self.enc_acts[i - 1].x2, self.enc_acts[i - 1].x2b)

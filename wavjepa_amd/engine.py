@@ -340,6 +340,13 @@ class JepaEngine:
         # conv backward over the active rows only (needs a ragged step and k >= stride in every GEMM conv layer)
         self.sparse_conv = _os.environ.get("WJ_SPARSE_CONV", "1") != "0" and all(k >= st for _, k, st in cfg.conv_spec[1:])
         self._conv_grads_dirty = False
+        # deterministic mode (WJ_DETERMINISTIC=1, or engine.deterministic = True before a step): every float sum of the backward whose
+        # order follows arrival order by default -- the split-K weight gradients, the column-sum folds, the attention backward's LDS
+        # sums -- takes its store-and-sum form (include/wavjepa_hip.h: the `deterministic` fields).  Loss, gradients, parameters and Adam
+        # moments are then bit-identical from run to run on one build and GPU model.  The slabs of the split-K forms live in two
+        # scratch buffers, one per stream (_det_ws), allocated once.
+        self.deterministic = _os.environ.get("WJ_DETERMINISTIC", "0") == "1"
+        self._det_slab: Dict[str, torch.Tensor] = {}
         # GELU' of conv layers 1..n-2 in the epilogue of the sparse dgrad above them (WJ_FUSE_CONV_GELU_BWD=0: separate passes)
         self.fuse_conv_gelu_bwd = _os.environ.get("WJ_FUSE_CONV_GELU_BWD", "1") != "0"
         # last predictor layer: after its attention only the target rows go on (WJ_TRIM_TAIL=0: every visible row)
@@ -834,6 +841,15 @@ class JepaEngine:
     def _dgrad(self, dY, w: _Layer, key: str, out, *, M: int, N: int, K: int, **kw) -> None:
         """out[M, N] = dY[M, K] . W   (W = the layer's `key` weight, stored [K][N] as nn.Linear keeps it): against the W^T shadow as a
         row-form GEMM, or (WJ_WT_DGRAD=0, widths that are not multiples of 64) against W itself in col form."""
+        colsum = kw.get("colsum") if self.deterministic else None
+        if colsum is not None:
+            # the fused column sums meet in one float atomic per row tile: deterministic mode sums the bf16 output in a pass of its own
+            kw = {k: v for k, v in kw.items() if k != "colsum"}
+        self._dgrad_gemm(dY, w, key, out, M=M, N=N, K=K, **kw)
+        if colsum is not None:
+            self._colsum_bf16(out, colsum, M=M, N=N, ldx=N)
+
+    def _dgrad_gemm(self, dY, w: _Layer, key: str, out, *, M: int, N: int, K: int, **kw) -> None:
         if self.wt_dgrad and key in self._wt_live.get(id(w), ()):
             ops.gemm(dY, getattr(w, key + "T"), out, M=M, N=N, K=K, lda=K, ldb=K, ldc=N,
                      workspace=self.pair_ws if id(w) in self._enc_ids else None, **kw)
@@ -851,8 +867,66 @@ class JepaEngine:
         kernels that wrote them; called before a section of the gradient buffer is declared final).  (On the side stream, with two
         scratch buffers: 46.64 against 46.65 ms/step -- stays on the main stream.)"""
         if self._folds:
-            ops.colsum_f32_group(self._folds)
+            if self.deterministic:
+                ops.colsum_f32_group(self._folds, deterministic=True)
+            else:
+                ops.colsum_f32_group(self._folds)
             self._folds = []
+
+    # ---- deterministic mode: scratch and call forms
+    def _det_ws_bytes(self) -> Tuple[int, int]:
+        """(slab bytes, column-sum partial bytes) that cover every deterministic launch of a step, from the library's own queries: the
+        split factor of a weight gradient grows with its K (the token rows) up to a limit set by its shapes, so K = 2^30 asks for
+        that limit -- one size for every mask draw, no allocation inside a step."""
+        c, C, big = self.cfg, self.C, 1 << 30
+        need = 0
+        for d, group in ((c.d_enc, 2), (c.d_dec, 1)):
+            layer = [(0, 0, 0, d, 4 * d, big), (0, 0, 0, 4 * d, d, big), (0, 0, 0, d, d, big), (0, 0, 0, 3 * d, d, big)]
+            for n in range(1, group + 1):
+                need = max(need, ops.wgrad_grouped_workspace_bytes(layer * n))
+        shapes = [(c.d_enc, c.d_dec), (c.d_dec, c.d_enc), (c.d_enc, C)] + [(C, k * C) for _, k, _ in c.conv_spec[1:]]
+        for m, n in shapes:
+            need = max(need, ops.workspace_bytes("wj_gemm_bf16", M=m, N=n, K=big, ldc=n, a_trans=1, b_trans=1, epilogue=ops.EPI_ATOMIC_F32,
+                                                 split_k=ops.pick_split_k(m, n, big), deterministic=1))
+        cs = max(ops.workspace_bytes("wj_colsum_bf16", M=big, N=n, deterministic=1) for n in (c.d_enc, c.d_dec, 4 * c.d_enc, 4 * c.d_dec))
+        return need, cs
+
+    def _det_ws(self) -> torch.Tensor:
+        """The slab scratch of the stream the caller launches on: the main stream and the side stream each own one, so two weight
+        gradients in flight never share a slab (launches of one stream are ordered)."""
+        if not self._det_slab:
+            slab, cs = self._det_ws_bytes()
+            for tag in ("main", "side"):
+                self._det_slab[tag] = _empty(max(slab, 256), dtype=torch.uint8, device=self.dev)
+            self._det_slab["colsum"] = _empty(max(cs, 256) // 4, dtype=torch.float32, device=self.dev)     # main-stream launches only
+        on_side = self.use_side and torch.cuda.current_stream() == self.side
+        return self._det_slab["side" if on_side else "main"]
+
+    def _det_kw(self) -> dict:
+        """extra arguments of a split-K weight-gradient ops.gemm call (none by default: the call is then exactly the default one)"""
+        return dict(workspace=self._det_ws(), deterministic=True) if self.deterministic else {}
+
+    def _colsum_bf16(self, x, out, *, M: int, N: int, ldx: int) -> None:
+        if self.deterministic:
+            self._det_ws()
+            ops.colsum_bf16(x, out, M=M, N=N, ldx=ldx, workspace=self._det_slab["colsum"], deterministic=True)
+        else:
+            ops.colsum_bf16(x, out, M=M, N=N, ldx=ldx)
+
+    def _fold_now(self, ws, ldx: int, rows: int, N: int, o0, o1, o2, n_each: int) -> None:
+        """deterministic fold of one partial matrix, at once (the undeferred forms)"""
+        if N > 2304:
+            raise RuntimeError(f"deterministic mode: no ordered fold for {N} columns (wj_colsum_f32_group takes <= 2304)")
+        ops.colsum_f32_group([(ws, ldx, rows, N, o0, o1, o2, n_each)], deterministic=True)
+
+    def _ln_bwd_direct(self, dy, x, gamma, mean, rstd, *, M: int, D: int, dgamma=None, dbeta=None, dbias=None, workspace=None, **kw) -> None:
+        """wj_layernorm_bwd that folds its parameter gradients at once.  Deterministic mode: always through the partial rows (no
+        gradient outputs, so the kernel has no atomics) and an ordered fold."""
+        if self.deterministic and (dgamma or dbeta or dbias):
+            ops.layernorm_bwd(dy, x, gamma, mean, rstd, M=M, D=D, workspace=self.red_ws, **kw)
+            self._fold_now(self.red_ws, 3 * D, ops.ln_bwd_partial_rows(M, D), 3 * D, dgamma, dbeta, dbias, D)
+        else:
+            ops.layernorm_bwd(dy, x, gamma, mean, rstd, M=M, D=D, dgamma=dgamma, dbeta=dbeta, dbias=dbias, workspace=workspace, **kw)
 
     def _ln_bwd(self, dy, x, gamma, mean, rstd, *, M: int, D: int, dgamma=None, dbeta=None, dbias=None, **kw) -> None:
         """wj_layernorm_bwd; its dgamma / dbeta / dbias partials are folded later, together with the neighbours' (see _flush_folds)."""
@@ -861,10 +935,12 @@ class JepaEngine:
             ops.layernorm_bwd(dy, x, gamma, mean, rstd, M=M, D=D, workspace=ws, **kw)
             self._folds.append((ws, 3 * D, ops.ln_bwd_partial_rows(M, D), 3 * D, dgamma, dbeta, dbias, D))
         else:
-            ops.layernorm_bwd(dy, x, gamma, mean, rstd, M=M, D=D, dgamma=dgamma, dbeta=dbeta, dbias=dbias, workspace=self.red_ws, **kw)
+            self._ln_bwd_direct(dy, x, gamma, mean, rstd, M=M, D=D, dgamma=dgamma, dbeta=dbeta, dbias=dbias, workspace=self.red_ws, **kw)
 
     def _attn_bwd(self, qkv, out, dout, lse, dqkv, *, B: int, H: int, hd: int, dbias, **kw) -> None:
         D3 = 3 * H * hd
+        if self.deterministic:
+            kw = dict(kw, deterministic=True)
         if self.defer_folds and D3 <= 2304 and dbias:
             ws = self._fold_slot()
             ops.attn_bwd(qkv, out, dout, lse, dqkv, B=B, H=H, hd=hd, dbias=dbias, dbias_ws=ws, defer_fold=True, **kw)
@@ -877,7 +953,7 @@ class JepaEngine:
         the launch goes to the side stream -- WJ_MAPPER_WGRAD_SIDE=0: main stream)"""
         def go():
             ops.gemm(dY, X, gW, M=n_out, N=k_in, K=m_tok, lda=n_out, ldb=k_in, ldc=k_in, a_trans=1, b_trans=1,
-                     epilogue=ops.EPI_ATOMIC_F32, split_k=ops.pick_split_k(n_out, k_in, m_tok))
+                     epilogue=ops.EPI_ATOMIC_F32, split_k=ops.pick_split_k(n_out, k_in, m_tok), **self._det_kw())
         if self.use_side and self.mapper_wgrad_side:
             self._on_side(go)
         else:
@@ -973,7 +1049,10 @@ class JepaEngine:
 
             def wgrads():
                 for i in range(0, len(probs), 8):
-                    ops.wgrad_grouped(probs[i:i + 8])
+                    if self.deterministic:
+                        ops.wgrad_grouped(probs[i:i + 8], workspace=self._det_ws(), deterministic=True)
+                    else:
+                        ops.wgrad_grouped(probs[i:i + 8])
                 if self.use_side:
                     for sl in slots:
                         bw["done"][sl].record(self.side)
@@ -1205,6 +1284,8 @@ class JepaEngine:
         if not getattr(f, "g_clean", False):      # (FusedAdamW.fuse_zero_grad: the last update left the buffer clear)
             f.g32.zero_()
         f.g_clean = False
+        if self.deterministic:
+            self._det_ws()              # (the slabs exist before the first launch; allocated once)
         self.refresh_wt()               # (already done beside the forward; a no-op then)
         rag = self.ragged_step
         Md, dseq = (plan.n_dec, (plan.dec_off, max(plan.max_dec, 1))) if rag else (Mp, None)
@@ -1213,13 +1294,13 @@ class JepaEngine:
         bw = self.bw["dec"]
         # decoder_to_encoder_mapper
         Mo = plan.n_tgt if (rag and self.tail is not None) else Md       # rows that left the predictor
-        ops.colsum_bf16(self.dpreds, f.gptr("decoder_to_encoder_mapper.bias"), M=Mo, N=De, ldx=De)
+        self._colsum_bf16(self.dpreds, f.gptr("decoder_to_encoder_mapper.bias"), M=Mo, N=De, ldx=De)
         self._wgrad(self.dpreds, self.dec_out_b, f.gptr("decoder_to_encoder_mapper.weight"), De, Dd, Mo)
         ops.gemm(self.dpreds, f.ptr16("decoder_to_encoder_mapper.weight"), bw["dx1"], M=Mo, N=Dd, K=De, lda=De, ldb=Dd, ldc=Dd,
                  b_trans=1, epilogue=ops.EPI_ADD_F32)
         last = self.dec_acts[-1]
-        ops.layernorm_bwd(bw["dx1"], last.x2, f.ptr32("decoder.norm.weight"), self.dec_fm, self.dec_fr, M=Mo, D=Dd, ds_f32=bw["dy"],
-                          dgamma=f.gptr("decoder.norm.weight"), dbeta=f.gptr("decoder.norm.bias"), workspace=self.red_ws)
+        self._ln_bwd_direct(bw["dx1"], last.x2, f.ptr32("decoder.norm.weight"), self.dec_fm, self.dec_fr, M=Mo, D=Dd, ds_f32=bw["dy"],
+                            dgamma=f.gptr("decoder.norm.weight"), dbeta=f.gptr("decoder.norm.bias"), workspace=self.red_ws)
         dy, dyb = bw["dy"], None
         for i in range(c.l_dec - 1, -1, -1):
             x_in, xb_in = (self.dec_in, self.dec_in_b) if i == 0 else (self.dec_acts[i - 1].x2, self.dec_acts[i - 1].x2b)
@@ -1234,11 +1315,18 @@ class JepaEngine:
             ops.mask_scatter_fill_pos_bwd(dy, plan.inv, self.d_cf, f.gptr("mask_token"), B=N, T=T, D=Dd, G=G,
                                           rowmap=plan.dec_map if rag else None, partials=ws)
             self._folds.append((ws, Dd, sf_rows, Dd, f.gptr("mask_token"), None, None, Dd))
+        elif self.deterministic:
+            # never the kernel's own atomics: partial rows, folded in order at once
+            if sf_rows * Dd * 4 > self.red_ws.numel() * 4:
+                raise RuntimeError("deterministic mode: the mask-token partial rows do not fit the reduction scratch")
+            ops.mask_scatter_fill_pos_bwd(dy, plan.inv, self.d_cf, f.gptr("mask_token"), B=N, T=T, D=Dd, G=G,
+                                          rowmap=plan.dec_map if rag else None, partials=self.red_ws)
+            self._fold_now(self.red_ws, Dd, sf_rows, Dd, f.gptr("mask_token"), None, None, Dd)
         else:
             ops.mask_scatter_fill_pos_bwd(dy, plan.inv, self.d_cf, f.gptr("mask_token"), B=N, T=T, D=Dd, G=G,
                                           rowmap=plan.dec_map if rag else None)
         # encoder_to_decoder_mapper (rows = gathered context tokens)
-        ops.colsum_bf16(self.d_cf, f.gptr("encoder_to_decoder_mapper.bias"), M=n_ctx, N=Dd, ldx=Dd)
+        self._colsum_bf16(self.d_cf, f.gptr("encoder_to_decoder_mapper.bias"), M=n_ctx, N=Dd, ldx=Dd)
         self._wgrad(self.d_cf, self.ctx_in, f.gptr("encoder_to_decoder_mapper.weight"), Dd, De, n_ctx)
         ops.gemm(self.d_cf, f.ptr16("encoder_to_decoder_mapper.weight"), self.d_ctx_in, M=n_ctx, N=De, K=Dd, lda=Dd, ldb=De,
                  ldc=De, b_trans=1)
@@ -1249,8 +1337,8 @@ class JepaEngine:
         else:
             ops.unmask_rows_f32(self.d_ctx_in, plan.inv, bw["dx1"], M=M, D=De)
         last = self.enc_acts[-1]
-        ops.layernorm_bwd(bw["dx1"], last.x2, f.ptr32("encoder.norm.weight"), self.enc_fm, self.enc_fr, M=Me, D=De, ds_f32=bw["dy"],
-                          dgamma=f.gptr("encoder.norm.weight"), dbeta=f.gptr("encoder.norm.bias"), workspace=self.red_ws)
+        self._ln_bwd_direct(bw["dx1"], last.x2, f.ptr32("encoder.norm.weight"), self.enc_fm, self.enc_fr, M=Me, D=De, ds_f32=bw["dy"],
+                            dgamma=f.gptr("encoder.norm.weight"), dbeta=f.gptr("encoder.norm.bias"), workspace=self.red_ws)
         dy, dyb = bw["dy"], None
         enc_ready = set()
         for i in range(c.l_enc - 1, -1, -1):
@@ -1287,7 +1375,7 @@ class JepaEngine:
         else:
             ops.cast_f32_to_bf16(dy, self.d_lf_b, M * De)
         if self.has_mapper:
-            ops.colsum_bf16(self.d_lf_b, f.gptr("post_extraction_mapper.bias"), M=M, N=De, ldx=De)
+            self._colsum_bf16(self.d_lf_b, f.gptr("post_extraction_mapper.bias"), M=M, N=De, ldx=De)
             self._wgrad(self.d_lf_b, self.fn_b, f.gptr("post_extraction_mapper.weight"), De, C, M)
             ops.gemm(self.d_lf_b, f.ptr16("post_extraction_mapper.weight"), self.d_fn, M=M, N=C, K=De, lda=De, ldb=C, ldc=C,
                      b_trans=1, epilogue=ops.EPI_ADD_F32)
@@ -1296,9 +1384,9 @@ class JepaEngine:
             d_fn = dy
         nl = len(c.conv_spec)
         S, Tc = self.S, self.Tc
-        ops.layernorm_bwd(d_fn, self.post_ptr[-1], f.ptr32("feature_norms.weight"), self.fn_mean, self.fn_rstd, M=M, D=C,
-                          ds_bf16=self.dpost_ptr[-1], dgamma=f.gptr("feature_norms.weight"), dbeta=f.gptr("feature_norms.bias"),
-                          x_is_bf16=True, in_seg=self.P[-1], in_valid=Tc, out_seg=self.P[-1], out_valid=Tc, chan=S if S > 1 else 0)
+        self._ln_bwd_direct(d_fn, self.post_ptr[-1], f.ptr32("feature_norms.weight"), self.fn_mean, self.fn_rstd, M=M, D=C,
+                            ds_bf16=self.dpost_ptr[-1], dgamma=f.gptr("feature_norms.weight"), dbeta=f.gptr("feature_norms.bias"),
+                            x_is_bf16=True, in_seg=self.P[-1], in_valid=Tc, out_seg=self.P[-1], out_valid=Tc, chan=S if S > 1 else 0)
         sparse = rag and self.sparse_conv
         if sparse:
             act_rows = self._conv_rows(plan)
@@ -1338,16 +1426,16 @@ class JepaEngine:
                         def conv_wgrad(l=l, k=k, s=s, dwp=dwp, act=act, n_act=n_act, si=si):
                             dwp.zero_()
                             ops.gemm(self.dpre_ptr[l], self.post_ptr[l - 1], dwp, M=C, N=k * C, K=n_act, lda=C, ldb=s * C, ldc=k * C, a_trans=1,
-                                     b_trans=1, epilogue=ops.EPI_ATOMIC_F32, split_k=ops.pick_split_k(C, k * C, n_act), rowmap=act)
+                                     b_trans=1, epilogue=ops.EPI_ATOMIC_F32, split_k=ops.pick_split_k(C, k * C, n_act), rowmap=act, **self._det_kw())
                             ops.conv_weight_layout(dwp, f.gptr(f"{self.stacks[si]}{l}.0.weight"), C_out=C, C_in=C, k=k, mode=2)
                         self._on_side(conv_wgrad)
                     elif n_act > 0:
                         ops.gemm(self.dpre_ptr[l], self.post_ptr[l - 1], dwp, M=C, N=k * C, K=n_act, lda=C, ldb=s * C, ldc=k * C, a_trans=1,
-                                 b_trans=1, epilogue=ops.EPI_ATOMIC_F32, split_k=ops.pick_split_k(C, k * C, n_act), rowmap=act)
+                                 b_trans=1, epilogue=ops.EPI_ATOMIC_F32, split_k=ops.pick_split_k(C, k * C, n_act), rowmap=act, **self._det_kw())
                 else:
                     ops.gelu_bwd_bf16(self.dpost_ptr[l] + r0, self.pre_ptr[l] + r0, self.dpre_ptr[l] + r0, rows * C)
                     ops.gemm(self.dpre_ptr[l] + r0, self.post_ptr[l - 1] + r0p, dwp, M=C, N=k * C, K=rows, lda=C, ldb=s * C, ldc=k * C,
-                             a_trans=1, b_trans=1, epilogue=ops.EPI_ATOMIC_F32, split_k=ops.pick_split_k(C, k * C, rows))
+                             a_trans=1, b_trans=1, epilogue=ops.EPI_ATOMIC_F32, split_k=ops.pick_split_k(C, k * C, rows), **self._det_kw())
                 if not side_wgrad:
                     ops.conv_weight_layout(dwp, f.gptr(f"{self.stacks[si]}{l}.0.weight"), C_out=C, C_in=C, k=k, mode=2)
                 for rho in range(s):

@@ -110,7 +110,7 @@ def require_gpu() -> None:
 
 def workspace_bytes(fn: str, **dims) -> int:
     """Scratch bytes entry point `fn` needs for the given dimensions (fields of its argument struct), from the library."""
-    struct_name = {"wj_gemm_bf16": "wj_gemm_args", "wj_mask_scatter_fill_pos_bwd": "wj_scatter_fill_bwd_args", "wj_layernorm_bwd": "wj_ln_bwd_args", "wj_attn_bwd": "wj_attn_bwd_args", "wj_conv0_gn_gelu_fwd": "wj_conv0_fwd_args",
+    struct_name = {"wj_gemm_bf16": "wj_gemm_args", "wj_colsum_bf16": "wj_colsum_args", "wj_mask_scatter_fill_pos_bwd": "wj_scatter_fill_bwd_args", "wj_layernorm_bwd": "wj_ln_bwd_args", "wj_attn_bwd": "wj_attn_bwd_args", "wj_conv0_gn_gelu_fwd": "wj_conv0_fwd_args",
                    "wj_conv0_gn_gelu_bwd": "wj_conv0_bwd_args", "wj_masked_mse": "wj_mse_args", "wj_grad_sumsq": "wj_sumsq_args",
                    "wj_rir_convolve": "wj_rir_conv_args", "wj_snr_mix": "wj_snr_mix_args", "wj_mse_groups": "wj_mse_groups_args"}[fn]
     a = STRUCTS[struct_name]()
@@ -124,8 +124,10 @@ def gemm(A: Ptr, B: Ptr, C: Ptr, *, M: int, N: int, K: int, lda: int, ldb: int, 
          b_trans: int = 0, epilogue: int = EPI_BF16, C2: Ptr = None, bias: Ptr = None, aux: Ptr = None, split_k: int = 1,
          seg_rows: int = 0, seg_valid: int = 0, alpha: float = 1.0, colsum: Ptr = None, rowmap: Ptr = None,
          workspace: Optional[torch.Tensor] = None, schedule: Optional[int] = None, persist_cus: Optional[int] = None,
-         stream: Optional[int] = None) -> None:
+         stream: Optional[int] = None, deterministic: bool = False) -> None:
     """workspace: a zero-initialised byte tensor the library may use for K-split pairs (see include/wavjepa_hip.h: wj_gemm_args).
+    deterministic: the split-K weight gradient (EPI_ATOMIC_F32, col-form operands) adds its K slices in a fixed order through slabs in
+    `workspace` (>= workspace_bytes("wj_gemm_bf16", ..., deterministic=1) bytes, contents irrelevant); a short one raises.
     schedule: force tile / schedule variant 0..6 for this call (None: this binding's default, gemm_set_variant; -1: the library picks;
     a variant that cannot run the shape falls back, see the header);
     persist_cus: resident persistent-GEMM workgroups per XCD (None: this binding's default, gemm_set_persist_cus)."""
@@ -135,7 +137,8 @@ def gemm(A: Ptr, B: Ptr, C: Ptr, *, M: int, N: int, K: int, lda: int, ldb: int, 
          lda=lda, ldb=ldb, ldc=ldc, M=M, N=N, K=K, a_trans=a_trans, b_trans=b_trans, epilogue=epilogue, split_k=split_k,
          seg_rows=seg_rows, seg_valid=seg_valid, alpha=alpha, workspace=_p(workspace),
          workspace_bytes=0 if workspace is None else workspace.numel() * workspace.element_size(),
-         schedule=0 if sched < 0 else sched + 1, persist_cus=_PERSIST_CUS if persist_cus is None else int(persist_cus))
+         schedule=0 if sched < 0 else sched + 1, persist_cus=_PERSIST_CUS if persist_cus is None else int(persist_cus),
+         deterministic=int(deterministic))
 
 
 def gemm_mxfp8(A8: Ptr, B8: Ptr, scale_a: Ptr, scale_b: Ptr, C: Ptr, *, M: int, N: int, K: int, lda: int, ldb: int, ldc: int,
@@ -158,14 +161,30 @@ def fp8_scale_dwords(rows: int, K: int) -> int:
     return (K // 128) * rows + 256
 
 
-def wgrad_grouped(problems, stream: Optional[int] = None) -> None:
-    """problems: [(dY, X, gW, n_out, k_in, m_tok)] (<= 8): gW[n_out, k_in] += dY[m_tok, n_out]^T @ X[m_tok, k_in], one launch."""
+def _wgrad_group_args(problems):
     a = STRUCTS["wj_wgrad_group_args"]()
     for i, (dY, X, gW, n_out, k_in, m_tok) in enumerate(problems):
         a.A[i], a.B[i], a.C[i] = _p(dY), _p(X), _p(gW)
         a.lda[i], a.ldb[i], a.ldc[i] = n_out, k_in, k_in
         a.M[i], a.N[i], a.K[i] = n_out, k_in, m_tok
     a.n = len(problems)
+    return a
+
+
+def wgrad_grouped_workspace_bytes(problems) -> int:
+    """Slab bytes the deterministic form of wgrad_grouped(problems) needs (0: no problem of the group is split); pointers are ignored."""
+    a = _wgrad_group_args(problems)
+    a.deterministic = 1
+    return _abi.workspace_bytes("wj_wgrad_grouped", a)
+
+
+def wgrad_grouped(problems, stream: Optional[int] = None, workspace: Optional[torch.Tensor] = None, deterministic: bool = False) -> None:
+    """problems: [(dY, X, gW, n_out, k_in, m_tok)] (<= 8): gW[n_out, k_in] += dY[m_tok, n_out]^T @ X[m_tok, k_in], one launch.
+    deterministic: K slices added in a fixed order through slabs in `workspace` (wgrad_grouped_workspace_bytes; contents irrelevant)."""
+    a = _wgrad_group_args(problems)
+    a.deterministic = int(deterministic)
+    a.workspace = _p(workspace)
+    a.workspace_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
     if PROFILE is None:
         _abi.call("wj_wgrad_grouped", a, _stream() if stream is None else stream)
         return
@@ -251,9 +270,11 @@ def ln_bwd_partial_rows(M: int, D: int) -> int:
     return int(_abi.load().wj_ln_bwd_partial_rows(int(M), int(D)))
 
 
-def colsum_f32_group(items, stream: Optional[int] = None) -> None:
-    """items: [(x, ldx, M, N, o0, o1, o2, n_each)] (<= 16): one launch folds every matrix's column sums into its outputs (+=)."""
+def colsum_f32_group(items, stream: Optional[int] = None, deterministic: bool = False) -> None:
+    """items: [(x, ldx, M, N, o0, o1, o2, n_each)] (<= 16): one launch folds every matrix's column sums into its outputs (+=).
+    deterministic: one adder per column, rows in ascending order (no float atomics)."""
     a = STRUCTS["wj_colsum_group_args"]()
+    a.deterministic = int(deterministic)
     for i, (x, ldx, M, N, o0, o1, o2, n_each) in enumerate(items):
         a.x[i], a.o0[i], a.o1[i], a.o2[i] = _p(x), _p(o0), _p(o1), _p(o2)
         a.ldx[i], a.M[i], a.N[i], a.n_each[i] = ldx, M, N, n_each
@@ -304,12 +325,15 @@ def rccl_bucket_allreduce_finalize() -> None:
     _abi.load().wj_rccl_bucket_allreduce_finalize()
 
 
-def colsum_bf16(x: Ptr, out: Ptr, *, M: int, N: int, ldx: int, stream: Optional[int] = None) -> None:
-    _run("wj_colsum_bf16", "wj_colsum_args", stream, x=_p(x), out=_p(out), ldx=ldx, M=M, N=N)
+def colsum_bf16(x: Ptr, out: Ptr, *, M: int, N: int, ldx: int, stream: Optional[int] = None, workspace: Optional[torch.Tensor] = None,
+                deterministic: bool = False) -> None:
+    """deterministic: partial rows in `workspace` (workspace_bytes("wj_colsum_bf16", M=, N=, deterministic=1) bytes), then one adder per column."""
+    _run("wj_colsum_bf16", "wj_colsum_args", stream, x=_p(x), out=_p(out), ldx=ldx, M=M, N=N, workspace=_p(workspace),
+         workspace_bytes=0 if workspace is None else workspace.numel() * workspace.element_size(), deterministic=int(deterministic))
 
 
-def colsum_f32(x: Ptr, out: Ptr, *, M: int, N: int, ldx: int, stream: Optional[int] = None) -> None:
-    _run("wj_colsum_f32", "wj_colsum_args", stream, x=_p(x), out=_p(out), ldx=ldx, M=M, N=N)
+def colsum_f32(x: Ptr, out: Ptr, *, M: int, N: int, ldx: int, stream: Optional[int] = None, deterministic: bool = False) -> None:
+    _run("wj_colsum_f32", "wj_colsum_args", stream, x=_p(x), out=_p(out), ldx=ldx, M=M, N=N, deterministic=int(deterministic))
 
 
 # ---------------------------------------------------------------------------------------------------------- attention
@@ -322,10 +346,10 @@ def attn_fwd(qkv: Ptr, out: Ptr, *, B: int, T: int, H: int, hd: int, key_mask: P
 
 def attn_bwd(qkv: Ptr, out: Ptr, dout: Ptr, lse: Ptr, dqkv: Ptr, *, B: int, T: int, H: int, hd: int, key_mask: Ptr = None,
              mask_group: int = 1, dbias: Ptr = None, dbias_ws: Ptr = None, seq_off: Ptr = None, defer_fold: bool = False,
-             stream: Optional[int] = None) -> None:
+             stream: Optional[int] = None, deterministic: bool = False) -> None:
     _run("wj_attn_bwd", "wj_attn_bwd_args", stream, qkv=_p(qkv), key_mask=_p(key_mask), seq_off=_p(seq_off), out=_p(out), dout=_p(dout),
          lse=_p(lse), dqkv=_p(dqkv), dbias=_p(dbias), dbias_ws=_p(dbias_ws), B=B, T=T, H=H, hd=hd, mask_group=mask_group,
-         defer_fold=int(defer_fold))
+         defer_fold=int(defer_fold), deterministic=int(deterministic))
 
 
 # ---------------------------------------------------------------------------------------------------------- conv front-end

@@ -123,7 +123,7 @@ class Trainer:
     def __init__(self, accelerator: str = "gpu", max_steps: int = 375000, max_epochs: int = -1, precision: str = "bf16-mixed",
                  devices: int = 1, gradient_clip_val: float = 5.0, gradient_clip_algorithm: str = "norm", strategy: str = "auto",
                  log_every_n_steps: int = 50, default_root_dir: Optional[str] = None, checkpoint_every_n_steps: int = 25000,
-                 **unused):
+                 deterministic: bool = False, **unused):
         if accelerator not in ("gpu", "cuda", "auto"):
             raise ValueError("wavjepa_amd trains on MI355X GPUs only (accelerator='gpu'); there is no CPU path")
         if precision not in ("bf16-mixed", "bf16"):
@@ -136,6 +136,9 @@ class Trainer:
         self.log_every_n_steps = log_every_n_steps
         self.root = default_root_dir
         self.ckpt_every = checkpoint_every_n_steps
+        # True: the engine's deterministic mode (bit-reproducible gradients and updates on one build and GPU model; the WJ_DETERMINISTIC
+        # environment variable switches it on as well).  One GPU: the order of a multi-GPU gradient reduction is RCCL's.
+        self.deterministic = bool(deterministic)
         self.rank, self.local_rank, self.world = init_distributed()
         self.logged: Dict[str, Any] = {}
 
@@ -164,6 +167,8 @@ class Trainer:
         model.trainer = self
         model.train()
         runner = StepRunner(model, self.gradient_clip_val)
+        if self.deterministic:
+            model._ensure_engine().deterministic = True       # before the first step
         if ckpt_path:
             ck = torch.load(ckpt_path, map_location="cpu", weights_only=False)
             model.load_state_dict(ck["state_dict"])
