@@ -548,7 +548,7 @@ int wj_masked_mse(const wj_mse_args*, void* stream);
  * query tells the caller how many BYTES the call described by the SAME argument struct needs (pointers in it are
  * ignored).  `fn` is the entry point's name: "wj_gemm_bf16" / "wj_wgrad_grouped" / "wj_colsum_bf16" (the K-split pair scratch, or with
  * `deterministic` the slabs / partial rows of the store-and-sum forms), "wj_layernorm_bwd", "wj_attn_bwd" (its dbias_ws), "wj_conv0_gn_gelu_fwd",
- * "wj_conv0_gn_gelu_bwd", "wj_masked_mse", "wj_grad_sumsq".  Returns 0 for entry points without scratch, -1 for an unknown
+ * "wj_conv0_gn_gelu_bwd", "wj_masked_mse", "wj_grad_sumsq", "wj_audio_prepare".  Returns 0 for entry points without scratch, -1 for an unknown
  * name or NULL arguments.
  * -----------------------------------------------------------------------------------------------------------*/
 int64_t wj_workspace_bytes(const char* fn, const void* args);
@@ -736,6 +736,46 @@ typedef struct {
     int32_t G;
 } wj_mse_groups_args;
 int wj_mse_groups(const wj_mse_groups_args*, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Audio preparation of the loader on the device (data_modules/WebAudioDataModule.py:43-60 resample,
+ * dataset_functions.py:90-111 normalize_audio + pad_or_truncate): a ragged batch of raw PCM clips -> rows of the [B][1][out_len] f32
+ * tensor that wj_crop_normalize_bf16 reads.  For every LISTED clip b (n = lengths[b]):
+ *       x[j]  = (float) pcm[offsets[b] + j] * 2^-(bits[b] - 1)           (pcm_kind 2: the float itself)
+ *       r[o]  = sum_{k < taps} table[o % nw][k] * xpad[(o / nw) * orig + k]      o < L_r = ceil(nw * n / orig)
+ *               (xpad as in wj_resample_fir below; one fmaf chain over k ascending, so r equals wj_resample_fir's output bit for bit;
+ *               table == NULL needs orig == nw and gives r = x)
+ *       rms   = sqrt(mean_o r[o]^2) over ALL L_r samples, also those beyond out_len
+ *       out[b][o] = r[o] * 10^((-14 - 20 log10 rms) / 20)  for o < min(out_len, L_r),  0 behind;  rms == 0 or skip_normalize: out = r
+ * One call serves the clips of ONE rate pair (orig = file rate / gcd, nw = target rate / gcd, table [nw][taps = 2 * width + orig] f32 on
+ * the device, from wavjepa_amd.resample.sinc_resample_kernel): a batch of mixed rates is one call per rate with the same `out`; rows that
+ * no call lists are not touched.  nw <= 1024 and taps <= 4096, otherwise WJ_ERR_UNSUPPORTED.
+ * pcm / table / out / workspace are DEVICE pointers.  offsets / lengths / bits (one entry per clip of the batch, B each) and clips (n_clips
+ * row indices) are small HOST arrays: they are read during the call only (their values travel as kernel arguments, 32 clips per launch),
+ * which is why every argument error -- also a clip index, a bit depth or a range outside the buffer -- is reported before any launch.
+ * The sum of squares goes through per-workgroup partial records in `workspace` that a second kernel adds in a fixed order; a third
+ * scales in place: no float atomics, two launches give the same bits, and a clip's output does not depend on the other clips.
+ * workspace: wj_workspace_bytes("wj_audio_prepare", args) bytes (from n_clips, max_len and the rate pair); not preserved.
+ * -----------------------------------------------------------------------------------------------------------*/
+typedef struct {
+    const void* pcm;         /* flat sample buffer: int16 (pcm_kind 0; every listed clip <= 16 bits), int32 (1) or f32 (2) */
+    const float* table;      /* [nw][taps] or NULL (orig == nw) */
+    float* out;              /* [B][out_len] */
+    void* workspace;
+    const int64_t* offsets;  /* HOST [B]: first sample of clip b in pcm, in elements */
+    const int32_t* lengths;  /* HOST [B]: samples of clip b at the file rate, 0 .. max_len */
+    const int32_t* bits;     /* HOST [B]: bits per sample, 8..32 (ignored, may be NULL, for pcm_kind 2) */
+    const int32_t* clips;    /* HOST [n_clips]: the rows this call prepares */
+    int64_t pcm_elems;       /* elements in pcm: offsets[b] + lengths[b] beyond it is WJ_ERR_ARG */
+    int64_t workspace_bytes;
+    int32_t B, n_clips;
+    int32_t pcm_kind;
+    int32_t max_len;         /* >= the longest listed clip: sizes the workspace */
+    int32_t orig, nw, width, taps;
+    int32_t out_len;
+    int32_t skip_normalize;  /* 1: out = r (resampled, padded / cut, no loudness gain) */
+} wj_audio_prepare_args;
+int wj_audio_prepare(const wj_audio_prepare_args*, void* stream);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,7 @@ setup: reference train.py:21-35,47-130,160-206,225-250) on top of the HIP engine
 
     python train.py                                   # configs/base.yaml
     python train.py masker=LibriSpeech trainer.steps=1000 trainer.batch_size=32
+    python train.py data=audioset data.data_dirs=/path/to/shards data.device_prep=true    # resampling / loudness / padding on the GPU
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train.py trainer.num_gpus=8
 """
 from __future__ import annotations
@@ -108,7 +109,7 @@ def create_data_source(cfg, nr_patches, device, rank):
         dm = WebAudioDataModule(masker, data_dirs=cfg.data.data_dirs, mixing_weights=cfg.data.get("mixing_weights", None),
                                 batch_size=cfg.trainer.batch_size, nr_samples_per_audio=cfg.data.samples_per_audio,
                                 nr_time_points=nr_patches, in_channels=cfg.data.in_channels, sr=cfg.data.sr, seed=cfg.seed, rank=rank,
-                                world_size=cfg.trainer.num_gpus)
+                                world_size=cfg.trainer.num_gpus, device_prep=bool(cfg.data.get("device_prep", False)), prep_device=device)
         dm.setup("fit")
         return dm.train_dataloader()
     return SyntheticAudioSource(masker, batch_size=cfg.trainer.batch_size, samples_per_audio=cfg.data.samples_per_audio,

@@ -12,7 +12,11 @@ yielding once it holds SHUFFLE_INITIAL = 100 samples, webdataset's `initial` -> 
 wavjepa_amd/audio_io.py; the STREAMINFO MD5 is verified for the first VERIFY_MD5_CLIPS clips of every worker; undecodable
 members and any per-sample failure are reported and skipped, as `wds.warn_and_continue` does) -> channel 0 -> kaiser-sinc
 resampling to `sr` when the file's rate differs -> RMS -14 dBFS, pad / cut to 10 s -> masks from the masker -> batches of
-`batch_size`.  MAX_SHARD_FAILURES unreadable shards in a row raise instead of spinning on warnings.  Several data
+`batch_size`.  With `device_prep=True` a worker stops after "channel 0": it ships the integer PCM, the file's rate and bit depth
+and the masks (drawn at the same point of its stream, so clip order and masks are those of the default mode), and resampling,
+loudness and padding run in the training process on the GPU (wavjepa_amd/audio_prep.py, one batch ahead of the step); clips
+longer than RAW_MAX_SECONDS, or at a rate the kernel does not take, are still prepared here and travel as float32.
+MAX_SHARD_FAILURES unreadable shards in a row raise instead of spinning on warnings.  Several data
 directories are mixed with `mixing_weights` (webdataset's RandomMix: a source is drawn with probability ~ its weight for every
 batch).  Workers are the torch DataLoader's processes, as upstream.
 """
@@ -26,7 +30,9 @@ from typing import Iterator, List, Optional, Sequence, Tuple, Union
 
 import torch
 
-from .. import audio_io
+import numpy as np
+
+from .. import audio_io, audio_prep
 from ..resample import KAISER_BEST, resample_waveform_cpu
 from .dataset_functions import pre_process
 
@@ -119,11 +125,17 @@ class WebAudioDataModule(_Base):
     MAX_SAMPLE_FAILURES: int = 1000          # consecutive samples that fail to decode / prepare before the stream raises (= SHUFFLE)
     NUM_WORKERS: int = 16
     PREFETCH_FACTOR: int = 2
+    RAW_MAX_SECONDS: int = 30                # device_prep: longer clips (the decoder admits 23 minutes) are prepared by the worker
 
     def __init__(self, masker, data_dirs, mixing_weights: Optional[Sequence[float]], batch_size: int = 96, nr_samples_per_audio: int = 16,
                  nr_time_points: int = 100, cache_size: int = 1000, in_channels: int = 1, sr: int = 16000, seed: int = 0, rank: Optional[int] = None,
                  world_size: Optional[int] = None, **kwargs):
+        """Keywords beyond the reference's signature, taken from **kwargs: device_prep (bool, default False: resampling, loudness
+        and padding on the GPU in the training process instead of in the workers) and prep_device (the GPU it uses; default: the
+        current device)."""
         super().__init__()
+        self.device_prep = bool(kwargs.pop("device_prep", False))
+        self.prep_device = kwargs.pop("prep_device", None)
         self.data_dirs = data_dirs
         self.mixing_weights = mixing_weights
         self.batch_size = batch_size
@@ -149,12 +161,29 @@ class WebAudioDataModule(_Base):
         ctx, tgt, vis = self.masker(batch_size=self.nr_samples_per_audio, n_times=self.nr_time_points, in_channels=self.in_channels)
         return audio, ctx, tgt, vis
 
+    def _retrieve_raw(self, data: bytes, verify_md5: bool):
+        """device_prep: FLAC bytes -> (channel-0 samples, rate, bits, state, context_mask, target_indices, ctx_and_target_masks).  The
+        samples stay integer PCM (state PCM); a clip the device is not given (too long, or a rate pair beyond the kernel's table
+        limits) goes through `_retrieve_sample` here and travels as the float32 row it produces (state PREPARED)."""
+        pcm, si = audio_io.decode_flac_pcm(data, verify_md5=verify_md5)
+        rate, bits = int(si.sample_rate), int(si.bits_per_sample)
+        if pcm.shape[0] > self.RAW_MAX_SECONDS * rate or not audio_prep.device_supports(rate, self.sr):
+            wav = np.ascontiguousarray(pcm.T.astype(np.float32) * np.float32(1.0 / float(1 << (bits - 1))))     # = audio_io.decode_flac
+            audio, ctx, tgt, vis = self._retrieve_sample((torch.from_numpy(wav), rate))
+            return audio[0].numpy(), self.sr, 32, audio_prep.PREPARED, ctx, tgt, vis
+        samples = pcm[:, 0].astype(np.int16 if bits <= 16 else np.int32)
+        ctx, tgt, vis = self.masker(batch_size=self.nr_samples_per_audio, n_times=self.nr_time_points, in_channels=self.in_channels)
+        return samples, rate, bits, audio_prep.PCM, ctx, tgt, vis
+
     def _samples(self, shards: List[str], rng: random.Random, shuffle: int) -> Iterator[tuple]:
         """Endless stream of prepared samples: raw samples popped from the shuffle buffer, then decoded and prepared."""
         decoded, failed_in_a_row = 0, 0
         for raw in raw_samples(shards, rng, shuffle, self.SHUFFLE_INITIAL, self.MAX_SHARD_FAILURES):
             try:
-                item = self._retrieve_sample(audio_io.decode_flac(raw["flac"], verify_md5=decoded < self.VERIFY_MD5_CLIPS))
+                if self.device_prep:
+                    item = self._retrieve_raw(raw["flac"], verify_md5=decoded < self.VERIFY_MD5_CLIPS)
+                else:
+                    item = self._retrieve_sample(audio_io.decode_flac(raw["flac"], verify_md5=decoded < self.VERIFY_MD5_CLIPS))
             except Exception as e:                                   # noqa: BLE001  (wds.warn_and_continue: any per-sample failure)
                 warnings.warn(f"{raw.get('__key__')}: {e!r}; skipped")
                 # a corpus in which NOTHING decodes (wrong bit depth, unsupported streams, every clip over the size bound) must not
@@ -180,6 +209,9 @@ class WebAudioDataModule(_Base):
         while True:
             src = rng.choices(range(len(streams)), weights=weights)[0]
             items = [next(streams[src]) for _ in range(self.batch_size)]
+            if self.device_prep:
+                yield audio_prep.RawAudioBatch.collate(items)
+                continue
             yield tuple(torch.stack([it[k] for it in items]) for k in range(4))
 
     # ------------------------------------------------------------------------------------------------ Lightning-style surface
@@ -197,7 +229,11 @@ class WebAudioDataModule(_Base):
         if self.audio_train is None:
             self.setup("fit")
         kw = dict(prefetch_factor=self.PREFETCH_FACTOR) if self.NUM_WORKERS > 0 else {}
-        return DataLoader(_ShardBatches(self), batch_size=None, pin_memory=torch.cuda.is_available(), num_workers=self.NUM_WORKERS, **kw)
+        loader = DataLoader(_ShardBatches(self), batch_size=None, pin_memory=torch.cuda.is_available(), num_workers=self.NUM_WORKERS, **kw)
+        if self.device_prep:
+            # the workers ship RawAudioBatch objects; resampling, loudness and padding run here, on the GPU, one batch ahead of the step
+            return audio_prep.DevicePrepLoader(loader, audio_prep.DevicePrep(self.sr, self.TARGET_SECONDS, self.prep_device))
+        return loader
 
 
 class _ShardBatches(torch.utils.data.IterableDataset):

@@ -112,7 +112,8 @@ def workspace_bytes(fn: str, **dims) -> int:
     """Scratch bytes entry point `fn` needs for the given dimensions (fields of its argument struct), from the library."""
     struct_name = {"wj_gemm_bf16": "wj_gemm_args", "wj_colsum_bf16": "wj_colsum_args", "wj_mask_scatter_fill_pos_bwd": "wj_scatter_fill_bwd_args", "wj_layernorm_bwd": "wj_ln_bwd_args", "wj_attn_bwd": "wj_attn_bwd_args", "wj_conv0_gn_gelu_fwd": "wj_conv0_fwd_args",
                    "wj_conv0_gn_gelu_bwd": "wj_conv0_bwd_args", "wj_masked_mse": "wj_mse_args", "wj_grad_sumsq": "wj_sumsq_args",
-                   "wj_rir_convolve": "wj_rir_conv_args", "wj_snr_mix": "wj_snr_mix_args", "wj_mse_groups": "wj_mse_groups_args"}[fn]
+                   "wj_rir_convolve": "wj_rir_conv_args", "wj_snr_mix": "wj_snr_mix_args", "wj_mse_groups": "wj_mse_groups_args",
+                   "wj_audio_prepare": "wj_audio_prepare_args"}[fn]
     a = STRUCTS[struct_name]()
     for k, v in dims.items():
         setattr(a, k, v)
@@ -517,3 +518,17 @@ def mse_groups(preds: Ptr, targets: Ptr, w: Ptr, loss: Ptr, workspace: Ptr, *, n
     """loss[0] = sum_g w[g] * mean((preds[g] - targets)^2), loss[1 + g] the per-set means; optional gradient (denoiser.py:350-355)."""
     _run("wj_mse_groups", "wj_mse_groups_args", stream, preds=_p(preds), targets=_p(targets), w=_p(w), gscale=_p(gscale), loss=_p(loss),
          dpreds=_p(dpreds), workspace=_p(workspace), n=n, G=G)
+
+
+def audio_prepare(pcm: Ptr, table: Ptr, out: Ptr, workspace: Ptr, *, offsets, lengths, bits, clips, pcm_elems: int, workspace_bytes: int,
+                  B: int, pcm_kind: int, max_len: int, orig: int, nw: int, width: int, taps: int, out_len: int,
+                  skip_normalize: bool = False, stream: Optional[int] = None) -> None:
+    """Raw PCM clips -> resampled, -14 dBFS, padded rows of `out` [B][out_len] (wj_audio_prepare).  `offsets` (int64), `lengths`,
+    `bits`, `clips` (int32) are HOST numpy arrays: the library reads them during the call; pcm_kind 0 / 1 / 2 = int16 / int32 / f32."""
+    import numpy as np
+    host = [np.ascontiguousarray(offsets, dtype=np.int64), np.ascontiguousarray(lengths, dtype=np.int32),
+            None if bits is None else np.ascontiguousarray(bits, dtype=np.int32), np.ascontiguousarray(clips, dtype=np.int32)]
+    _run("wj_audio_prepare", "wj_audio_prepare_args", stream, pcm=_p(pcm), table=_p(table), out=_p(out), workspace=_p(workspace),
+         offsets=host[0].ctypes.data, lengths=host[1].ctypes.data, bits=0 if host[2] is None else host[2].ctypes.data,
+         clips=host[3].ctypes.data, pcm_elems=pcm_elems, workspace_bytes=workspace_bytes, B=B, n_clips=int(host[3].size), pcm_kind=pcm_kind,
+         max_len=max_len, orig=orig, nw=nw, width=width, taps=taps, out_len=out_len, skip_normalize=int(skip_normalize))
