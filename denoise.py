@@ -4,6 +4,7 @@
 starts from the pre-trained WavJEPA checkpoint, which is also the frozen teacher) on the HIP engine.
 
     python denoise.py trainer.teacher_ckpt_weights=runs/last.ckpt data.data_dir=/corpus/a-{000..099}.tar data.rir_dir=... data.noise_dir=...
+    python denoise.py ... data.device_prep=true          # clean and noise clips prepared on the GPU; the workers only decode
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 denoise.py trainer.num_gpus=8 ...
 """
 import os
@@ -49,12 +50,13 @@ def setup_trainer(cfg) -> Trainer:
                    checkpoint_every_n_steps=2500)
 
 
-def create_data_module(cfg, nr_patches, rank: int):
+def create_data_module(cfg, nr_patches, rank: int, prep_device=None):
     return WebAudioDataModuleDenoiser(data_dir=cfg.data.data_dir, noise_dir=cfg.data.noise_dir, rir_dir=cfg.data.rir_dir,
                                       batch_size=cfg.trainer.batch_size, nr_samples_per_audio=cfg.data.samples_per_audio,
                                       nr_time_points=nr_patches, with_rir=cfg.data.with_rir, with_noise=cfg.data.with_noise,
                                       snr_high=cfg.data.snr_high, snr_low=cfg.data.snr_low, seed=cfg.seed, rank=rank,
-                                      world_size=int(cfg.trainer.num_gpus))
+                                      world_size=int(cfg.trainer.num_gpus), device_prep=bool(cfg.data.get("device_prep", False)),
+                                      prep_device=prep_device)
 
 
 def build_model(cfg):
@@ -69,7 +71,7 @@ def main(argv=None):
         torch.manual_seed(cfg.seed)
         trainer = setup_trainer(cfg)
         model, patches = build_model(cfg)
-        data_module = create_data_module(cfg, patches, trainer.rank)
+        data_module = create_data_module(cfg, patches, trainer.rank, torch.device("cuda", trainer.local_rank))
         if trainer.rank == 0:
             print(f"Effective Batch Size is: {cfg.trainer.batch_size * cfg.data.samples_per_audio * cfg.trainer.num_gpus}")
         weights = torch.load(cfg.trainer.teacher_ckpt_weights, weights_only=False)

@@ -548,7 +548,7 @@ int wj_masked_mse(const wj_mse_args*, void* stream);
  * query tells the caller how many BYTES the call described by the SAME argument struct needs (pointers in it are
  * ignored).  `fn` is the entry point's name: "wj_gemm_bf16" / "wj_wgrad_grouped" / "wj_colsum_bf16" (the K-split pair scratch, or with
  * `deterministic` the slabs / partial rows of the store-and-sum forms), "wj_layernorm_bwd", "wj_attn_bwd" (its dbias_ws), "wj_conv0_gn_gelu_fwd",
- * "wj_conv0_gn_gelu_bwd", "wj_masked_mse", "wj_grad_sumsq", "wj_audio_prepare".  Returns 0 for entry points without scratch, -1 for an unknown
+ * "wj_conv0_gn_gelu_bwd", "wj_masked_mse", "wj_grad_sumsq", "wj_audio_prepare", "wj_noise_prepare".  Returns 0 for entry points without scratch, -1 for an unknown
  * name or NULL arguments.
  * -----------------------------------------------------------------------------------------------------------*/
 int64_t wj_workspace_bytes(const char* fn, const void* args);
@@ -776,6 +776,46 @@ typedef struct {
     int32_t skip_normalize;  /* 1: out = r (resampled, padded / cut, no loudness gain) */
 } wj_audio_prepare_args;
 int wj_audio_prepare(const wj_audio_prepare_args*, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Noise-clip preparation of the denoiser stage on the device (dataset_functions.py pre_process_noise, scene_module/
+ * generate_scenes.py:132-154 the cut and the fades, WebAudioDataModuleDenoiser.py:228-243 the placement): a ragged batch of f32 noise
+ * clips AT THE TARGET RATE -> rows of the [B][out_len] f32 tensor scene.generate_scene takes as `noise`.  For every LISTED clip b, with
+ * n = lengths[b], F = fade_len, T = out_len and x[j] = noise[offsets[b] + j]:
+ *       rms = sqrt(mean_j x[j]^2) over ALL n samples (also those a cut removes);  g = 10^((-14 - 20 log10 rms) / 20),  g = 1 when rms == 0
+ *       up[k] = k / (F - 1),  dn[k] = 1 - k / (F - 1)     k < F   (torch.linspace(0, 1, F) and (1, 0, F); F == 1: up = {0}, dn = {1})
+ *       n >  T:  m = T, s = cut_start[b] in [0, n - T),  w[i] = g * x[s + i] * (i >= m - F ? dn[i - (m - F)] : 1),                   p = 0
+ *       n <= T:  m = n,  w[i] = g * x[i] * (i < F ? up[i] : 1) * (i >= m - F ? dn[i - (m - F)] : 1),    p = place_start[b] in [0, T - n]
+ *       out[b][p + i] = w[i] for i < m,  exactly 0.0 everywhere else in the row
+ * (F <= n < 2F: the two ramps overlap and both apply; n == T: no cut, no offset, both fades.)  cut_start is read for n > T only and
+ * place_start for n <= T only.  The scene kernels take noise_length = m and noise_start_idx = p.
+ * noise / out / workspace are DEVICE pointers.  offsets / lengths / cut_start / place_start (B entries each) and clips (n_clips row
+ * indices) are small HOST arrays, read during the call only (their values travel as kernel arguments, 64 clips per launch), which is
+ * why every argument error is WJ_ERR_ARG before any launch: a range outside noise_elems, n < F (the loader's CPU path raises on such
+ * a clip and skips the sample), n > max_len, T < F, F < 1, a cut or an offset out of range, a clip index outside [0, B).
+ * Two kernels: per-workgroup partial sums of squares into `workspace` (groups of four samples counted from the clip's start, so the
+ * order of the additions does not depend on where the clip lies in `noise`), then one kernel that adds the clip's partials in a fixed
+ * order in fp64, forms g and writes the WHOLE row, zeros included (no memset).  No float atomics: two launches give the same bits, a
+ * row does not depend on the other clips of the batch, rows that no call lists are not touched.
+ * workspace: wj_workspace_bytes("wj_noise_prepare", args) bytes (from n_clips and max_len; -1 for dimensions the entry refuses).
+ * -----------------------------------------------------------------------------------------------------------*/
+typedef struct {
+    const float* noise;          /* flat f32 sample buffer */
+    float* out;                  /* [B][out_len] */
+    void* workspace;
+    const int64_t* offsets;      /* HOST [B]: first sample of clip b in noise, in elements */
+    const int32_t* lengths;      /* HOST [B]: n, fade_len .. max_len */
+    const int32_t* cut_start;    /* HOST [B]: s, used when n > out_len */
+    const int32_t* place_start;  /* HOST [B]: p, used when n <= out_len */
+    const int32_t* clips;        /* HOST [n_clips]: the rows this call prepares */
+    int64_t noise_elems;         /* elements in noise: offsets[b] + lengths[b] beyond it is WJ_ERR_ARG */
+    int64_t workspace_bytes;
+    int32_t B, n_clips;
+    int32_t max_len;             /* >= the longest listed clip: sizes the workspace */
+    int32_t out_len;             /* T */
+    int32_t fade_len;            /* F, 1 .. out_len */
+} wj_noise_prepare_args;
+int wj_noise_prepare(const wj_noise_prepare_args*, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,14 @@ pad / cut) as ONE HIP entry, `wj_audio_prepare` (csrc/audio_prep.hip), on a ragg
     DevicePrepLoader   the iterable train_dataloader() returns in raw mode: wraps the DataLoader, prepares one batch ahead
     prepare_waveforms  the same kernel for clips held in memory
 
+The denoiser stage (data_modules/WebAudioDataModuleDenoiser.py, `device_prep=True`) adds the noise branch, `wj_noise_prepare`
+(csrc/noise_prep.hip: -14 dBFS over the whole noise clip, random cut or fade-in + placement, fade-out):
+
+    RawDenoiserBatch     a RawAudioBatch of the clean clips + every noise clip as it came from its `.npy` member in one flat float32
+                         buffer with the worker's draws (cut position, placement), and the RIR / SNR fields unchanged
+    DenoiserDevicePrep   raw batch -> the 7-tuple Denoiser.on_after_batch_transfer takes, audio [B, T] and noise [B, T] on the device;
+                         DevicePrep(32000, 10) for the clean clips, same stream, same two-buffer scheme; DevicePrepLoader takes either
+
 GPU only, no fallback: on a host without a HIP device every entry raises."""
 from __future__ import annotations
 
@@ -96,12 +104,16 @@ class RawAudioBatch:
 class _Pending:
     """A batch whose preparation is enqueued on the side stream."""
 
-    def __init__(self, batch: tuple, done: "torch.cuda.Event"):
-        self._batch, self._done = batch, done
+    def __init__(self, batch: tuple, done: "torch.cuda.Event", fresh: Sequence[torch.Tensor] = ()):
+        self._batch, self._done, self._fresh = batch, done, fresh
 
     def get(self) -> tuple:
-        """Orders the current stream behind the preparation (an event wait on the device, no host synchronise) and hands the batch out."""
-        torch.cuda.current_stream(self._batch[0].device).wait_event(self._done)
+        """Orders the current stream behind the preparation (an event wait on the device, no host synchronise) and hands the batch out.
+        `fresh`: tensors allocated on the side stream for this batch alone; the allocator learns that the current stream reads them."""
+        cur = torch.cuda.current_stream(self._batch[0].device)
+        cur.wait_event(self._done)
+        for t in self._fresh:
+            t.record_stream(cur)
         return self._batch
 
 
@@ -208,11 +220,134 @@ class DevicePrep:
         return self.prepare_async(raw).get()
 
 
-class DevicePrepLoader:
-    """Iterable over prepared batches: pulls RawAudioBatch objects from `loader` and keeps ONE batch ahead of the consumer, so the
-    preparation of batch k + 1 is on the side stream before step k is enqueued."""
+class RawDenoiserBatch:
+    """A denoiser batch as a raw-mode worker ships it.  `clean`: the clean clips (a RawAudioBatch without masks).  Noise clip b is
+    `noise_lengths[b]` float32 samples at the target rate starting at `noise_offsets[b]` of `noise` (every offset a multiple of
+    four floats), exactly as its `.npy` member held them; `cut_start[b]` is the worker's draw for a clip longer than `out_len`,
+    `place_start[b]` for a shorter one (0 where not drawn).  `source_rir` [B, C, L], `noise_rirs` [B, n, C, L] and `snr` [B] are
+    what the default mode's collate makes of them: a field the configuration turns off is a list of None (then `noise` holds one
+    zero and the lengths are 0)."""
 
-    def __init__(self, loader: Iterable, prep: DevicePrep):
+    def __init__(self, clean: RawAudioBatch, noise: torch.Tensor, noise_offsets: torch.Tensor, noise_lengths: torch.Tensor,
+                 cut_start: torch.Tensor, place_start: torch.Tensor, source_rir, noise_rirs, snr, out_len: int):
+        self.clean, self.noise, self.noise_offsets, self.noise_lengths = clean, noise, noise_offsets, noise_lengths
+        self.cut_start, self.place_start = cut_start, place_start
+        self.source_rir, self.noise_rirs, self.snr, self.out_len = source_rir, noise_rirs, snr, int(out_len)
+
+    def __len__(self) -> int:
+        return len(self.clean)
+
+    @property
+    def has_noise(self) -> bool:
+        return isinstance(self.snr, torch.Tensor)
+
+    @property
+    def noise_length(self) -> torch.Tensor:
+        """m: the samples of each noise clip that land in its row (int64 [B], the default mode's `noise_length`)."""
+        return self.noise_lengths.to(torch.int64).clamp(max=self.out_len)
+
+    @property
+    def noise_start_idx(self) -> torch.Tensor:
+        """p (int64 [B], the default mode's `noise_start_idx`)."""
+        return self.place_start.to(torch.int64)
+
+    def noise_clip(self, b: int) -> torch.Tensor:
+        o = int(self.noise_offsets[b])
+        return self.noise[o:o + int(self.noise_lengths[b])]
+
+    def pin_memory(self) -> "RawDenoiserBatch":
+        """For the DataLoader's pinning thread: the sample buffers are what is uploaded in bulk."""
+        self.clean, self.noise = self.clean.pin_memory(), self.noise.pin_memory()
+        return self
+
+    @staticmethod
+    def collate(items: Sequence[tuple], out_len: int) -> "RawDenoiserBatch":
+        """items: (clean item of RawAudioBatch.collate, source_rir | None, noise 1-D float32 numpy | None, cut_start, place_start,
+        noise_rirs | None, snr | None) per sample."""
+        clean = RawAudioBatch.collate([it[0] for it in items])
+        offsets, lengths, total = [], [], 0
+        for it in items:
+            n = 0 if it[2] is None else int(it[2].shape[0])
+            offsets.append(total)
+            lengths.append(n)
+            total += (n + 3) // 4 * 4                                   # 16-byte aligned clips: aligned dwordx4 loads in pass 1
+        noise = np.zeros(max(total, 1), dtype=np.float32)
+        for it, o, n in zip(items, offsets, lengths):
+            if n:
+                noise[o:o + n] = it[2]
+
+        def column(k):
+            col = [it[k] for it in items]
+            if any(c is None for c in col):
+                return col
+            return torch.stack(col) if isinstance(col[0], torch.Tensor) else torch.tensor(col)
+        return RawDenoiserBatch(clean, torch.from_numpy(noise), torch.tensor(offsets, dtype=torch.int64),
+                                torch.tensor(lengths, dtype=torch.int32), torch.tensor([int(it[3]) for it in items], dtype=torch.int32),
+                                torch.tensor([int(it[4]) for it in items], dtype=torch.int32), column(1), column(5), column(6), out_len)
+
+
+class DenoiserDevicePrep:
+    FADE_SECONDS = 0.2                  # generate_scenes.py:132-154
+
+    def __init__(self, sr: int = 32000, seconds: int = 10, device=None):
+        self.clean = DevicePrep(sr, seconds, device)
+        self.sr, self.out_len, self.fade_len = self.clean.sr, self.clean.out_len, int(self.FADE_SECONDS * int(sr))
+        self._noise: List[Optional[torch.Tensor]] = [None, None]
+        self._k = 0
+
+    def prepare_async(self, raw: RawDenoiserBatch) -> _Pending:
+        if raw.out_len != self.out_len:
+            raise ValueError(f"the batch was drawn for rows of {raw.out_len} samples, this object prepares {self.out_len}")
+        pending = self.clean.prepare_async(raw.clean)         # (raises without a GPU); the side stream now waits for the step two batches ago
+        dev = self.clean.device
+        from .engine import _upload_stream
+        side = _upload_stream(dev)
+        B = len(raw)
+        audio = pending._batch[0][:, 0]
+        fresh: List[torch.Tensor] = []
+
+        def up(t):
+            if not isinstance(t, torch.Tensor):
+                return t
+            fresh.append(t.to(dev, non_blocking=True))
+            return fresh[-1]
+        with torch.cuda.stream(side):
+            slot = self._k % 2
+            self._k += 1
+            noise = [None] * B
+            if raw.has_noise:
+                noise = self._noise[slot]
+                if noise is None or noise.shape[0] != B:
+                    noise = self._noise[slot] = torch.empty(B, self.out_len, dtype=torch.float32, device=dev)
+                lengths = raw.noise_lengths.numpy()
+                max_len = int(lengths.max())
+                src = self.clean._upload("noise", raw.noise, side)
+                need = ops.workspace_bytes("wj_noise_prepare", B=B, n_clips=B, max_len=max_len, out_len=self.out_len, fade_len=self.fade_len)
+                if need < 0:
+                    raise ValueError(f"wj_noise_prepare refuses clips of at most {max_len} samples with a fade of {self.fade_len}")
+                ws = self.clean._grown("noise_ws", (need + 3) // 4, torch.float32)
+                ops.noise_prepare(src, noise, ws, offsets=raw.noise_offsets.numpy(), lengths=lengths, cut_start=raw.cut_start.numpy(),
+                                  place_start=raw.place_start.numpy(), clips=np.arange(B, dtype=np.int32), noise_elems=int(raw.noise.numel()),
+                                  workspace_bytes=ws.numel() * 4, B=B, max_len=max_len, out_len=self.out_len, fade_len=self.fade_len,
+                                  stream=side.cuda_stream)
+            batch = (audio, up(raw.source_rir), noise, up(raw.noise_length), up(raw.noise_start_idx), up(raw.noise_rirs), up(raw.snr))
+            done = torch.cuda.Event()
+            done.record(side)
+        return _Pending(batch, done, fresh)
+
+    def prepare(self, raw: RawDenoiserBatch):
+        """-> (audio [B, T] float32 on the device, source_rir, noise [B, T], noise_length, noise_start_idx, noise_rirs, snr): the batch
+        of Denoiser.on_after_batch_transfer.  audio and noise are buffers this object owns, overwritten by the second prepare() after
+        this one."""
+        return self.prepare_async(raw).get()
+
+
+class DevicePrepLoader:
+    """Iterable over prepared batches: pulls RawAudioBatch (RawDenoiserBatch) objects from `loader` and keeps ONE batch ahead of the
+    consumer, so the preparation of batch k + 1 is on the side stream before step k is enqueued.  `prep`: a DevicePrep or a
+    DenoiserDevicePrep."""
+
+    def __init__(self, loader: Iterable, prep):
         self.loader, self.prep = loader, prep
 
     def __iter__(self):

@@ -10,7 +10,14 @@ members of their own tar shards (the reference's RIRDataManager / NoiseDataManag
 here every DataLoader worker keeps its own two streams instead of two extra loader processes feeding queues).  Per sample
 (reference :203-248): channel 0 -> resample to 32 kHz -> -14 dBFS, 10 s; rirs[0] is the source RIR, rirs[1:] the noise RIRs; the noise
 clip is normalised to -14 dBFS, cut at random to the clip length with a 0.2 s fade-out when longer, faded in and out when shorter and
-then placed at a random offset; SNR uniform in [snr_low, snr_high]."""
+then placed at a random offset; SNR uniform in [snr_low, snr_high].
+
+With `device_prep=True` a worker stops after "channel 0" and after reading the noise clip: it ships the clean clip as integer PCM and
+the noise clip as its `.npy` member held it, makes the SAME random draws in the same order (cut position only when the noise is
+longer than 10 s, placement only when shorter, then the SNR: one seed gives the same augmentation in both modes) and leaves
+resampling, loudness, padding, cut, fades and placement to the training process on the GPU (wavjepa_amd/audio_prep.py
+`DenoiserDevicePrep`: `wj_audio_prepare` at 32 kHz + `wj_noise_prepare`, one batch ahead of the step).  Clean clips longer than
+RAW_MAX_SECONDS, or at a rate the kernel does not take, are still prepared here and travel as float32."""
 import io
 import os
 import random
@@ -20,7 +27,7 @@ from typing import Iterator, List, Optional
 import numpy as np
 import torch
 
-from .. import audio_io
+from .. import audio_io, audio_prep
 from ..resample import KAISER_BEST, resample_waveform_cpu
 from .dataset_functions import pre_process, pre_process_noise
 from .WebAudioDataModule import _Base, expand_shards, iterate_shard, raw_samples
@@ -85,11 +92,18 @@ class WebAudioDataModuleDenoiser(_Base):
     VERIFY_MD5_CLIPS: int = 64
     MAX_SHARD_FAILURES: int = 16
     MAX_SAMPLE_FAILURES: int = 1000
+    TARGET_SECONDS: int = 10
+    RAW_MAX_SECONDS: int = 30                # device_prep: longer clean clips are prepared by the worker
 
     def __init__(self, data_dir: str, rir_dir: str, noise_dir: str, batch_size: int = 32, with_noise: bool = False, with_rir: bool = False,
                  nr_samples_per_audio: int = 16, nr_time_points: int = 100, cache_size: int = 1000, snr_low: float = -5.0, snr_high: float = 5.0,
                  seed: int = 0, rank: Optional[int] = None, world_size: Optional[int] = None, **kwargs):
+        """Keywords beyond the reference's signature, taken from **kwargs: device_prep (bool, default False: resampling, loudness,
+        padding and the noise clip's cut / fades / placement on the GPU in the training process instead of in the workers) and
+        prep_device (the GPU it uses; default: the current device)."""
         super().__init__()
+        self.device_prep = bool(kwargs.pop("device_prep", False))
+        self.prep_device = kwargs.pop("prep_device", None)
         self.data_dir, self.rir_dir, self.noise_dir = data_dir, rir_dir, noise_dir
         self.batch_size = batch_size
         self.nr_samples_per_audio = nr_samples_per_audio
@@ -127,6 +141,39 @@ class WebAudioDataModuleDenoiser(_Base):
             snr = torch.distributions.uniform.Uniform(self.snr_low, self.snr_high).sample().item()
         return audio, source_rir, noise, noise_length, noise_start_idx, noise_rirs, snr
 
+    def _augment_raw(self, data: bytes, verify_md5: bool, rir_loader, noise_loader):
+        """device_prep: FLAC bytes -> (clean item of RawAudioBatch.collate, source_rir, noise samples, cut_start, place_start, noise_rirs,
+        snr).  The streams and torch's generator are consumed exactly as `_augment_sample` consumes them."""
+        pcm, si = audio_io.decode_flac_pcm(data, verify_md5=verify_md5)
+        rate, bits = int(si.sample_rate), int(si.bits_per_sample)
+        out_len = self.TARGET_SECONDS * self.sr
+        if pcm.shape[0] > self.RAW_MAX_SECONDS * rate or not audio_prep.device_supports(rate, self.sr):
+            wav = torch.from_numpy(np.ascontiguousarray(pcm[:, 0].astype(np.float32) * np.float32(1.0 / float(1 << (bits - 1)))))
+            if rate != self.sr:
+                wav = resample_waveform_cpu(wav, rate, self.sr, resampling_method="sinc_interp_kaiser", **KAISER_BEST)
+            clean = (pre_process(wav, self.sr).squeeze(0).numpy(), self.sr, 32, audio_prep.PREPARED, None, None, None)
+        else:
+            clean = (pcm[:, 0].astype(np.int16 if bits <= 16 else np.int32), rate, bits, audio_prep.PCM, None, None, None)
+        noise = noise_rirs = snr = source_rir = None
+        cut_start, place_start = 0, 0
+        if self.with_rir:
+            rirs = next(rir_loader)
+            source_rir = rirs[0]
+        if self.with_noise:
+            if self.with_rir:
+                noise_rirs = rirs[1:]
+            noise = next(noise_loader)
+            n, fade = int(noise.shape[-1]), int(0.2 * self.sr)
+            if noise.ndim != 1 or n < fade:
+                raise ValueError(f"a noise clip of shape {tuple(noise.shape)} cannot be faded over {fade} samples")    # (fade_noise raises too)
+            if n > out_len:
+                cut_start = torch.randint(0, n - out_len, (1,)).item()
+            elif n < out_len:
+                place_start = torch.randint(0, out_len - n, (1,)).item()
+            snr = torch.distributions.uniform.Uniform(self.snr_low, self.snr_high).sample().item()
+            noise = noise.numpy()
+        return clean, source_rir, noise, cut_start, place_start, noise_rirs, snr
+
     def _batches(self, worker: int, n_workers: int):
         rng = random.Random(f"{self.seed}/{self.rank}/{self.world_size}/{worker}/{n_workers}")
         torch.manual_seed(rng.randrange(1 << 31))            # the per-sample draws (fade position, offset, SNR) use torch's generator
@@ -139,8 +186,11 @@ class WebAudioDataModuleDenoiser(_Base):
         batch, decoded, failed_in_a_row = [], 0, 0
         for raw in raw_samples(shards, rng, self.SHUFFLE, self.SHUFFLE_INITIAL, self.MAX_SHARD_FAILURES):
             try:
-                item = self._augment_sample(audio_io.decode_flac(raw["flac"], verify_md5=decoded < self.VERIFY_MD5_CLIPS), rir_loader,
-                                            noise_loader)
+                if self.device_prep:
+                    item = self._augment_raw(raw["flac"], decoded < self.VERIFY_MD5_CLIPS, rir_loader, noise_loader)
+                else:
+                    item = self._augment_sample(audio_io.decode_flac(raw["flac"], verify_md5=decoded < self.VERIFY_MD5_CLIPS), rir_loader,
+                                                noise_loader)
             except Exception as e:                           # noqa: BLE001
                 warnings.warn(f"{raw.get('__key__')}: {e!r}; skipped")
                 failed_in_a_row += 1                         # a corpus in which nothing decodes raises instead of warning for ever
@@ -152,7 +202,10 @@ class WebAudioDataModuleDenoiser(_Base):
             failed_in_a_row = 0
             batch.append(item)
             if len(batch) == self.batch_size:
-                yield collate(batch)
+                if self.device_prep:
+                    yield audio_prep.RawDenoiserBatch.collate(batch, self.TARGET_SECONDS * self.sr)
+                else:
+                    yield collate(batch)
                 batch = []
 
     def setup(self, stage: str):
@@ -166,6 +219,10 @@ class WebAudioDataModuleDenoiser(_Base):
         if self.audio_train is None:
             self.setup("fit")
         kw = dict(prefetch_factor=self.PREFETCH_FACTOR) if self.NUM_WORKERS > 0 else {}
+        if self.device_prep:
+            # the workers ship RawDenoiserBatch objects; both clips are prepared here, on the GPU, one batch ahead of the step
+            loader = DataLoader(_DenoiserBatches(self), batch_size=None, pin_memory=torch.cuda.is_available(), num_workers=self.NUM_WORKERS, **kw)
+            return audio_prep.DevicePrepLoader(loader, audio_prep.DenoiserDevicePrep(self.sr, self.TARGET_SECONDS, self.prep_device))
         return DataLoader(_DenoiserBatches(self), batch_size=None, pin_memory=False, num_workers=self.NUM_WORKERS, **kw)
 
 

@@ -113,7 +113,7 @@ def workspace_bytes(fn: str, **dims) -> int:
     struct_name = {"wj_gemm_bf16": "wj_gemm_args", "wj_colsum_bf16": "wj_colsum_args", "wj_mask_scatter_fill_pos_bwd": "wj_scatter_fill_bwd_args", "wj_layernorm_bwd": "wj_ln_bwd_args", "wj_attn_bwd": "wj_attn_bwd_args", "wj_conv0_gn_gelu_fwd": "wj_conv0_fwd_args",
                    "wj_conv0_gn_gelu_bwd": "wj_conv0_bwd_args", "wj_masked_mse": "wj_mse_args", "wj_grad_sumsq": "wj_sumsq_args",
                    "wj_rir_convolve": "wj_rir_conv_args", "wj_snr_mix": "wj_snr_mix_args", "wj_mse_groups": "wj_mse_groups_args",
-                   "wj_audio_prepare": "wj_audio_prepare_args"}[fn]
+                   "wj_audio_prepare": "wj_audio_prepare_args", "wj_noise_prepare": "wj_noise_prepare_args"}[fn]
     a = STRUCTS[struct_name]()
     for k, v in dims.items():
         setattr(a, k, v)
@@ -532,3 +532,17 @@ def audio_prepare(pcm: Ptr, table: Ptr, out: Ptr, workspace: Ptr, *, offsets, le
          offsets=host[0].ctypes.data, lengths=host[1].ctypes.data, bits=0 if host[2] is None else host[2].ctypes.data,
          clips=host[3].ctypes.data, pcm_elems=pcm_elems, workspace_bytes=workspace_bytes, B=B, n_clips=int(host[3].size), pcm_kind=pcm_kind,
          max_len=max_len, orig=orig, nw=nw, width=width, taps=taps, out_len=out_len, skip_normalize=int(skip_normalize))
+
+
+def noise_prepare(noise: Ptr, out: Ptr, workspace: Ptr, *, offsets, lengths, cut_start, place_start, clips, noise_elems: int,
+                  workspace_bytes: int, B: int, max_len: int, out_len: int, fade_len: int, stream: Optional[int] = None) -> None:
+    """f32 noise clips at the target rate -> -14 dBFS, cut or faded in and placed, faded out: rows of `out` [B][out_len]
+    (wj_noise_prepare).  `offsets` (int64), `lengths`, `cut_start`, `place_start`, `clips` (int32) are HOST numpy arrays: the library
+    reads them during the call."""
+    import numpy as np
+    host = [np.ascontiguousarray(offsets, dtype=np.int64)] + [np.ascontiguousarray(v, dtype=np.int32)
+                                                               for v in (lengths, cut_start, place_start, clips)]
+    _run("wj_noise_prepare", "wj_noise_prepare_args", stream, noise=_p(noise), out=_p(out), workspace=_p(workspace),
+         offsets=host[0].ctypes.data, lengths=host[1].ctypes.data, cut_start=host[2].ctypes.data, place_start=host[3].ctypes.data,
+         clips=host[4].ctypes.data, noise_elems=noise_elems, workspace_bytes=workspace_bytes, B=B, n_clips=int(host[4].size),
+         max_len=max_len, out_len=out_len, fade_len=fade_len)
