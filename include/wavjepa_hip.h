@@ -279,6 +279,64 @@ int wj_colsum_f32_group(const wj_colsum_group_args*, void* stream);
 int wj_ln_bwd_partial_rows(int M, int D);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * LayerNorm of a PRE-norm (norm_first=True) stack: x = x + branch(norm(x)), torch TransformerEncoderLayer's norm_first branch.
+ * The fusion point sits half a layer later than above: one kernel adds the PREVIOUS branch into the residual stream and normalises
+ * the sum for the NEXT branch (norm1 of layer i adds layer i-1's linear2 output, norm2 adds out_proj's, a stack's final norm adds the
+ * last linear2 output).
+ *   s = x (+ r);  y = (s - mean) * rstd * gamma + beta
+ *   x: f32 [M][D];  r: bf16 [M][D] or NULL (the first layer of a stack has no branch yet).  Outputs, each optional: s_f32 (the new
+ *   stream; may alias x), y_bf16 (the next GEMM's A operand), y_f32 (a stack's final norm at inference; tests), mean, rstd.
+ *   With none of y_f32 / y_bf16 / mean / rstd the entry only adds (the teacher's last layer: no norm follows it).
+ *   group_stats / group_rows: layout and quarter order of wj_ln_fwd_args.group_stats, but over s, not y -- a pre-norm layer's output
+ *   is the stream, and the teacher targets (wj_instnorm_mean) need its per-clip sums.  Plain stores, no float atomics.
+ *   D: every width wj_layernorm_fwd takes (a multiple of 4, <= 1024).  Additive to ABI 17.
+ * -----------------------------------------------------------------------------------------------------------*/
+typedef struct {
+    const float* x;
+    const void* r;
+    const float* gamma;
+    const float* beta;
+    float* s_f32;
+    float* y_f32;
+    void* y_bf16;
+    float* mean;
+    float* rstd;
+    float* group_stats;
+    int32_t M, D;
+    int32_t group_rows;
+    float eps;
+} wj_ln_pre_fwd_args;
+int wj_layernorm_pre_fwd(const wj_ln_pre_fwd_args*, void* stream);
+
+/* Backward of the above.  ds = (dres) + LN-backward(dy; s, gamma, mean, rstd): the gradient of the stream s.
+ *   dy: f32 [M][D], or bf16 with dy_is_bf16 (the bf16 grad_input of in_proj / linear1);  dres: f32 or NULL -- the gradient that reaches
+ *   s on the residual path (NULL behind a stack's final norm: nothing bypasses it).  Outputs, each optional: ds_f32 (may alias dres),
+ *   ds_bf16 = bf16(ds), the dY of the previous branch's linear2 / out_proj.
+ *   dgamma / dbeta / dbias (dbias = column sums of bf16(ds): the bias gradient of the Linear whose output was added into s) and
+ *   workspace follow wj_ln_bwd_args: atomics into the f32 buffers; or per-workgroup partial rows in workspace
+ *   (wj_workspace_bytes("wj_layernorm_pre_bwd", args) bytes) folded by a second kernel; or, with all three NULL, the partial rows
+ *   ([wj_ln_pre_bwd_partial_rows(M, D)][3][D]) left in place for a later wj_colsum_f32_group. */
+typedef struct {
+    const void* dy;
+    const float* dres;
+    const float* s;
+    const float* gamma;
+    const float* mean;
+    const float* rstd;
+    float* ds_f32;
+    void* ds_bf16;
+    float* dgamma;
+    float* dbeta;
+    float* dbias;
+    float* workspace;
+    int32_t M, D;
+    int32_t dy_is_bf16;
+} wj_ln_pre_bwd_args;
+int wj_layernorm_pre_bwd(const wj_ln_pre_bwd_args*, void* stream);
+/* rows of partials wj_layernorm_pre_bwd writes for M token rows of width D (its workgroup count); no stream, no device work */
+int wj_ln_pre_bwd_partial_rows(int M, int D);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Multi-head self-attention with a key-padding mask, forward and backward.
  * Replaces F.multi_head_attention_forward / scaled_dot_product_attention inside nn.TransformerEncoderLayer for the
  * student (jepa.py:397,452, mask = ctx_masks), the predictor (jepa.py:438, mask = ctx_and_target_masks) and the

@@ -3,6 +3,7 @@
 (a ring of buffer sets larger than the L2 + MALL so that no launch finds its inputs cached).
 
   python tools/ln_bench.py                      # the step's shapes: teacher 51200 x 768, student 10045 x 768, predictor 86781 x 384
+                                                # (post-norm kernels, and the pre-norm ones of norm_first stacks beside them)
   WJ_LN_BWD_ONE_PASS_ROWS=0 python tools/ln_bench.py   # backward with four passes per wave whatever M is
 
 Environment switches are read by the library at its first launch, so each configuration is its own process."""
@@ -16,7 +17,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from wavjepa_amd import ops  # noqa: E402
 
-SHAPES = [("teacher", 51200, 768), ("student", 10045, 768), ("predictor", 86781, 384), ("predictor-last", 46601, 384)]
+SHAPES = [("teacher", 51200, 768), ("student", 10045, 768), ("predictor", 86781, 384), ("predictor-last", 46601, 384),
+          ("predictor-ragged", 21600, 384)]
 
 
 def main():
@@ -44,7 +46,15 @@ def main():
             ops.layernorm_bwd(s["dy"], s["x"], gamma, s["mean"], s["rstd"], M=M, D=D, r=s["r"], dy2=s["dy2"], dy2_is_bf16=True,
                               ds_f32=s["ds"], ds_bf16=s["dsb"], workspace=ws)
 
-        for label, fn, bytes_per in (("fwd", fwd, 12), ("bwd", bwd, 18)):
+        # pre-norm: s = x + r stored as f32 beside y (bf16); the backward reads s, dy (bf16) and the residual-path gradient -- no r
+        def pre_fwd(s):
+            ops.layernorm_pre_fwd(s["x"], gamma, beta, M=M, D=D, eps=1e-5, r=s["r"], s_f32=s["y"], y_bf16=s["yb"], mean=s["mean"], rstd=s["rstd"])
+
+        def pre_bwd(s):
+            ops.layernorm_pre_bwd(s["dy2"], s["x"], gamma, s["mean"], s["rstd"], M=M, D=D, dy_is_bf16=True, dres=s["dy"], ds_f32=s["ds"],
+                                  ds_bf16=s["dsb"], workspace=ws)
+
+        for label, fn, bytes_per in (("fwd", fwd, 12), ("bwd", bwd, 18), ("pre-fwd", pre_fwd, 12), ("pre-bwd", pre_bwd, 16)):
             for s in sets:
                 fwd(s)
                 fn(s)
@@ -59,8 +69,8 @@ def main():
             torch.cuda.synchronize()
             us = sorted(a.elapsed_time(b) * 1e3 for a, b in times)
             med = us[len(us) // 2]
-            print(f"{name:15s} {label} M={M:6d} D={D:4d}  median {med:7.1f} us  min {us[0]:7.1f}  {M * D * bytes_per / med / 1e6:6.2f} TB/s "
-                  f"({M * D * bytes_per / 1e6:.0f} MB, partial rows {ops.ln_bwd_partial_rows(M, D) if label == 'bwd' else '-'})", flush=True)
+            print(f"{name:16s} {label:7s} M={M:6d} D={D:4d}  median {med:7.1f} us  min {us[0]:7.1f}  {M * D * bytes_per / med / 1e6:6.2f} TB/s "
+                  f"({M * D * bytes_per / 1e6:.0f} MB, partial rows {ops.ln_bwd_partial_rows(M, D) if label.endswith('bwd') else '-'})", flush=True)
 
 
 if __name__ == "__main__":

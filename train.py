@@ -66,10 +66,14 @@ class ComponentFactory:
         cls = NETWORKS.get(cfg.model)
         if cls is None:
             raise ValueError(f"Unknown network type: {cfg.model}. Available networks: {list(NETWORKS.keys())}")
+        # trainer.norm_first: pre-norm layers in every stack; trainer.norm_first_decoder: the predictor's own setting (default: the same)
+        norm_first = bool(cfg.trainer.get("norm_first", False))
+        norm_first_dec = bool(cfg.trainer.get("norm_first_decoder", norm_first))
         try:
             return cls(feature_extractor=extractor, transformer_encoder_cfg=TransformerEncoderCFG.create(),
-                       transformer_encoder_layers_cfg=TransformerLayerCFG.create(), transformer_decoder_cfg=TransformerEncoderCFG.create(),
-                       transformer_decoder_layers_cfg=TransformerLayerCFG.create(d_model=384), lr=cfg.optimizer.lr,
+                       transformer_encoder_layers_cfg=TransformerLayerCFG.create(norm_first=norm_first),
+                       transformer_decoder_cfg=TransformerEncoderCFG.create(),
+                       transformer_decoder_layers_cfg=TransformerLayerCFG.create(d_model=384, norm_first=norm_first_dec), lr=cfg.optimizer.lr,
                        adam_betas=(cfg.optimizer.b1, cfg.optimizer.b2), adam_weight_decay=cfg.optimizer.weight_decay,
                        resample_sr=cfg.data.sr, process_audio_seconds=cfg.data.process_seconds,
                        nr_samples_per_audio=cfg.data.samples_per_audio, compile_modules=cfg.trainer.compile_modules,

@@ -595,7 +595,7 @@ extern "C" int wj_device_count(void) {
 extern "C" int wj_struct_size(const char* name) {
     if (!name) return -1;
 #define WJ_SZ(T) if (!strcmp(name, #T)) return (int)sizeof(T);
-    WJ_SZ(wj_gemm_args) WJ_SZ(wj_ln_fwd_args) WJ_SZ(wj_ln_bwd_args) WJ_SZ(wj_colsum_args) WJ_SZ(wj_attn_fwd_args)
+    WJ_SZ(wj_gemm_args) WJ_SZ(wj_ln_fwd_args) WJ_SZ(wj_ln_bwd_args) WJ_SZ(wj_ln_pre_fwd_args) WJ_SZ(wj_ln_pre_bwd_args) WJ_SZ(wj_colsum_args) WJ_SZ(wj_attn_fwd_args)
     WJ_SZ(wj_attn_bwd_args) WJ_SZ(wj_conv0_fwd_args) WJ_SZ(wj_conv0_bwd_args) WJ_SZ(wj_gelu_bwd_args) WJ_SZ(wj_conv_w_args)
     WJ_SZ(wj_add_pos_args) WJ_SZ(wj_gather_args) WJ_SZ(wj_scatter_fill_args) WJ_SZ(wj_scatter_fill_bwd_args)
     WJ_SZ(wj_unmask_rows_args) WJ_SZ(wj_instnorm_args) WJ_SZ(wj_mse_args) WJ_SZ(wj_ema_args) WJ_SZ(wj_sumsq_args)
@@ -629,6 +629,7 @@ extern "C" int64_t wj_workspace_bytes(const char* fn, const void* args) {
         return (int64_t)wj_scatter_fill_bwd_partial_rows(a->B, a->T) * a->D * 4;
     }
     if (!strcmp(fn, "wj_layernorm_bwd")) return 1536LL * 3 * ((const wj_ln_bwd_args*)args)->D * 4;
+    if (!strcmp(fn, "wj_layernorm_pre_bwd")) return 1536LL * 3 * ((const wj_ln_pre_bwd_args*)args)->D * 4;   // the same grid cap
     if (!strcmp(fn, "wj_attn_bwd")) {
         const wj_attn_bwd_args* a = (const wj_attn_bwd_args*)args;
         return (int64_t)a->B * 3 * a->H * a->hd * 4;
@@ -645,7 +646,7 @@ extern "C" int64_t wj_workspace_bytes(const char* fn, const void* args) {
     if (!strcmp(fn, "wj_mse_groups")) return wj_mse_groups_ws_bytes((const wj_mse_groups_args*)args);
     if (!strcmp(fn, "wj_audio_prepare")) return wj_audio_prepare_ws_bytes((const wj_audio_prepare_args*)args);
     if (!strcmp(fn, "wj_noise_prepare")) return wj_noise_prepare_ws_bytes((const wj_noise_prepare_args*)args);
-    static const char* const none[] = {"wj_layernorm_fwd", "wj_colsum_f32", "wj_attn_fwd", "wj_gelu_bwd_bf16",
+    static const char* const none[] = {"wj_layernorm_fwd", "wj_layernorm_pre_fwd", "wj_colsum_f32", "wj_attn_fwd", "wj_gelu_bwd_bf16",
         "wj_conv_weight_layout", "wj_add_pos", "wj_mask_gather_rows", "wj_mask_scatter_fill_pos",
         "wj_unmask_rows_f32", "wj_instnorm_accumulate", "wj_instnorm_mean", "wj_ema_update", "wj_adamw_step", "wj_cast_f32_to_bf16",
         "wj_crop_normalize_bf16", "wj_zero_rows", "wj_spin", "wj_gemm_mxfp8", "wj_quantize_mxfp8", "wj_resample_fir", "wj_transpose_bf16", "wj_colsum_f32_group", "wj_rccl_bucket_allreduce_launch", "wj_rccl_bucket_allreduce_wait", "wj_collective_footprint"};

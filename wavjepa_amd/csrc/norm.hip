@@ -378,6 +378,242 @@ __global__ __launch_bounds__(BWD_THREADS) void ln_bwd_kernel(wj_ln_bwd_args a) {
     }
 }
 
+// ---- pre-norm (norm_first) stacks: x = x + branch(LN(x)) --------------------------------------------------------------------------
+// The fusion point sits half a layer later than in the post-norm kernels above: ONE kernel adds the previous branch into the residual
+// stream and normalises the sum for the next branch.  s = x (+ r) is the new stream (stored as f32, in place when s_f32 == x: a lane
+// reads exactly the elements it writes), y = LN(s) the next GEMM's A operand.  Same row ownership, vector widths and reductions as
+// ln_fwd_kernel; group_stats are taken over s (a pre-norm layer's OUTPUT is the stream).  Without any of y / mean / rstd the kernel
+// only adds (the teacher's last layer has no norm behind it).
+template <int V, int LPR>
+__global__ __launch_bounds__(256) void ln_pre_fwd_kernel(wj_ln_pre_fwd_args a) {
+    constexpr int RPW = 64 / LPR;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int li = lane % LPR, sr = lane / LPR;
+    const int D = a.D;
+    const float invD = 1.0f / (float)D;
+    const bool norm = a.y_f32 || a.y_bf16 || a.mean || a.rstd;          // kernel-uniform
+    f32x4 gam[V], bet[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        const int col = li * 4 + LPR * 4 * j;
+        gam[j] = bet[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (col < D) {
+            gam[j] = *reinterpret_cast<const f32x4*>(a.gamma + col);
+            bet[j] = *reinterpret_cast<const f32x4*>(a.beta + col);
+        }
+    }
+    // row assignment exactly as ln_fwd_kernel: interleaved over the grid, or (group_stats) a contiguous quarter of one group per workgroup
+    int m_begin = (blockIdx.x * 4 + wave) * RPW + sr, m_end = a.M, m_step = gridDim.x * 4 * RPW;
+    if (a.group_stats) {
+        const int grp = blockIdx.x / GS_SPLIT, part = blockIdx.x - grp * GS_SPLIT;
+        const int rpp = (a.group_rows + GS_SPLIT - 1) / GS_SPLIT;
+        m_begin = grp * a.group_rows + part * rpp + wave * RPW + sr;
+        m_end = min(a.M, grp * a.group_rows + min(a.group_rows, (part + 1) * rpp));
+        m_step = 4 * RPW;
+    }
+    float gs1 = 0.f, gs2 = 0.f;
+    for (int m = m_begin; m < m_end; m += m_step) {
+        f32x4 s[V];
+        float sum = 0.f;
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const int col = li * 4 + LPR * 4 * j;
+            s[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (col < D) {
+                s[j] = *reinterpret_cast<const f32x4*>(a.x + (long)m * D + col);
+                if (a.r) {
+                    const bf16x4 r = *reinterpret_cast<const bf16x4*>((const bf16_t*)a.r + (long)m * D + col);
+                    s[j] += f32x4{bf2f(r[0]), bf2f(r[1]), bf2f(r[2]), bf2f(r[3])};
+                }
+                if (a.s_f32) *reinterpret_cast<f32x4*>(a.s_f32 + (long)m * D + col) = s[j];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    sum += s[j][e];
+                    gs1 += s[j][e];
+                    gs2 = fmaf(s[j][e], s[j][e], gs2);
+                }
+            }
+        }
+        if (!norm) continue;
+        const float mean = row_sum<V, LPR>(sum) * invD;
+        float sq = 0.f;
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const int col = li * 4 + LPR * 4 * j;
+            if (col < D) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float d = s[j][e] - mean;
+                    sq += d * d;
+                }
+            }
+        }
+        const float var = row_sum<V, LPR>(sq) * invD;
+        const float rstd = rsqrtf(var + a.eps);
+        if (li == 0) {
+            if (a.mean) a.mean[m] = mean;
+            if (a.rstd) a.rstd[m] = rstd;
+        }
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const int col = li * 4 + LPR * 4 * j;
+            if (col < D) {
+                f32x4 y;
+                bf16x4 o;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    y[e] = (s[j][e] - mean) * rstd * gam[j][e] + bet[j][e];
+                    o[e] = f2bf(y[e]);
+                }
+                if (a.y_f32) *reinterpret_cast<f32x4*>(a.y_f32 + (long)m * D + col) = y;
+                if (a.y_bf16) *reinterpret_cast<bf16x4*>((bf16_t*)a.y_bf16 + (long)m * D + col) = o;
+            }
+        }
+    }
+    if (a.group_stats) {                     // kernel-uniform: fold lanes, then waves, then one pair of stores per workgroup
+        __shared__ float gred[4][2];
+        gs1 = wave_sum(gs1);
+        gs2 = wave_sum(gs2);
+        if (lane == 0) { gred[wave][0] = gs1; gred[wave][1] = gs2; }
+        __syncthreads();
+        if (threadIdx.x < 2) {
+            float* gsp = a.group_stats + (long)blockIdx.x * 2;         // [group][GS_SPLIT][2]
+            gsp[threadIdx.x] = gred[0][threadIdx.x] + gred[1][threadIdx.x] + gred[2][threadIdx.x] + gred[3][threadIdx.x];
+        }
+    }
+}
+
+// Backward of the above: ds = (dres) + LN-backward(dy; s, gamma, mean, rstd).  dres is the gradient that bypasses the norm on the
+// residual path (NULL behind a stack's final norm), dy the grad_input of the branch's first Linear (bf16 under autocast) or an f32
+// gradient.  One operand fewer than ln_bwd_kernel (the stream s was stored, there is no r to add back).  ds_bf16 = bf16(ds) is the dY
+// of the PREVIOUS branch's last Linear and dbias its bias gradient.  Grid, row slots and the column-partial epilogue are ln_bwd_kernel's.
+template <int V, int LPR>
+__global__ __launch_bounds__(BWD_THREADS) void ln_pre_bwd_kernel(wj_ln_pre_bwd_args a) {
+    constexpr int RPW = 64 / LPR;
+    constexpr int CW = LPR * 4 * V;                 // columns covered (>= D)
+    constexpr int nw = BWD_THREADS / 64;
+    __shared__ float cacc[nw][3][CW];               // per-wave column partials, added in wave order below
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int li = lane % LPR, sr = lane / LPR;
+    const int D = a.D;
+    const float invD = 1.0f / (float)D;
+
+    f32x4 dg[V], db[V], dbi[V], gam[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        dg[j] = db[j] = dbi[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        const int col = li * 4 + LPR * 4 * j;
+        gam[j] = col < D ? *reinterpret_cast<const f32x4*>(a.gamma + col) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    const int stride = gridDim.x * nw * RPW;
+    for (int m0 = (blockIdx.x * nw + wave) * RPW + sr; m0 < a.M; m0 += 2 * stride) {
+        int mrow[2] = {m0, m0 + stride};
+        f32x4 xh[2][V], dy[2][V];
+        float mean[2], rstd[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const bool live = mrow[u] < a.M;
+            const int m = live ? mrow[u] : m0;
+            mean[u] = a.mean[m];
+            rstd[u] = a.rstd[m];
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const int col = li * 4 + LPR * 4 * j;
+                xh[u][j] = dy[u][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (col < D) {
+                    xh[u][j] = *reinterpret_cast<const f32x4*>(a.s + (long)m * D + col);
+                    dy[u][j] = load4(a.dy, (long)m, D, col, a.dy_is_bf16);
+                }
+            }
+        }
+        float c1[2] = {0.f, 0.f}, c2[2] = {0.f, 0.f};
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const int col = li * 4 + LPR * 4 * j;
+                if (col < D) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        xh[u][j][e] = (xh[u][j][e] - mean[u]) * rstd[u];
+                        const float g = dy[u][j][e] * gam[j][e];
+                        c1[u] += g;
+                        c2[u] += g * xh[u][j][e];
+                    }
+                }
+            }
+#pragma unroll
+        for (int o = LPR / 2; o > 0; o >>= 1) {      // four reductions interleaved
+            c1[0] += __shfl_xor(c1[0], o, 64); c2[0] += __shfl_xor(c2[0], o, 64);
+            c1[1] += __shfl_xor(c1[1], o, 64); c2[1] += __shfl_xor(c2[1], o, 64);
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            if (mrow[u] >= a.M) continue;
+            const int m = mrow[u];
+            const float k1 = c1[u] * invD, k2 = c2[u] * invD;
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const int col = li * 4 + LPR * 4 * j;
+                if (col < D) {
+                    // the residual-path gradient is read here, not with s and dy: held across the reductions it costs 8 V registers
+                    // (D = 768: 174 against 150, two waves per SIMD instead of three)
+                    f32x4 ds = a.dres ? *reinterpret_cast<const f32x4*>(a.dres + (long)m * D + col) : f32x4{0.f, 0.f, 0.f, 0.f};
+                    bf16x4 dsb;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        ds[e] += rstd[u] * (dy[u][j][e] * gam[j][e] - k1 - xh[u][j][e] * k2);
+                        dsb[e] = f2bf(ds[e]);
+                        dg[j][e] += dy[u][j][e] * xh[u][j][e];
+                        db[j][e] += dy[u][j][e];
+                        dbi[j][e] += bf2f(dsb[e]);
+                    }
+                    if (a.ds_f32) *reinterpret_cast<f32x4*>(a.ds_f32 + (long)m * D + col) = ds;
+                    if (a.ds_bf16) *reinterpret_cast<bf16x4*>((bf16_t*)a.ds_bf16 + (long)m * D + col) = dsb;
+                }
+            }
+        }
+    }
+    if constexpr (RPW == 2) {                       // fold the two sub-rows of the wave before touching LDS
+#pragma unroll
+        for (int j = 0; j < V; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                dg[j][e] += __shfl_xor(dg[j][e], 32, 64);
+                db[j][e] += __shfl_xor(db[j][e], 32, 64);
+                dbi[j][e] += __shfl_xor(dbi[j][e], 32, 64);
+            }
+    }
+    if (sr == 0) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const int col = li * 4 + LPR * 4 * j;
+            if (col < D) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    cacc[wave][0][col + e] = dg[j][e];
+                    cacc[wave][1][col + e] = db[j][e];
+                    cacc[wave][2][col + e] = dbi[j][e];
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (a.workspace) {   // plain coalesced stores of this workgroup's partials; a second kernel folds them
+        float* ws = a.workspace + (long)blockIdx.x * 3 * D;
+        for (int c = threadIdx.x; c < 3 * D; c += BWD_THREADS) {
+            const int w = c / D, cc = c % D;
+            ws[c] = cacc[0][w][cc] + cacc[1][w][cc] + cacc[2][w][cc] + cacc[3][w][cc];
+        }
+        return;
+    }
+    for (int c = threadIdx.x; c < D; c += BWD_THREADS) {
+        if (a.dgamma) atomicAdd(a.dgamma + c, cacc[0][0][c] + cacc[1][0][c] + cacc[2][0][c] + cacc[3][0][c]);
+        if (a.dbeta) atomicAdd(a.dbeta + c, cacc[0][1][c] + cacc[1][1][c] + cacc[2][1][c] + cacc[3][1][c]);
+        if (a.dbias) atomicAdd(a.dbias + c, cacc[0][2][c] + cacc[1][2][c] + cacc[2][2][c] + cacc[3][2][c]);
+    }
+}
+
 // out[c] += sum over rows of an f32 matrix: workgroup = 128 columns x a row range (float4 per thread, 8 row lanes)
 __global__ __launch_bounds__(256) void colsum_f32_kernel(const float* __restrict__ x, long ldx, int M, int N,
                                                          float* __restrict__ o0, float* __restrict__ o1, float* __restrict__ o2,
@@ -672,6 +908,62 @@ extern "C" int wj_layernorm_bwd(const wj_ln_bwd_args* a, void* stream) {
             case 2: hipLaunchKernelGGL((ln_bwd_kernel<2, 64>), g, b, 0, s, *a); break;
             case 3: hipLaunchKernelGGL((ln_bwd_kernel<3, 64>), g, b, 0, s, *a); break;
             default: hipLaunchKernelGGL((ln_bwd_kernel<4, 64>), g, b, 0, s, *a); break;
+        }
+    }
+    if (a->workspace && (a->dgamma || a->dbeta || a->dbias))
+        launch_colsum_f32(a->workspace, 3L * a->D, grid, 3 * a->D, a->dgamma, a->dbeta, a->dbias, a->D, (hipStream_t)stream);
+    WJ_CHECK_LAUNCH();
+    return WJ_OK;
+}
+
+// ---- pre-norm entries (the dispatch over D is the post-norm kernels')
+extern "C" int wj_layernorm_pre_fwd(const wj_ln_pre_fwd_args* a, void* stream) {
+    if (!a || !a->x || !a->gamma || !a->beta) return WJ_ERR_ARG;
+    if (a->M <= 0 || a->D <= 0 || (a->D & 3) || a->D > 256 * MAXV) return WJ_ERR_ARG;
+    if (a->group_stats && a->group_rows <= 0) return WJ_ERR_ARG;
+    WJ_CLEAR_STALE_ERROR();
+    const bool half = (a->D % 128 == 0) && (a->D % 256 != 0) && a->D <= 384;   // 128 / 384: 32 lanes per row
+    const int rpw = half ? 2 : 1;
+    int grid = (a->M + 4 * rpw - 1) / (4 * rpw);
+    if (grid > 8192) grid = 8192;
+    if (a->group_stats) grid = ((a->M + a->group_rows - 1) / a->group_rows) * GS_SPLIT;
+    dim3 g(grid), b(256);
+    hipStream_t s = (hipStream_t)stream;
+    if (half) {
+        if (a->D == 128) hipLaunchKernelGGL((ln_pre_fwd_kernel<1, 32>), g, b, 0, s, *a);
+        else hipLaunchKernelGGL((ln_pre_fwd_kernel<3, 32>), g, b, 0, s, *a);
+    } else {
+        switch ((a->D + 255) / 256) {
+            case 1: hipLaunchKernelGGL((ln_pre_fwd_kernel<1, 64>), g, b, 0, s, *a); break;
+            case 2: hipLaunchKernelGGL((ln_pre_fwd_kernel<2, 64>), g, b, 0, s, *a); break;
+            case 3: hipLaunchKernelGGL((ln_pre_fwd_kernel<3, 64>), g, b, 0, s, *a); break;
+            default: hipLaunchKernelGGL((ln_pre_fwd_kernel<4, 64>), g, b, 0, s, *a); break;
+        }
+    }
+    WJ_CHECK_LAUNCH();
+    return WJ_OK;
+}
+
+// the backward runs on wj_layernorm_bwd's grid: the same partial rows
+extern "C" int wj_ln_pre_bwd_partial_rows(int M, int D) { return wj_ln_bwd_partial_rows(M, D); }
+
+extern "C" int wj_layernorm_pre_bwd(const wj_ln_pre_bwd_args* a, void* stream) {
+    if (!a || !a->dy || !a->s || !a->gamma || !a->mean || !a->rstd) return WJ_ERR_ARG;
+    if (a->M <= 0 || a->D <= 0 || (a->D & 3) || a->D > 256 * MAXV) return WJ_ERR_ARG;
+    WJ_CLEAR_STALE_ERROR();
+    const bool half = (a->D % 128 == 0) && (a->D % 256 != 0) && a->D <= 384;
+    const int grid = ln_bwd_grid(a->M, a->D);
+    dim3 g(grid), b(BWD_THREADS);
+    hipStream_t s = (hipStream_t)stream;
+    if (half) {
+        if (a->D == 128) hipLaunchKernelGGL((ln_pre_bwd_kernel<1, 32>), g, b, 0, s, *a);
+        else hipLaunchKernelGGL((ln_pre_bwd_kernel<3, 32>), g, b, 0, s, *a);
+    } else {
+        switch ((a->D + 255) / 256) {
+            case 1: hipLaunchKernelGGL((ln_pre_bwd_kernel<1, 64>), g, b, 0, s, *a); break;
+            case 2: hipLaunchKernelGGL((ln_pre_bwd_kernel<2, 64>), g, b, 0, s, *a); break;
+            case 3: hipLaunchKernelGGL((ln_pre_bwd_kernel<3, 64>), g, b, 0, s, *a); break;
+            default: hipLaunchKernelGGL((ln_pre_bwd_kernel<4, 64>), g, b, 0, s, *a); break;
         }
     }
     if (a->workspace && (a->dgamma || a->dbeta || a->dbias))

@@ -135,6 +135,8 @@ class Denoiser(_ModuleBase):
             enc_c.update(num_layers=24)
         self.n_encoder_heads = enc_l["nhead"]
         self.encoder_embedding_dim = enc_l["d_model"]
+        if enc_l.get("norm_first", False):
+            raise NotImplementedError("the Denoiser stage runs post-norm stacks only (norm_first=False); pre-norm is a JEPA pre-training option")
         self.encoder = TransformerStack(enc_l, enc_c["num_layers"])
         c_feat = feature_extractor.embedding_dim
         self.post_extraction_mapper = nn.Linear(c_feat, self.encoder_embedding_dim) if c_feat != self.encoder_embedding_dim else None

@@ -49,6 +49,8 @@ class EngineConfig:
     conv_prefixes: Sequence[str] = ("extract_audio.cnn.",)   # state_dict prefix of every stream's stack (one entry: shared weights)
     ln_eps: float = 1e-6    # transformer layers (reference types/wavjepa_configs.py:37)
     norm_eps: float = 1e-5  # feature_norms / final norms (nn.LayerNorm default)
+    norm_first_enc: bool = False   # pre-norm layers x = x + branch(LN(x)) in the student AND the teacher (nn.TransformerEncoderLayer norm_first)
+    norm_first_dec: bool = False   # ... in the predictor
 
 
 @dataclass
@@ -357,6 +359,7 @@ class JepaEngine:
         # re-quantised from their bf16 shadows once per step, activations by wj_quantize_mxfp8 in front of each GEMM.  The backward
         # is unchanged: it differentiates the bf16 graph (straight-through), with the saved bf16 activations and bf16 weights.
         self.fp8 = _os.environ.get("WJ_FP8", "0") == "1"
+        self._check_fp8()
         self._w8: Dict[int, Tuple[torch.Tensor, torch.Tensor, int, int]] = {}     # bf16 weight pointer -> (q, scales, N, K)
         self._a8: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}               # per stack: activation scratch (q, scales)
         self.side = self._pick_side_stream() if self.use_side else torch.cuda.Stream(device=self.dev)
@@ -509,8 +512,13 @@ class JepaEngine:
             return [(0, 0, self.N * self.S)]
         return [(c, c * self.N, self.N) for c in range(self.S)]
 
+    def _check_fp8(self) -> None:
+        if self.fp8 and (self.cfg.norm_first_enc or self.cfg.norm_first_dec):
+            raise RuntimeError("fp8 mode (WJ_FP8=1 / engine.fp8) covers post-norm stacks only: a norm_first=True stack runs in bf16")
+
     def _fp8_weights(self) -> None:
         """(Re-)quantise the forward weights of the transformer stacks from their bf16 shadows (once per step in fp8 mode)."""
+        self._check_fp8()
         c = self.cfg
         if not self._w8:
             for layers, d in ((self.enc_layers, c.d_enc), (self.tea_layers, c.d_enc), (self.dec_layers, c.d_dec)):
@@ -701,6 +709,9 @@ class JepaEngine:
         self.dec_out_b = _empty(Md, c.d_dec, dtype=bf, device=dev)
         self.dec_fm = _empty(Md, dtype=f32, device=dev)
         self.dec_fr = _empty(Md, dtype=f32, device=dev)
+        # pre-norm stacks: the stream that enters the stack's final norm (its backward needs it; post-norm reads the last layer's x2)
+        self.enc_sf = _empty(Me, c.d_enc, dtype=f32, device=dev) if c.norm_first_enc else None
+        self.dec_sf = _empty(Md, c.d_dec, dtype=f32, device=dev) if c.norm_first_dec else None
         self.preds = _empty(Md, c.d_enc, dtype=bf, device=dev)
         self.targets = _empty(M, c.d_enc, dtype=f32, device=dev)
         # teacher: outputs of the last top_k layers (fp32) and their per-clip (sum, sum of squares)
@@ -802,6 +813,43 @@ class JepaEngine:
                           mean=a.m2, rstd=a.r2, group_stats=x2_stats, group_rows=self.T if x2_stats is not None else 0,
                           workgroups=lean if x2_stats is None else 0, **f8_out)
         return f8 and sub is None              # the small fp8 buffer now holds x2 for the next layer of this stack
+
+    def _layer_fwd_pre(self, w: _Layer, a: _Acts, x_in, r_in, M: int, D: int, H: int, B: int, mask: Optional[torch.Tensor],
+                       seq: Optional[Tuple[torch.Tensor, int]] = None, save: bool = True, s_out: Optional[torch.Tensor] = None,
+                       s_stats: Optional[torch.Tensor] = None, sub: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None,
+                       stack: str = "enc"):
+        """Pre-norm layer (norm_first=True): s1 = s0 + out_proj(attn(in_proj(LN1(s0)))); s2 = s1 + linear2(gelu(linear1(LN2(s1)))).
+        The residual add of a branch is fused into the NEXT norm (wj_layernorm_pre_fwd), so the layer takes its input as the pair
+        (x_in, r_in) -- s0 = x_in + r_in, r_in = the previous layer's linear2 output, None for the first layer of a stack -- and returns
+        its output as the pair (s1, linear2 output): the next layer's norm1, or the stack's final norm, adds them.
+        Saved in `a`: x1 = s0 (when r_in is None, s0 is x_in itself and nothing is stored), x1b = LN1(s0), x2 = s1, x2b = LN2(s1).
+        s_out / s_stats (teacher): s0 -- the previous layer's output -- goes to its own buffer, with its per-clip (sum, sum of squares).
+        seq, save, sub: as _layer_fwd."""
+        eps = self.cfg.ln_eps
+        s0 = x_in if (r_in is None and s_out is None) else (a.x1 if s_out is None else s_out)
+        ops.layernorm_pre_fwd(x_in, w.g1, w.be1, M=M, D=D, eps=eps, r=r_in, s_f32=None if s0 is x_in else s0, y_bf16=a.x1b,
+                              mean=a.m1 if save else None, rstd=a.r1 if save else None, group_stats=s_stats,
+                              group_rows=self.T if s_stats is not None else 0)
+        self._linear_fwd(stack, a.x1b, w.wqkv, a.qkv, M=M, N=3 * D, K=D, bias=w.bqkv)
+        if seq is not None:
+            ops.attn_fwd(a.qkv, a.o, B=B, T=seq[1], H=H, hd=D // H, seq_off=seq[0], lse=a.lse if save else None)
+        else:
+            ops.attn_fwd(a.qkv, a.o, B=B, T=self.T, H=H, hd=D // H, key_mask=mask, lse=a.lse if save else None)
+        o_in = a.o
+        if sub is not None:
+            rows, _, M = sub                                   # M: the rows that go on
+            ops.mask_gather_rows(a.o, rows, self.tail_o, n_rows=M, D=D, elem_bytes=2)
+            ops.mask_gather_rows(s0, rows, self.tail_x, n_rows=M, D=D, elem_bytes=4)
+            o_in, s0 = self.tail_o, self.tail_x
+        self._linear_fwd(stack, o_in, w.wo, a.p, M=M, N=D, K=D, bias=w.bo)
+        ops.layernorm_pre_fwd(s0, w.g2, w.be2, M=M, D=D, eps=eps, r=a.p, s_f32=a.x2, y_bf16=a.x2b, mean=a.m2 if save else None,
+                              rstd=a.r2 if save else None)
+        if save:
+            self._linear_fwd(stack, a.x2b, w.w1, a.h, M=M, N=4 * D, K=D, bias=w.b1, epilogue=ops.EPI_BIAS_GELU2, C2=a.g)
+        else:
+            self._linear_fwd(stack, a.x2b, w.w1, a.g, M=M, N=4 * D, K=D, bias=w.b1, epilogue=ops.EPI_BIAS_GELU)
+        self._linear_fwd(stack, a.g, w.w2, a.f, M=M, N=D, K=4 * D, bias=w.b2)
+        return a.x2, a.f
 
     def _gemm8(self, q, sc, w_ptr: int, out, *, M: int, N: int, K: int, bias, epilogue: int = ops.EPI_BF16, C2=None, **extra) -> None:
         w8 = self._w8[w_ptr]
@@ -1064,6 +1112,95 @@ class JepaEngine:
         self._dgrad(dqkv, w, "wqkv", dxb, M=Mall, N=D, K=3 * D)
         return ds_all, dxb, flush
 
+    def _ln_pre_bwd(self, dy, s, gamma, mean, rstd, *, M: int, D: int, dgamma=None, dbeta=None, dbias=None, **kw) -> None:
+        """wj_layernorm_pre_bwd with the fold forms of _ln_bwd / _ln_bwd_direct: partial rows folded later with the neighbours', or at
+        once (deterministic mode: always through partial rows and an ordered fold, never the kernel's own atomics)."""
+        if not (dgamma or dbeta or dbias):
+            ops.layernorm_pre_bwd(dy, s, gamma, mean, rstd, M=M, D=D, **kw)
+        elif self.defer_folds and 3 * D <= 2304:
+            ws = self._fold_slot()
+            ops.layernorm_pre_bwd(dy, s, gamma, mean, rstd, M=M, D=D, workspace=ws, **kw)
+            self._folds.append((ws, 3 * D, ops.ln_pre_bwd_partial_rows(M, D), 3 * D, dgamma, dbeta, dbias, D))
+        elif self.deterministic:
+            ops.layernorm_pre_bwd(dy, s, gamma, mean, rstd, M=M, D=D, workspace=self.red_ws, **kw)
+            self._fold_now(self.red_ws, 3 * D, ops.ln_pre_bwd_partial_rows(M, D), 3 * D, dgamma, dbeta, dbias, D)
+        else:
+            ops.layernorm_pre_bwd(dy, s, gamma, mean, rstd, M=M, D=D, dgamma=dgamma, dbeta=dbeta, dbias=dbias, workspace=self.red_ws, **kw)
+
+    def _layer_bwd_pre(self, w: _Layer, a: _Acts, s0: torch.Tensor, below: Optional[_Layer], dx_out: torch.Tensor, M: int, D: int, H: int,
+                       B: int, mask: Optional[torch.Tensor], bw: dict, parity: int, seq: Optional[Tuple[torch.Tensor, int]] = None,
+                       sub: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None, flush: bool = True):
+        """Backward of _layer_fwd_pre.  On entry bw["ds"] holds d(s2) (fp32) and bw["dsb2"][parity] its bf16 rounding -- both written by
+        the backward of the norm one half-layer up (the layer above's norm1, or the stack's final norm), which also gave linear2.bias its
+        gradient.  On exit the same holds for the layer `below` (slot parity - 1); below = None (the first layer of the stack): d(s0)
+        goes to dx_out (fp32) for the consumers below the stack.  s0: the stream the layer read (a.x1, or the stack's input for the
+        first layer).  Every GEMM, attention and weight-gradient call is _layer_bwd's; returns (d(s0) buffer, flushed)."""
+        ds, dx1, do = bw["ds"], bw["dx1"], bw["do"]
+        dsb2, dsb1, dh, dqkv = bw["dsb2"][parity], bw["dsb1"][parity], bw["dh"][parity], bw["dqkv"][parity]
+        if self.use_side and bw["used"][parity]:
+            torch.cuda.current_stream().wait_event(bw["done"][parity])   # side stream finished reading this parity's buffers
+        Mall, o_in = M, a.o
+        if sub is not None:              # ds holds the sub-rows only; everything up to the attention works on them
+            M = sub[2]
+            o_in = self.tail_o
+        dgb, dxb = bw["dgb"], bw["dxb"]
+        self._dgrad(dsb2, w, "w2", dh, M=M, N=4 * D, K=D, epilogue=ops.EPI_MUL_GELU_GRAD, aux=a.h,
+                    colsum=w.gb1)        # linear1.bias gradient = column sums of dh, fused into the producing epilogue
+        bw["pending"] += [(dsb2, a.g, w.gw2, D, 4 * D, M), (dh, a.x2b, w.gw1, 4 * D, D, M)]
+        self._dgrad(dh, w, "w1", dgb, M=M, N=D, K=4 * D)
+        # norm2: d(s1) = d(s2) + LN2'(d LN2(s1)), in place; its bf16 rounding is out_proj's dY, its column sums out_proj.bias's gradient
+        self._ln_pre_bwd(dgb, a.x2, w.g2, a.m2, a.r2, M=M, D=D, dres=ds, dy_is_bf16=True, ds_f32=ds, ds_bf16=dsb1,
+                         dgamma=w.gg2, dbeta=w.gbe2, dbias=w.gbo)
+        ds_all = ds
+        if sub is None:
+            self._dgrad(dsb1, w, "wo", do, M=M, N=D, K=D)
+        else:                             # back to all rows: zero gradient where no output was used
+            self._dgrad(dsb1, w, "wo", self.tail_do, M=M, N=D, K=D)
+            ops.unmask_rows_f32(self.tail_do, sub[1], do, M=Mall, D=D, dst_is_bf16=True)
+            ops.unmask_rows_f32(ds, sub[1], dx1, M=Mall, D=D, src_is_f32=True)       # dx1 is free again: residual gradient
+            ds_all = dx1
+        if seq is not None:
+            self._attn_bwd(a.qkv, a.o, do, a.lse, dqkv, B=B, T=seq[1], H=H, hd=D // H, seq_off=seq[0], dbias=w.gbqkv)
+        else:
+            self._attn_bwd(a.qkv, a.o, do, a.lse, dqkv, B=B, T=self.T, H=H, hd=D // H, key_mask=mask, dbias=w.gbqkv)
+        bw["pending"] += [(dsb1, o_in, w.gwo, D, D, M), (dqkv, a.x1b, w.gwqkv, 3 * D, D, Mall)]
+        bw["pending_slots"].append(parity)
+        if flush:
+            probs, slots = bw["pending"], bw["pending_slots"]
+            bw["pending"], bw["pending_slots"] = [], []
+
+            def wgrads():
+                for i in range(0, len(probs), 8):
+                    if self.deterministic:
+                        ops.wgrad_grouped(probs[i:i + 8], workspace=self._det_ws(), deterministic=True)
+                    else:
+                        ops.wgrad_grouped(probs[i:i + 8])
+                if self.use_side:
+                    for sl in slots:
+                        bw["done"][sl].record(self.side)
+                        bw["used"][sl] = True
+            self._on_side(wgrads)
+        self._dgrad(dqkv, w, "wqkv", dxb, M=Mall, N=D, K=3 * D)
+        # norm1: d(s0) = d(s1) + LN1'(d LN1(s0)).  Above a layer it is that layer's d(s2): fp32 in bw["ds"], bf16 (linear2's dY) in the
+        # layer's own slot, column sums = its linear2.bias gradient -- every gradient of THIS layer is out when the call returns
+        if below is None:
+            self._ln_pre_bwd(dxb, s0, w.g1, a.m1, a.r1, M=Mall, D=D, dres=ds_all, dy_is_bf16=True, ds_f32=dx_out,
+                             dgamma=w.gg1, dbeta=w.gbe1)
+            return dx_out, flush
+        pb = (parity - 1) % bw["nbuf"]
+        if self.use_side and bw["used"][pb]:
+            torch.cuda.current_stream().wait_event(bw["done"][pb])       # (slot pb's last readers went out at least a layer ago)
+        self._ln_pre_bwd(dxb, s0, w.g1, a.m1, a.r1, M=Mall, D=D, dres=ds_all, dy_is_bf16=True, ds_f32=ds, ds_bf16=bw["dsb2"][pb],
+                         dgamma=w.gg1, dbeta=w.gbe1, dbias=below.gb2)
+        return ds, flush
+
+    def _stack_bwd_top_pre(self, dy, sf, norm: str, fm, fr, top: _Layer, bw: dict, parity: int, M: int, D: int) -> None:
+        """Backward of a pre-norm stack's final norm (dy: fp32 gradient of its output; nothing bypasses it): d(stream) for the top
+        layer -- fp32 in bw["ds"], bf16 in its slot -- and that layer's linear2.bias gradient."""
+        f = self.flat
+        self._ln_pre_bwd(dy, sf, f.ptr32(norm + ".weight"), fm, fr, M=M, D=D, ds_f32=bw["ds"], ds_bf16=bw["dsb2"][parity],
+                         dgamma=f.gptr(norm + ".weight"), dbeta=f.gptr(norm + ".bias"), dbias=top.gb2)
+
     # ------------------------------------------------------------------------------------------------ front-end
     def _frontend(self, audio: torch.Tensor) -> None:
         """audio bf16 [N, C_in, L] -> lf (fp32) / lf_b (bf16) [N*T, d_enc]   (reference jepa.py:391-396)"""
@@ -1151,7 +1288,9 @@ class JepaEngine:
             # and opened a 2-ms gap under rocprofv3, whose per-launch overhead makes the host the slower side.)
             self._conv_rows(plan)
         n_ctx = plan.n_ctx
-        if self.ragged_step:
+        if c.norm_first_enc:
+            self._student_fwd_pre(plan)
+        elif self.ragged_step:
             # student encoder on the context rows only, packed per clip (non-context rows are dropped at jepa.py:399 and,
             # being key-masked, never influence a context row)
             Me, eseq = n_ctx, (plan.enc_off, max(plan.max_enc, 1))
@@ -1188,22 +1327,48 @@ class JepaEngine:
                                       out_f32=self.dec_in, out_bf16=self.dec_in_b)
         x, xb = self.dec_in, self.dec_in_b
         self.tail = (plan.tgt_rows, plan.tgt_inv, plan.n_tgt) if (self.ragged_step and self.trim_tail and plan.n_tgt > 0) else None
-        Mo = Md                          # rows that leave the predictor
-        xq = False
-        for i, (w, a) in enumerate(zip(self.dec_layers, self.dec_acts)):
-            last = i == c.l_dec - 1
-            xq = self._layer_fwd(w, a, x, xb, Md, Dd, c.h_dec, N * G, plan.vis_u8, dseq, sub=self.tail if last else None, stack="dec",
-                                 xq_ready=xq)
-            x, xb = a.x2, a.x2b
-        if self.tail is not None:
-            Mo = plan.n_tgt
-        ops.layernorm_fwd(x, f.ptr32("decoder.norm.weight"), f.ptr32("decoder.norm.bias"), M=Mo, D=Dd, eps=c.norm_eps,
-                          y_bf16=self.dec_out_b, mean=self.dec_fm, rstd=self.dec_fr,
-                          workgroups=self.ln_lean_wgs if (self._lean_now and "dec" in self.ln_lean) else 0)
+        Mo = plan.n_tgt if self.tail is not None else Md      # rows that leave the predictor
+        if c.norm_first_dec:
+            r = None
+            for i, (w, a) in enumerate(zip(self.dec_layers, self.dec_acts)):
+                x, r = self._layer_fwd_pre(w, a, x, r, Md, Dd, c.h_dec, N * G, plan.vis_u8, dseq,
+                                           sub=self.tail if i == c.l_dec - 1 else None, stack="dec")
+            # the final norm also performs the last residual add; the stream it normalises is kept for its backward
+            ops.layernorm_pre_fwd(x, f.ptr32("decoder.norm.weight"), f.ptr32("decoder.norm.bias"), M=Mo, D=Dd, eps=c.norm_eps, r=r,
+                                  s_f32=self.dec_sf, y_bf16=self.dec_out_b, mean=self.dec_fm, rstd=self.dec_fr)
+        else:
+            xq = False
+            for i, (w, a) in enumerate(zip(self.dec_layers, self.dec_acts)):
+                last = i == c.l_dec - 1
+                xq = self._layer_fwd(w, a, x, xb, Md, Dd, c.h_dec, N * G, plan.vis_u8, dseq, sub=self.tail if last else None, stack="dec",
+                                     xq_ready=xq)
+                x, xb = a.x2, a.x2b
+            ops.layernorm_fwd(x, f.ptr32("decoder.norm.weight"), f.ptr32("decoder.norm.bias"), M=Mo, D=Dd, eps=c.norm_eps,
+                              y_bf16=self.dec_out_b, mean=self.dec_fm, rstd=self.dec_fr,
+                              workgroups=self.ln_lean_wgs if (self._lean_now and "dec" in self.ln_lean) else 0)
         ops.gemm(self.dec_out_b, f.ptr16("decoder_to_encoder_mapper.weight"), self.preds, M=Mo, N=De, K=Dd, lda=Dd, ldb=Dd,
                  ldc=De, bias=f.ptr32("decoder_to_encoder_mapper.bias"))
         self._join_side()               # teacher targets (side stream) are needed by the loss
         self._mse(None, None)
+
+    def _student_fwd_pre(self, plan: MaskPlan) -> None:
+        """Pre-norm student: the context rows packed per clip (ragged step), or every token with the keys restricted to the context and
+        the boolean-mask gather behind the final norm -> self.ctx_in.  The first norm1 makes the bf16 GEMM operand itself, so only the
+        fp32 rows are gathered."""
+        c, f, N, De = self.cfg, self.flat, self.N, self.cfg.d_enc
+        if self.ragged_step:
+            Me, eseq, mask, x = plan.n_ctx, (plan.enc_off, max(plan.max_enc, 1)), None, self.enc_in
+            ops.mask_gather_rows(self.lf, plan.keep, self.enc_in, n_rows=plan.n_ctx, D=De, elem_bytes=4)
+        else:
+            Me, eseq, mask, x = self.M, None, plan.ctx_u8, self.lf
+        r = None
+        for w, a in zip(self.enc_layers, self.enc_acts):
+            x, r = self._layer_fwd_pre(w, a, x, r, Me, De, c.h_enc, N, mask, eseq)
+        ops.layernorm_pre_fwd(x, f.ptr32("encoder.norm.weight"), f.ptr32("encoder.norm.bias"), M=Me, D=De, eps=c.norm_eps, r=r,
+                              s_f32=self.enc_sf, y_bf16=self.ctx_in if self.ragged_step else self.enc_out_b, mean=self.enc_fm,
+                              rstd=self.enc_fr)
+        if not self.ragged_step:
+            ops.mask_gather_rows(self.enc_out_b, plan.keep, self.ctx_in, n_rows=plan.n_ctx, D=De, elem_bytes=2)
 
     def _mse(self, dpreds, gscale_ptr) -> None:
         c, plan = self.cfg, self.plan
@@ -1230,7 +1395,39 @@ class JepaEngine:
         ops.unmask_rows_f32(self.preds, inv, out, M=N * G * T, D=De, src_is_f32=False, dst_is_bf16=True)
         return out.view(N * G, T, De)
 
+    def _teacher_targets_pre(self) -> None:
+        """Pre-norm teacher.  A layer's output is the stream s = x + branch, which exists only once the NEXT norm1 has added the
+        branch (the last layer's: a plain add, the teacher has no final norm): that kernel writes a kept output to its own buffer,
+        with the per-clip sums over s that wj_instnorm_mean needs."""
+        c, N, M, De = self.cfg, self.N, self.M, self.cfg.d_enc
+        a = self.scratch
+        x, r = self.lf, None
+        fused = 1 < c.top_k <= 8
+        kept, nl = 0, len(self.tea_layers)
+        for i in range(nl + 1):                    # step i materialises layer i - 1's output (i = nl: the stack's)
+            keep = i > 0 and c.l_enc - (i - 1) <= c.top_k
+            dest = self.tea_keep[kept] if (keep and fused) else None
+            stats = self.tea_stats[kept] if dest is not None else None
+            if i < nl:
+                x_in = x
+                x, r = self._layer_fwd_pre(self.tea_layers[i], a, x, r, M, De, c.h_enc, N, None, save=False, s_out=dest, s_stats=stats,
+                                           stack="tea")
+                s = dest if dest is not None else (x_in if i == 0 else a.x1)
+            else:
+                w = self.tea_layers[-1]            # (gamma / beta are not read: no normalised output is asked for)
+                s = dest if dest is not None else (self.targets if c.top_k <= 1 else a.x1)
+                ops.layernorm_pre_fwd(x, w.g1, w.be1, M=M, D=De, eps=c.ln_eps, r=r, s_f32=s, group_stats=stats,
+                                      group_rows=self.T if stats is not None else 0)
+            if keep and not fused and c.top_k > 1:   # mean over the layers actually kept: min(top_k, layers) (reference jepa.py:249-252)
+                ops.instnorm_accumulate(s, self.targets, B=N, TD=self.T * De, accumulate=kept > 0, scale=1.0 / min(c.top_k, c.l_enc))
+            kept += int(keep)
+        if fused:
+            ops.instnorm_mean(self.tea_keep[:kept], self.tea_stats, self.targets, B=N, TD=self.T * De)
+
     def _teacher_targets(self) -> None:
+        if self.cfg.norm_first_enc:
+            self._teacher_targets_pre()
+            return
         c, N, M, De = self.cfg, self.N, self.M, self.cfg.d_enc
         a = self.scratch
         x, xb = self.lf, self.lf_b
@@ -1299,13 +1496,21 @@ class JepaEngine:
         ops.gemm(self.dpreds, f.ptr16("decoder_to_encoder_mapper.weight"), bw["dx1"], M=Mo, N=Dd, K=De, lda=De, ldb=Dd, ldc=Dd,
                  b_trans=1, epilogue=ops.EPI_ADD_F32)
         last = self.dec_acts[-1]
-        self._ln_bwd_direct(bw["dx1"], last.x2, f.ptr32("decoder.norm.weight"), self.dec_fm, self.dec_fr, M=Mo, D=Dd, ds_f32=bw["dy"],
-                            dgamma=f.gptr("decoder.norm.weight"), dbeta=f.gptr("decoder.norm.bias"), workspace=self.red_ws)
-        dy, dyb = bw["dy"], None
-        for i in range(c.l_dec - 1, -1, -1):
-            x_in, xb_in = (self.dec_in, self.dec_in_b) if i == 0 else (self.dec_acts[i - 1].x2, self.dec_acts[i - 1].x2b)
-            dy, dyb, _ = self._layer_bwd(self.dec_layers[i], self.dec_acts[i], x_in, xb_in, dy, dyb, bw["dy"], Md, Dd, c.h_dec, N * G, plan.vis_u8,
-                                         bw, i % bw["nbuf"], dseq, sub=self.tail if (rag and i == c.l_dec - 1) else None, bottom=i == 0)
+        if c.norm_first_dec:
+            self._stack_bwd_top_pre(bw["dx1"], self.dec_sf, "decoder.norm", self.dec_fm, self.dec_fr, self.dec_layers[-1], bw,
+                                    (c.l_dec - 1) % bw["nbuf"], Mo, Dd)
+            for i in range(c.l_dec - 1, -1, -1):
+                dy, _ = self._layer_bwd_pre(self.dec_layers[i], self.dec_acts[i], self.dec_in if i == 0 else self.dec_acts[i].x1,
+                                            self.dec_layers[i - 1] if i > 0 else None, bw["dy"], Md, Dd, c.h_dec, N * G, plan.vis_u8, bw,
+                                            i % bw["nbuf"], dseq, sub=self.tail if (rag and i == c.l_dec - 1) else None)
+        else:
+            self._ln_bwd_direct(bw["dx1"], last.x2, f.ptr32("decoder.norm.weight"), self.dec_fm, self.dec_fr, M=Mo, D=Dd, ds_f32=bw["dy"],
+                                dgamma=f.gptr("decoder.norm.weight"), dbeta=f.gptr("decoder.norm.bias"), workspace=self.red_ws)
+            dy, dyb = bw["dy"], None
+            for i in range(c.l_dec - 1, -1, -1):
+                x_in, xb_in = (self.dec_in, self.dec_in_b) if i == 0 else (self.dec_acts[i - 1].x2, self.dec_acts[i - 1].x2b)
+                dy, dyb, _ = self._layer_bwd(self.dec_layers[i], self.dec_acts[i], x_in, xb_in, dy, dyb, bw["dy"], Md, Dd, c.h_dec, N * G, plan.vis_u8,
+                                             bw, i % bw["nbuf"], dseq, sub=self.tail if (rag and i == c.l_dec - 1) else None, bottom=i == 0)
         n_ctx = plan.n_ctx
         # the mask-token gradient leaves the kernel as one partial row per workgroup, folded with the other deferred folds (round 4:
         # 384 global float atomics per workgroup into the same 384 addresses)
@@ -1337,18 +1542,27 @@ class JepaEngine:
         else:
             ops.unmask_rows_f32(self.d_ctx_in, plan.inv, bw["dx1"], M=M, D=De)
         last = self.enc_acts[-1]
-        self._ln_bwd_direct(bw["dx1"], last.x2, f.ptr32("encoder.norm.weight"), self.enc_fm, self.enc_fr, M=Me, D=De, ds_f32=bw["dy"],
-                            dgamma=f.gptr("encoder.norm.weight"), dbeta=f.gptr("encoder.norm.bias"), workspace=self.red_ws)
+        if c.norm_first_enc:
+            self._stack_bwd_top_pre(bw["dx1"], self.enc_sf, "encoder.norm", self.enc_fm, self.enc_fr, self.enc_layers[-1], bw,
+                                    (c.l_enc - 1) % bw["nbuf"], Me, De)
+        else:
+            self._ln_bwd_direct(bw["dx1"], last.x2, f.ptr32("encoder.norm.weight"), self.enc_fm, self.enc_fr, M=Me, D=De, ds_f32=bw["dy"],
+                                dgamma=f.gptr("encoder.norm.weight"), dbeta=f.gptr("encoder.norm.bias"), workspace=self.red_ws)
         dy, dyb = bw["dy"], None
         enc_ready = set()
         for i in range(c.l_enc - 1, -1, -1):
             first = (self.enc_in, self.enc_in_b) if rag else (self.lf, self.lf_b)
-            x_in, xb_in = first if i == 0 else (self.enc_acts[i - 1].x2, self.enc_acts[i - 1].x2b)
+            flush_i = (c.l_enc - 1 - i) % bw["group"] == bw["group"] - 1 or i == 0
             # the weight gradients of two layers share a grouped launch: a layer's section of the gradient buffer is final (and its
             # all-reduce bucket may go) once the launch that carries it has been queued
-            dy, dyb, done = self._layer_bwd(self.enc_layers[i], self.enc_acts[i], x_in, xb_in, dy, dyb, bw["dy"], Me, De, c.h_enc, N, plan.ctx_u8,
-                                            bw, i % bw["nbuf"], eseq, flush=(c.l_enc - 1 - i) % bw["group"] == bw["group"] - 1 or i == 0,
-                                            bottom=i == 0)
+            if c.norm_first_enc:
+                dy, done = self._layer_bwd_pre(self.enc_layers[i], self.enc_acts[i], first[0] if i == 0 else self.enc_acts[i].x1,
+                                               self.enc_layers[i - 1] if i > 0 else None, bw["dy"], Me, De, c.h_enc, N, plan.ctx_u8, bw,
+                                               i % bw["nbuf"], eseq, flush=flush_i)
+            else:
+                x_in, xb_in = first if i == 0 else (self.enc_acts[i - 1].x2, self.enc_acts[i - 1].x2b)
+                dy, dyb, done = self._layer_bwd(self.enc_layers[i], self.enc_acts[i], x_in, xb_in, dy, dyb, bw["dy"], Me, De, c.h_enc, N, plan.ctx_u8,
+                                                bw, i % bw["nbuf"], eseq, flush=flush_i, bottom=i == 0)
             if done:
                 for j in range(min(c.l_enc - 1, i + bw["group"] - 1), i - 1, -1):
                     if j not in enc_ready:
@@ -1548,6 +1762,13 @@ class JepaEngine:
         self.wait_optimizer()
         self._frontend(audio)
         a = self.scratch
+        if c.norm_first_enc:
+            x, r = self.lf, None
+            for w in self.enc_layers:
+                x, r = self._layer_fwd_pre(w, a, x, r, self.M, c.d_enc, c.h_enc, N, key_mask_u8, save=False)
+            ops.layernorm_pre_fwd(x, f.ptr32("encoder.norm.weight"), f.ptr32("encoder.norm.bias"), M=self.M, D=c.d_enc, eps=c.norm_eps,
+                                  r=r, y_f32=self.enc_out)
+            return self.enc_out.view(N, self.T, c.d_enc)
         x, xb = self.lf, self.lf_b
         xq = False
         for w in self.enc_layers:

@@ -59,18 +59,23 @@ class _PostNormLayer(nn.Module):
         self.nhead = nhead
 
 
+class _PreNormLayer(_PostNormLayer):
+    """The same parameters, names and initialisation; the engine runs x = x + branch(norm(x)) (nn.TransformerEncoderLayer norm_first=True)."""
+    norm_first = True
+
+
 class TransformerStack(nn.Module):
-    """`num_layers` deep copies of one post-norm layer + final LayerNorm (as nn.TransformerEncoder(layer, norm=...))."""
+    """`num_layers` deep copies of one layer (post-norm, or pre-norm with norm_first=True) + final LayerNorm (as
+    nn.TransformerEncoder(layer, norm=...)).  Both layouts have the same parameter names and shapes."""
 
     def __init__(self, layer_cfg: Dict[str, Any], num_layers: int):
         super().__init__()
-        if layer_cfg.get("norm_first", False):
-            raise NotImplementedError("the WavJEPA path is post-norm (norm_first=False)")
+        self.norm_first = bool(layer_cfg.get("norm_first", False))
         if layer_cfg.get("dropout", 0.0) != 0.0:
             raise NotImplementedError("dropout is 0 on the WavJEPA path")
         if int(layer_cfg["dim_feedforward"]) != 4 * int(layer_cfg["d_model"]):
             raise NotImplementedError("feed-forward width must be 4 * d_model")
-        first = _PostNormLayer(**layer_cfg)
+        first = (_PreNormLayer if self.norm_first else _PostNormLayer)(**layer_cfg)
         self.layers = nn.ModuleList([first] + [copy.deepcopy(first) for _ in range(num_layers - 1)])
         self.norm = nn.LayerNorm(layer_cfg["d_model"])
         self.d_model, self.nhead, self.num_layers = int(layer_cfg["d_model"]), int(layer_cfg["nhead"]), num_layers
@@ -308,6 +313,11 @@ class JEPA(_ModuleBase):
         c_feat = feature_extractor.embedding_dim
         self.post_extraction_mapper = nn.Linear(c_feat, self.encoder_embedding_dim) if c_feat != self.encoder_embedding_dim else None
         self.decoder = TransformerStack(dec_l, dec_c["num_layers"])
+        # recorded only when set: checkpoints of post-norm models keep the hyper-parameter set they always had
+        if self.encoder.norm_first:
+            self.hparams["norm_first_encoder"] = True
+        if self.decoder.norm_first:
+            self.hparams["norm_first_decoder"] = True
         self.decoder_to_encoder_mapper = nn.Linear(self.decoder_embedding_dim, self.encoder_embedding_dim, bias=True)
         self.encoder_to_decoder_mapper = nn.Linear(self.encoder_embedding_dim, self.decoder_embedding_dim)
         self.mask_token = nn.Parameter(torch.zeros(1, 1, self.decoder_embedding_dim))
@@ -416,7 +426,8 @@ class JEPA(_ModuleBase):
         cfg = EngineConfig(conv_spec=spec, in_channels=conv_in, streams=streams, conv_prefixes=prefixes, n_samples=self.target_length,
                            d_enc=self.encoder_embedding_dim, h_enc=self.n_encoder_heads, l_enc=self.encoder.num_layers,
                            d_dec=self.decoder_embedding_dim, h_dec=self.n_decoder_heads, l_dec=self.decoder.num_layers,
-                           top_k=int(self.hparams.average_top_k_layers), ln_eps=self.encoder.layer_norm_eps)
+                           top_k=int(self.hparams.average_top_k_layers), ln_eps=self.encoder.layer_norm_eps,
+                           norm_first_enc=self.encoder.norm_first, norm_first_dec=self.decoder.norm_first)
         self._engine = JepaEngine(cfg, self._flat, self.pos_encoding_encoder.data, self.pos_encoding_decoder.data)
         self._anchor = torch.zeros(1, device=self.device, requires_grad=True)
         self._student_bf16_fresh = False

@@ -110,7 +110,7 @@ def require_gpu() -> None:
 
 def workspace_bytes(fn: str, **dims) -> int:
     """Scratch bytes entry point `fn` needs for the given dimensions (fields of its argument struct), from the library."""
-    struct_name = {"wj_gemm_bf16": "wj_gemm_args", "wj_colsum_bf16": "wj_colsum_args", "wj_mask_scatter_fill_pos_bwd": "wj_scatter_fill_bwd_args", "wj_layernorm_bwd": "wj_ln_bwd_args", "wj_attn_bwd": "wj_attn_bwd_args", "wj_conv0_gn_gelu_fwd": "wj_conv0_fwd_args",
+    struct_name = {"wj_gemm_bf16": "wj_gemm_args", "wj_colsum_bf16": "wj_colsum_args", "wj_mask_scatter_fill_pos_bwd": "wj_scatter_fill_bwd_args", "wj_layernorm_bwd": "wj_ln_bwd_args", "wj_layernorm_pre_bwd": "wj_ln_pre_bwd_args", "wj_attn_bwd": "wj_attn_bwd_args", "wj_conv0_gn_gelu_fwd": "wj_conv0_fwd_args",
                    "wj_conv0_gn_gelu_bwd": "wj_conv0_bwd_args", "wj_masked_mse": "wj_mse_args", "wj_grad_sumsq": "wj_sumsq_args",
                    "wj_rir_convolve": "wj_rir_conv_args", "wj_snr_mix": "wj_snr_mix_args", "wj_mse_groups": "wj_mse_groups_args",
                    "wj_audio_prepare": "wj_audio_prepare_args", "wj_noise_prepare": "wj_noise_prepare_args"}[fn]
@@ -269,6 +269,29 @@ def layernorm_bwd(dy: Ptr, x: Ptr, gamma: Ptr, mean: Ptr, rstd: Ptr, *, M: int, 
 def ln_bwd_partial_rows(M: int, D: int) -> int:
     """Rows of partials layernorm_bwd leaves in its workspace ([rows][3][D]) for M token rows of width D."""
     return int(_abi.load().wj_ln_bwd_partial_rows(int(M), int(D)))
+
+
+def layernorm_pre_fwd(x: Ptr, gamma: Ptr, beta: Ptr, *, M: int, D: int, eps: float, r: Ptr = None, s_f32: Ptr = None, y_f32: Ptr = None,
+                      y_bf16: Ptr = None, mean: Ptr = None, rstd: Ptr = None, group_stats: Ptr = None, group_rows: int = 0,
+                      stream: Optional[int] = None) -> None:
+    """Pre-norm fusion: s = x (+ r) -> s_f32 (may be x itself), y = LN(s) -> y_bf16 / y_f32; group_stats are taken over s."""
+    _run("wj_layernorm_pre_fwd", "wj_ln_pre_fwd_args", stream, x=_p(x), r=_p(r), gamma=_p(gamma), beta=_p(beta), s_f32=_p(s_f32),
+         y_f32=_p(y_f32), y_bf16=_p(y_bf16), mean=_p(mean), rstd=_p(rstd), group_stats=_p(group_stats), M=M, D=D, group_rows=group_rows,
+         eps=eps)
+
+
+def layernorm_pre_bwd(dy: Ptr, s: Ptr, gamma: Ptr, mean: Ptr, rstd: Ptr, *, M: int, D: int, dres: Ptr = None, dy_is_bf16: bool = False,
+                      ds_f32: Ptr = None, ds_bf16: Ptr = None, dgamma: Ptr = None, dbeta: Ptr = None, dbias: Ptr = None,
+                      workspace: Ptr = None, stream: Optional[int] = None) -> None:
+    """ds = (dres) + LN-backward(dy) -> ds_f32 (may be dres itself) / ds_bf16; dbias = column sums of bf16(ds)."""
+    _run("wj_layernorm_pre_bwd", "wj_ln_pre_bwd_args", stream, dy=_p(dy), dres=_p(dres), s=_p(s), gamma=_p(gamma), mean=_p(mean),
+         rstd=_p(rstd), ds_f32=_p(ds_f32), ds_bf16=_p(ds_bf16), dgamma=_p(dgamma), dbeta=_p(dbeta), dbias=_p(dbias),
+         workspace=_p(workspace), M=M, D=D, dy_is_bf16=int(dy_is_bf16))
+
+
+def ln_pre_bwd_partial_rows(M: int, D: int) -> int:
+    """Rows of partials layernorm_pre_bwd leaves in its workspace ([rows][3][D]) for M token rows of width D."""
+    return int(_abi.load().wj_ln_pre_bwd_partial_rows(int(M), int(D)))
 
 
 def colsum_f32_group(items, stream: Optional[int] = None, deterministic: bool = False) -> None:
