@@ -41,7 +41,7 @@ class DenoiserEngine(JepaEngine):
 
     def forward_pair(self, audio: torch.Tensor, targets: torch.Tensor, alpha: float) -> None:
         """audio bf16 [2N, C, L] (clean clips first), targets fp32 [N, T, d_enc] -> self.dn_loss = (loss, loss_clean, loss_generated)."""
-        c, f = self.cfg, self.flat
+        c = self.cfg
         N2 = audio.shape[0]
         if N2 % 2 or targets.numel() != (N2 // 2) * self.T * c.d_enc:
             raise ValueError("denoiser step: 2N clips (N clean + N generated) and N x T x d_enc targets expected")
@@ -55,34 +55,19 @@ class DenoiserEngine(JepaEngine):
         self.set_wt_need(self.M, 0)
         self.dn_targets = targets.reshape(-1, c.d_enc).float().contiguous()
         self._frontend(audio)
-        x, xb = self.lf, self.lf_b
-        for w, a in zip(self.enc_layers, self.enc_acts):
-            self._layer_fwd(w, a, x, xb, self.M, c.d_enc, c.h_enc, N2, None)
-            x, xb = a.x2, a.x2b
-        ops.layernorm_fwd(x, f.ptr32("encoder.norm.weight"), f.ptr32("encoder.norm.bias"), M=self.M, D=c.d_enc, eps=c.norm_eps,
-                          y_f32=self.enc_out, mean=self.enc_fm, rstd=self.enc_fr)
+        self._stack_fwd("enc", self.lf, self.lf_b, self.M, N2, None, acts=self.enc_acts, y_f32=self.enc_out, mean=self.enc_fm, rstd=self.enc_fr)
         self.dn_n = (N2 // 2) * self.T * c.d_enc
         ops.mse_groups(self.enc_out, self.dn_targets, self.dn_w, self.dn_loss, self.dn_ws, n=self.dn_n, G=2)
 
     def backward_pair(self, gscale_ptr: int = 0) -> None:
-        c, f = self.cfg, self.flat
-        De, M, N2 = c.d_enc, self.M, self.N
-        f.g32.zero_()
+        self.flat.g32.zero_()
         if self.deterministic:
             self._det_ws()
         self.refresh_wt()
         bw = self.bw["enc"]
         ops.mse_groups(self.enc_out, self.dn_targets, self.dn_w, self.dn_loss, self.dn_ws, n=self.dn_n, G=2, dpreds=bw["dx1"],
                        gscale=gscale_ptr if gscale_ptr else None)
-        last = self.enc_acts[-1]
-        self._ln_bwd_direct(bw["dx1"], last.x2, f.ptr32("encoder.norm.weight"), self.enc_fm, self.enc_fr, M=M, D=De, ds_f32=bw["dy"],
-                            dgamma=f.gptr("encoder.norm.weight"), dbeta=f.gptr("encoder.norm.bias"), workspace=self.red_ws)
-        dy, dyb = bw["dy"], None
-        for i in range(c.l_enc - 1, -1, -1):
-            x_in, xb_in = (self.lf, self.lf_b) if i == 0 else (self.enc_acts[i - 1].x2, self.enc_acts[i - 1].x2b)
-            dy, dyb, _ = self._layer_bwd(self.enc_layers[i], self.enc_acts[i], x_in, xb_in, dy, dyb, bw["dy"], M, De, c.h_enc, N2, None, bw,
-                                         i % bw["nbuf"], None, flush=(c.l_enc - 1 - i) % bw["group"] == bw["group"] - 1 or i == 0,
-                                         bottom=i == 0)
+        dy = self._stack_bwd("enc", self.lf, self.lf_b, self.M, self.N, None)
         self._frontend_bwd(dy, False, None)
         self._flush_folds()
         self._join_side()

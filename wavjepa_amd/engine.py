@@ -752,6 +752,31 @@ class JepaEngine:
         self.d_fn = _empty(M, C, dtype=f32, device=dev)
 
     # ------------------------------------------------------------------------------------------------ building blocks
+    # ---- pieces of a layer that the post-norm and the pre-norm layout share
+    def _attn_fwd(self, a: _Acts, D: int, H: int, B: int, mask: Optional[torch.Tensor], seq: Optional[Tuple[torch.Tensor, int]],
+                  save: bool) -> None:
+        """a.o = attention(a.qkv): packed sequences (`seq`) or T tokens per sequence under a key mask; `save` keeps the softmax statistics."""
+        lse = a.lse if save else None
+        if seq is not None:
+            ops.attn_fwd(a.qkv, a.o, B=B, T=seq[1], H=H, hd=D // H, seq_off=seq[0], lse=lse)
+        else:
+            ops.attn_fwd(a.qkv, a.o, B=B, T=self.T, H=H, hd=D // H, key_mask=mask, lse=lse)
+
+    def _tail_gather(self, a: _Acts, x: torch.Tensor, sub: Tuple[torch.Tensor, torch.Tensor, int], D: int):
+        """The `sub` rows of the attention output and of the residual source x: (tail_o, tail_x, the number of rows that go on)."""
+        rows, _, M = sub
+        ops.mask_gather_rows(a.o, rows, self.tail_o, n_rows=M, D=D, elem_bytes=2)
+        ops.mask_gather_rows(x, rows, self.tail_x, n_rows=M, D=D, elem_bytes=4)
+        return self.tail_o, self.tail_x, M
+
+    def _mlp_fwd(self, stack: str, w: _Layer, a: _Acts, xb: torch.Tensor, M: int, D: int, save: bool) -> None:
+        """a.f = linear2(gelu(linear1(xb))) in bf16; `save` also keeps gelu'(linear1 output) in a.h for the backward."""
+        if save:
+            self._linear_fwd(stack, xb, w.w1, a.h, M=M, N=4 * D, K=D, bias=w.b1, epilogue=ops.EPI_BIAS_GELU2, C2=a.g)
+        else:
+            self._linear_fwd(stack, xb, w.w1, a.g, M=M, N=4 * D, K=D, bias=w.b1, epilogue=ops.EPI_BIAS_GELU)
+        self._linear_fwd(stack, a.g, w.w2, a.f, M=M, N=D, K=4 * D, bias=w.b2)
+
     def _layer_fwd(self, w: _Layer, a: _Acts, x_in: torch.Tensor, xb_in: torch.Tensor, M: int, D: int, H: int, B: int,
                    mask: Optional[torch.Tensor], seq: Optional[Tuple[torch.Tensor, int]] = None, save: bool = True,
                    x2_out: Optional[torch.Tensor] = None, x2_stats: Optional[torch.Tensor] = None,
@@ -776,16 +801,10 @@ class JepaEngine:
             if not xq_ready:
                 ops.quantize_mxfp8(xb_in, qs, ss, M=M, K=D, ldx=D, ldq=D, ld_scale=M)
             self._gemm8(qs, ss, w.wqkv, a.qkv, M=M, N=3 * D, K=D, bias=w.bqkv)
-        if seq is not None:
-            ops.attn_fwd(a.qkv, a.o, B=B, T=seq[1], H=H, hd=D // H, seq_off=seq[0], lse=a.lse if save else None)
-        else:
-            ops.attn_fwd(a.qkv, a.o, B=B, T=self.T, H=H, hd=D // H, key_mask=mask, lse=a.lse if save else None)
+        self._attn_fwd(a, D, H, B, mask, seq, save)
         o_in = a.o
         if sub is not None:
-            rows, _, M = sub                                   # M: the rows that go on
-            ops.mask_gather_rows(a.o, rows, self.tail_o, n_rows=M, D=D, elem_bytes=2)
-            ops.mask_gather_rows(x_in, rows, self.tail_x, n_rows=M, D=D, elem_bytes=4)
-            o_in, x_in = self.tail_o, self.tail_x
+            o_in, x_in, M = self._tail_gather(a, x_in, sub, D)
         f8_out = dict(y_fp8=qs, y_fp8_scales=ss, ld_fp8_scale=M) if f8 else {}
         if f8:
             ops.quantize_mxfp8(o_in, qs, ss, M=M, K=D, ldx=D, ldq=D, ld_scale=M)
@@ -802,11 +821,7 @@ class JepaEngine:
                 self._gemm8(qs, ss, w.w1, None, M=M, N=4 * D, K=D, bias=w.b1, epilogue=ops.EPI_BIAS_GELU, **gq)
             self._gemm8(qb, sb, w.w2, a.f, M=M, N=D, K=4 * D, bias=w.b2)
         else:
-            if save:
-                self._linear_fwd(stack, a.x1b, w.w1, a.h, M=M, N=4 * D, K=D, bias=w.b1, epilogue=ops.EPI_BIAS_GELU2, C2=a.g)
-            else:
-                self._linear_fwd(stack, a.x1b, w.w1, a.g, M=M, N=4 * D, K=D, bias=w.b1, epilogue=ops.EPI_BIAS_GELU)
-            self._linear_fwd(stack, a.g, w.w2, a.f, M=M, N=D, K=4 * D, bias=w.b2)
+            self._mlp_fwd(stack, w, a, a.x1b, M, D, save)
         # x2_out / x2_stats (teacher): the layer output goes to its own buffer and its per-clip (sum, sum of squares) is
         # accumulated on the way, so that the targets are ONE pass over the kept layers (wj_instnorm_mean)
         ops.layernorm_fwd(a.x1, w.g2, w.be2, M=M, D=D, eps=eps, r=a.f, y_f32=a.x2 if x2_out is None else x2_out, y_bf16=a.x2b,
@@ -831,24 +846,14 @@ class JepaEngine:
                               mean=a.m1 if save else None, rstd=a.r1 if save else None, group_stats=s_stats,
                               group_rows=self.T if s_stats is not None else 0)
         self._linear_fwd(stack, a.x1b, w.wqkv, a.qkv, M=M, N=3 * D, K=D, bias=w.bqkv)
-        if seq is not None:
-            ops.attn_fwd(a.qkv, a.o, B=B, T=seq[1], H=H, hd=D // H, seq_off=seq[0], lse=a.lse if save else None)
-        else:
-            ops.attn_fwd(a.qkv, a.o, B=B, T=self.T, H=H, hd=D // H, key_mask=mask, lse=a.lse if save else None)
+        self._attn_fwd(a, D, H, B, mask, seq, save)
         o_in = a.o
         if sub is not None:
-            rows, _, M = sub                                   # M: the rows that go on
-            ops.mask_gather_rows(a.o, rows, self.tail_o, n_rows=M, D=D, elem_bytes=2)
-            ops.mask_gather_rows(s0, rows, self.tail_x, n_rows=M, D=D, elem_bytes=4)
-            o_in, s0 = self.tail_o, self.tail_x
+            o_in, s0, M = self._tail_gather(a, s0, sub, D)
         self._linear_fwd(stack, o_in, w.wo, a.p, M=M, N=D, K=D, bias=w.bo)
         ops.layernorm_pre_fwd(s0, w.g2, w.be2, M=M, D=D, eps=eps, r=a.p, s_f32=a.x2, y_bf16=a.x2b, mean=a.m2 if save else None,
                               rstd=a.r2 if save else None)
-        if save:
-            self._linear_fwd(stack, a.x2b, w.w1, a.h, M=M, N=4 * D, K=D, bias=w.b1, epilogue=ops.EPI_BIAS_GELU2, C2=a.g)
-        else:
-            self._linear_fwd(stack, a.x2b, w.w1, a.g, M=M, N=4 * D, K=D, bias=w.b1, epilogue=ops.EPI_BIAS_GELU)
-        self._linear_fwd(stack, a.g, w.w2, a.f, M=M, N=D, K=4 * D, bias=w.b2)
+        self._mlp_fwd(stack, w, a, a.x2b, M, D, save)
         return a.x2, a.f
 
     def _gemm8(self, q, sc, w_ptr: int, out, *, M: int, N: int, K: int, bias, epilogue: int = ops.EPI_BF16, C2=None, **extra) -> None:
@@ -967,32 +972,62 @@ class JepaEngine:
             raise RuntimeError(f"deterministic mode: no ordered fold for {N} columns (wj_colsum_f32_group takes <= 2304)")
         ops.colsum_f32_group([(ws, ldx, rows, N, o0, o1, o2, n_each)], deterministic=True)
 
-    def _ln_bwd_direct(self, dy, x, gamma, mean, rstd, *, M: int, D: int, dgamma=None, dbeta=None, dbias=None, workspace=None, **kw) -> None:
-        """wj_layernorm_bwd that folds its parameter gradients at once.  Deterministic mode: always through the partial rows (no
-        gradient outputs, so the kernel has no atomics) and an ordered fold."""
-        if self.deterministic and (dgamma or dbeta or dbias):
-            ops.layernorm_bwd(dy, x, gamma, mean, rstd, M=M, D=D, workspace=self.red_ws, **kw)
-            self._fold_now(self.red_ws, 3 * D, ops.ln_bwd_partial_rows(M, D), 3 * D, dgamma, dbeta, dbias, D)
-        else:
-            ops.layernorm_bwd(dy, x, gamma, mean, rstd, M=M, D=D, dgamma=dgamma, dbeta=dbeta, dbias=dbias, workspace=workspace, **kw)
+    def _fold_form(self, N: int, wanted: bool, defer: bool = True, fits: bool = True):
+        """How the partial rows [rows][N] of a kernel's parameter gradients get folded into the gradient buffer -> (form, scratch):
+        "slot": the kernel leaves them in a slot of fold_ws, folded later with the neighbours' by one grouped launch (_flush_folds);
+        "now":  deterministic mode without a slot: the kernel leaves them in red_ws, folded in order at once;
+        "own":  the kernel reduces by itself (no scratch from here), or no gradient output was asked for (`wanted`).
+        defer=False: a producer that never waits for the grouped fold; fits: its partial rows fit a slot."""
+        if wanted and defer and self.defer_folds and N <= 2304 and fits:
+            return "slot", self._fold_slot()
+        if wanted and self.deterministic:
+            return "now", self.red_ws
+        return "own", None
 
-    def _ln_bwd(self, dy, x, gamma, mean, rstd, *, M: int, D: int, dgamma=None, dbeta=None, dbias=None, **kw) -> None:
-        """wj_layernorm_bwd; its dgamma / dbeta / dbias partials are folded later, together with the neighbours' (see _flush_folds)."""
-        if self.defer_folds and 3 * D <= 2304 and (dgamma or dbeta or dbias):
-            ws = self._fold_slot()
-            ops.layernorm_bwd(dy, x, gamma, mean, rstd, M=M, D=D, workspace=ws, **kw)
-            self._folds.append((ws, 3 * D, ops.ln_bwd_partial_rows(M, D), 3 * D, dgamma, dbeta, dbias, D))
+    def _fold(self, form: str, ws, N: int, rows: int, o0, o1, o2, n_each: int) -> None:
+        """queue ("slot") or perform ("now") the fold of the partial rows a kernel left in `ws`"""
+        if form == "slot":
+            self._folds.append((ws, N, rows, N, o0, o1, o2, n_each))
+        elif form == "now":
+            self._fold_now(ws, N, rows, N, o0, o1, o2, n_each)
+
+    def _ln_bwd(self, dy, x, gamma, mean, rstd, *, M: int, D: int, dgamma=None, dbeta=None, dbias=None, defer: bool = True,
+                workspace=None, **kw) -> None:
+        """wj_layernorm_bwd; its dgamma / dbeta / dbias partials are folded later, together with the neighbours' (see _flush_folds), or
+        in deterministic mode at once -- never by the kernel's own atomics then.  workspace: what an undeferred caller hands the
+        kernel's own reduction (a deferring one: red_ws)."""
+        form, ws = self._fold_form(3 * D, bool(dgamma or dbeta or dbias), defer)
+        if form == "own":
+            ops.layernorm_bwd(dy, x, gamma, mean, rstd, M=M, D=D, dgamma=dgamma, dbeta=dbeta, dbias=dbias,
+                              workspace=self.red_ws if defer else workspace, **kw)
         else:
-            self._ln_bwd_direct(dy, x, gamma, mean, rstd, M=M, D=D, dgamma=dgamma, dbeta=dbeta, dbias=dbias, workspace=self.red_ws, **kw)
+            ops.layernorm_bwd(dy, x, gamma, mean, rstd, M=M, D=D, workspace=ws, **kw)
+            self._fold(form, ws, 3 * D, ops.ln_bwd_partial_rows(M, D), dgamma, dbeta, dbias, D)
+
+    def _ln_bwd_direct(self, dy, x, gamma, mean, rstd, *, M: int, D: int, workspace=None, **kw) -> None:
+        """wj_layernorm_bwd that folds its parameter gradients at once (the norms outside the layers)."""
+        self._ln_bwd(dy, x, gamma, mean, rstd, M=M, D=D, defer=False, workspace=workspace, **kw)
+
+    def _ln_pre_bwd(self, dy, s, gamma, mean, rstd, *, M: int, D: int, dgamma=None, dbeta=None, dbias=None, **kw) -> None:
+        """wj_layernorm_pre_bwd with the fold forms of _ln_bwd."""
+        wanted = bool(dgamma or dbeta or dbias)
+        form, ws = self._fold_form(3 * D, wanted)
+        if form == "own":
+            ops.layernorm_pre_bwd(dy, s, gamma, mean, rstd, M=M, D=D, dgamma=dgamma, dbeta=dbeta, dbias=dbias,
+                                  workspace=self.red_ws if wanted else None, **kw)
+        else:
+            ops.layernorm_pre_bwd(dy, s, gamma, mean, rstd, M=M, D=D, workspace=ws, **kw)
+            self._fold(form, ws, 3 * D, ops.ln_pre_bwd_partial_rows(M, D), dgamma, dbeta, dbias, D)
 
     def _attn_bwd(self, qkv, out, dout, lse, dqkv, *, B: int, H: int, hd: int, dbias, **kw) -> None:
+        """wj_attn_bwd: the in_proj bias partials go to a slot, or the kernel folds them itself out of red_ws (in order when deterministic)."""
         D3 = 3 * H * hd
         if self.deterministic:
             kw = dict(kw, deterministic=True)
-        if self.defer_folds and D3 <= 2304 and dbias:
-            ws = self._fold_slot()
+        form, ws = self._fold_form(D3, bool(dbias))
+        if form == "slot":
             ops.attn_bwd(qkv, out, dout, lse, dqkv, B=B, H=H, hd=hd, dbias=dbias, dbias_ws=ws, defer_fold=True, **kw)
-            self._folds.append((ws, D3, B, D3, dbias, None, None, D3))
+            self._fold(form, ws, D3, B, dbias, None, None, D3)
         else:
             ops.attn_bwd(qkv, out, dout, lse, dqkv, B=B, H=H, hd=hd, dbias=dbias, dbias_ws=self.red_ws, **kw)
 
@@ -1044,6 +1079,64 @@ class JepaEngine:
             ev.record(self.side)
             torch.cuda.current_stream().wait_event(ev)
 
+    # ---- pieces of a layer's backward that the post-norm and the pre-norm layout share
+    def _slot_wait(self, bw: dict, slot: int) -> None:
+        if self.use_side and bw["used"][slot]:
+            torch.cuda.current_stream().wait_event(bw["done"][slot])   # side stream finished reading this slot's buffers
+
+    def _mlp_bwd(self, w: _Layer, a: _Acts, xb: torch.Tensor, bw: dict, parity: int, M: int, D: int) -> None:
+        """d(linear2 output) (bf16, bw["dsb2"][parity]) -> d(linear1 input) (bf16, bw["dgb"]); xb: the bf16 operand linear1 read.
+        The two weight gradients are queued (_wgrads)."""
+        dsb2, dh = bw["dsb2"][parity], bw["dh"][parity]
+        self._dgrad(dsb2, w, "w2", dh, M=M, N=4 * D, K=D, epilogue=ops.EPI_MUL_GELU_GRAD, aux=a.h,
+                    colsum=w.gb1)        # linear1.bias gradient = column sums of dh, fused into the producing epilogue
+        bw["pending"] += [(dsb2, a.g, w.gw2, D, 4 * D, M), (dh, xb, w.gw1, 4 * D, D, M)]
+        self._dgrad(dh, w, "w1", bw["dgb"], M=M, N=D, K=4 * D)
+
+    def _attn_block_bwd(self, w: _Layer, a: _Acts, xb: torch.Tensor, bw: dict, parity: int, M: int, D: int, H: int, B: int,
+                        mask: Optional[torch.Tensor], seq: Optional[Tuple[torch.Tensor, int]],
+                        sub: Optional[Tuple[torch.Tensor, torch.Tensor, int]]) -> torch.Tensor:
+        """d(out_proj output) (bf16, bw["dsb1"][parity]; with `sub`: on the sub-rows) -> d(qkv) over all M rows (bw["dqkv"][parity]);
+        xb: the bf16 operand in_proj read.  Returns the fp32 residual gradient over all M rows: bw["ds"], with `sub` scattered into
+        bw["dx1"].  The two weight gradients are queued (_wgrads)."""
+        ds, dx1, do, dsb1, dqkv = bw["ds"], bw["dx1"], bw["do"], bw["dsb1"][parity], bw["dqkv"][parity]
+        if sub is None:
+            Ms, o_in, ds_all = M, a.o, ds
+            self._dgrad(dsb1, w, "wo", do, M=M, N=D, K=D)
+        else:                             # back to all rows: zero gradient where no output was used
+            Ms, o_in, ds_all = sub[2], self.tail_o, dx1
+            self._dgrad(dsb1, w, "wo", self.tail_do, M=Ms, N=D, K=D)
+            ops.unmask_rows_f32(self.tail_do, sub[1], do, M=M, D=D, dst_is_bf16=True)
+            ops.unmask_rows_f32(ds, sub[1], dx1, M=M, D=D, src_is_f32=True)       # dx1 is free again: residual gradient
+        if seq is not None:
+            self._attn_bwd(a.qkv, a.o, do, a.lse, dqkv, B=B, T=seq[1], H=H, hd=D // H, seq_off=seq[0], dbias=w.gbqkv)
+        else:
+            self._attn_bwd(a.qkv, a.o, do, a.lse, dqkv, B=B, T=self.T, H=H, hd=D // H, key_mask=mask, dbias=w.gbqkv)
+        bw["pending"] += [(dsb1, o_in, w.gwo, D, D, Ms), (dqkv, xb, w.gwqkv, 3 * D, D, M)]
+        return ds_all
+
+    def _wgrads(self, bw: dict, parity: int, flush: bool) -> None:
+        """The four weight-gradient GEMMs of a layer only need (dY, X) and nothing downstream needs them before the optimiser: they are
+        queued, and with `flush` the queue goes out as grouped launches on the side stream while the main stream continues the dgrad
+        chain (`parity` = the layer's buffer slot; its `done` event tells the main stream when the slot may be written again)."""
+        bw["pending_slots"].append(parity)
+        if not flush:
+            return
+        probs, slots = bw["pending"], bw["pending_slots"]
+        bw["pending"], bw["pending_slots"] = [], []
+
+        def wgrads():
+            for i in range(0, len(probs), 8):
+                if self.deterministic:
+                    ops.wgrad_grouped(probs[i:i + 8], workspace=self._det_ws(), deterministic=True)
+                else:
+                    ops.wgrad_grouped(probs[i:i + 8])
+            if self.use_side:
+                for sl in slots:
+                    bw["done"][sl].record(self.side)
+                    bw["used"][sl] = True
+        self._on_side(wgrads)
+
     def _layer_bwd(self, w: _Layer, a: _Acts, x_in: torch.Tensor, xb_in: torch.Tensor, dy: torch.Tensor, dyb: Optional[torch.Tensor],
                    dx_out: torch.Tensor, M: int, D: int, H: int, B: int, mask: Optional[torch.Tensor], bw: dict, parity: int,
                    seq: Optional[Tuple[torch.Tensor, int]] = None,
@@ -1054,78 +1147,25 @@ class JepaEngine:
         LayerNorm backward that consumes the sum adds it to the fp32 residual gradient on its way in (`dy2`): 2 + 2 bytes per element
         instead of the 4 + 4 of a read-modify-write fp32 GEMM epilogue.  Only the `bottom` layer of a stack folds the two into one
         fp32 tensor (dx_out), for the consumers below the stack.
-        The four weight-gradient GEMMs only need (dY, X) and nothing downstream needs them before the optimiser: they are queued
-        and go out as one grouped launch on the side stream (with `flush`; `parity` = this layer's buffer slot) while the main
-        stream continues the dgrad chain.  Returns True when the queue was flushed (the queued layers' gradients are then final in
+        Returns flushed = True when the weight-gradient queue went out (_wgrads: the queued layers' gradients are then final in
         side-stream order)."""
-        ds, dx1, do = bw["ds"], bw["dx1"], bw["do"]
-        dsb2, dsb1, dh, dqkv = bw["dsb2"][parity], bw["dsb1"][parity], bw["dh"][parity], bw["dqkv"][parity]
-        if self.use_side and bw["used"][parity]:
-            torch.cuda.current_stream().wait_event(bw["done"][parity])   # side stream finished reading this parity's buffers
-        Mall, x_ln1, o_in = M, x_in, a.o
+        ds, dxb, dqkv = bw["ds"], bw["dxb"], bw["dqkv"][parity]
+        self._slot_wait(bw, parity)
+        Ms, x_ln1 = M, x_in
         if sub is not None:              # dy holds the sub-rows only; everything up to the attention works on them
-            M = sub[2]
-            x_ln1, o_in = self.tail_x, self.tail_o
-        dgb, dxb = bw["dgb"], bw["dxb"]
-        self._ln_bwd(dy, a.x1, w.g2, a.m2, a.r2, M=M, D=D, r=a.f, dy2=dyb, dy2_is_bf16=dyb is not None, ds_f32=ds, ds_bf16=dsb2,
+            Ms, x_ln1 = sub[2], self.tail_x
+        self._ln_bwd(dy, a.x1, w.g2, a.m2, a.r2, M=Ms, D=D, r=a.f, dy2=dyb, dy2_is_bf16=dyb is not None, ds_f32=ds, ds_bf16=bw["dsb2"][parity],
                      dgamma=w.gg2, dbeta=w.gbe2, dbias=w.gb2)
-        self._dgrad(dsb2, w, "w2", dh, M=M, N=4 * D, K=D, epilogue=ops.EPI_MUL_GELU_GRAD, aux=a.h,
-                    colsum=w.gb1)        # linear1.bias gradient = column sums of dh, fused into the producing epilogue
-
-        bw["pending"] += [(dsb2, a.g, w.gw2, D, 4 * D, M), (dh, a.x1b, w.gw1, 4 * D, D, M)]
-        self._dgrad(dh, w, "w1", dgb, M=M, N=D, K=4 * D)
-        self._ln_bwd(ds, x_ln1, w.g1, a.m1, a.r1, M=M, D=D, r=a.p, dy2=dgb, dy2_is_bf16=True, ds_f32=ds, ds_bf16=dsb1,
+        self._mlp_bwd(w, a, a.x1b, bw, parity, Ms, D)
+        self._ln_bwd(ds, x_ln1, w.g1, a.m1, a.r1, M=Ms, D=D, r=a.p, dy2=bw["dgb"], dy2_is_bf16=True, ds_f32=ds, ds_bf16=bw["dsb1"][parity],
                      dgamma=w.gg1, dbeta=w.gbe1, dbias=w.gbo)      # ds updated in place
-        ds_all = ds
-        if sub is None:
-            self._dgrad(dsb1, w, "wo", do, M=M, N=D, K=D)
-        else:                             # back to all rows: zero gradient where no output was used
-            self._dgrad(dsb1, w, "wo", self.tail_do, M=M, N=D, K=D)
-            ops.unmask_rows_f32(self.tail_do, sub[1], do, M=Mall, D=D, dst_is_bf16=True)
-            ops.unmask_rows_f32(ds, sub[1], dx1, M=Mall, D=D, src_is_f32=True)       # dx1 is free again: residual gradient
-            ds_all = dx1
-        if seq is not None:
-            self._attn_bwd(a.qkv, a.o, do, a.lse, dqkv, B=B, T=seq[1], H=H, hd=D // H, seq_off=seq[0], dbias=w.gbqkv)
-        else:
-            self._attn_bwd(a.qkv, a.o, do, a.lse, dqkv, B=B, T=self.T, H=H, hd=D // H, key_mask=mask, dbias=w.gbqkv)
-
-        bw["pending"] += [(dsb1, o_in, w.gwo, D, D, M), (dqkv, xb_in, w.gwqkv, 3 * D, D, Mall)]
-        bw["pending_slots"].append(parity)
-        if flush:
-            probs, slots = bw["pending"], bw["pending_slots"]
-            bw["pending"], bw["pending_slots"] = [], []
-
-            def wgrads():
-                for i in range(0, len(probs), 8):
-                    if self.deterministic:
-                        ops.wgrad_grouped(probs[i:i + 8], workspace=self._det_ws(), deterministic=True)
-                    else:
-                        ops.wgrad_grouped(probs[i:i + 8])
-                if self.use_side:
-                    for sl in slots:
-                        bw["done"][sl].record(self.side)
-                        bw["used"][sl] = True
-            self._on_side(wgrads)
+        ds_all = self._attn_block_bwd(w, a, xb_in, bw, parity, M, D, H, B, mask, seq, sub)
+        self._wgrads(bw, parity, flush)
         if bottom:
-            self._dgrad(dqkv, w, "wqkv", dx_out, M=Mall, N=D, K=3 * D, epilogue=ops.EPI_ADD_F32, aux=ds_all)
+            self._dgrad(dqkv, w, "wqkv", dx_out, M=M, N=D, K=3 * D, epilogue=ops.EPI_ADD_F32, aux=ds_all)
             return dx_out, None, flush
-        self._dgrad(dqkv, w, "wqkv", dxb, M=Mall, N=D, K=3 * D)
+        self._dgrad(dqkv, w, "wqkv", dxb, M=M, N=D, K=3 * D)
         return ds_all, dxb, flush
-
-    def _ln_pre_bwd(self, dy, s, gamma, mean, rstd, *, M: int, D: int, dgamma=None, dbeta=None, dbias=None, **kw) -> None:
-        """wj_layernorm_pre_bwd with the fold forms of _ln_bwd / _ln_bwd_direct: partial rows folded later with the neighbours', or at
-        once (deterministic mode: always through partial rows and an ordered fold, never the kernel's own atomics)."""
-        if not (dgamma or dbeta or dbias):
-            ops.layernorm_pre_bwd(dy, s, gamma, mean, rstd, M=M, D=D, **kw)
-        elif self.defer_folds and 3 * D <= 2304:
-            ws = self._fold_slot()
-            ops.layernorm_pre_bwd(dy, s, gamma, mean, rstd, M=M, D=D, workspace=ws, **kw)
-            self._folds.append((ws, 3 * D, ops.ln_pre_bwd_partial_rows(M, D), 3 * D, dgamma, dbeta, dbias, D))
-        elif self.deterministic:
-            ops.layernorm_pre_bwd(dy, s, gamma, mean, rstd, M=M, D=D, workspace=self.red_ws, **kw)
-            self._fold_now(self.red_ws, 3 * D, ops.ln_pre_bwd_partial_rows(M, D), 3 * D, dgamma, dbeta, dbias, D)
-        else:
-            ops.layernorm_pre_bwd(dy, s, gamma, mean, rstd, M=M, D=D, dgamma=dgamma, dbeta=dbeta, dbias=dbias, workspace=self.red_ws, **kw)
 
     def _layer_bwd_pre(self, w: _Layer, a: _Acts, s0: torch.Tensor, below: Optional[_Layer], dx_out: torch.Tensor, M: int, D: int, H: int,
                        B: int, mask: Optional[torch.Tensor], bw: dict, parity: int, seq: Optional[Tuple[torch.Tensor, int]] = None,
@@ -1134,72 +1174,99 @@ class JepaEngine:
         the backward of the norm one half-layer up (the layer above's norm1, or the stack's final norm), which also gave linear2.bias its
         gradient.  On exit the same holds for the layer `below` (slot parity - 1); below = None (the first layer of the stack): d(s0)
         goes to dx_out (fp32) for the consumers below the stack.  s0: the stream the layer read (a.x1, or the stack's input for the
-        first layer).  Every GEMM, attention and weight-gradient call is _layer_bwd's; returns (d(s0) buffer, flushed)."""
-        ds, dx1, do = bw["ds"], bw["dx1"], bw["do"]
-        dsb2, dsb1, dh, dqkv = bw["dsb2"][parity], bw["dsb1"][parity], bw["dh"][parity], bw["dqkv"][parity]
-        if self.use_side and bw["used"][parity]:
-            torch.cuda.current_stream().wait_event(bw["done"][parity])   # side stream finished reading this parity's buffers
-        Mall, o_in = M, a.o
-        if sub is not None:              # ds holds the sub-rows only; everything up to the attention works on them
-            M = sub[2]
-            o_in = self.tail_o
-        dgb, dxb = bw["dgb"], bw["dxb"]
-        self._dgrad(dsb2, w, "w2", dh, M=M, N=4 * D, K=D, epilogue=ops.EPI_MUL_GELU_GRAD, aux=a.h,
-                    colsum=w.gb1)        # linear1.bias gradient = column sums of dh, fused into the producing epilogue
-        bw["pending"] += [(dsb2, a.g, w.gw2, D, 4 * D, M), (dh, a.x2b, w.gw1, 4 * D, D, M)]
-        self._dgrad(dh, w, "w1", dgb, M=M, N=D, K=4 * D)
+        first layer).  Returns (d(s0) buffer, flushed)."""
+        ds, dxb = bw["ds"], bw["dxb"]
+        self._slot_wait(bw, parity)
+        Ms = M if sub is None else sub[2]      # ds holds the sub-rows only; everything up to the attention works on them
+        self._mlp_bwd(w, a, a.x2b, bw, parity, Ms, D)
         # norm2: d(s1) = d(s2) + LN2'(d LN2(s1)), in place; its bf16 rounding is out_proj's dY, its column sums out_proj.bias's gradient
-        self._ln_pre_bwd(dgb, a.x2, w.g2, a.m2, a.r2, M=M, D=D, dres=ds, dy_is_bf16=True, ds_f32=ds, ds_bf16=dsb1,
+        self._ln_pre_bwd(bw["dgb"], a.x2, w.g2, a.m2, a.r2, M=Ms, D=D, dres=ds, dy_is_bf16=True, ds_f32=ds, ds_bf16=bw["dsb1"][parity],
                          dgamma=w.gg2, dbeta=w.gbe2, dbias=w.gbo)
-        ds_all = ds
-        if sub is None:
-            self._dgrad(dsb1, w, "wo", do, M=M, N=D, K=D)
-        else:                             # back to all rows: zero gradient where no output was used
-            self._dgrad(dsb1, w, "wo", self.tail_do, M=M, N=D, K=D)
-            ops.unmask_rows_f32(self.tail_do, sub[1], do, M=Mall, D=D, dst_is_bf16=True)
-            ops.unmask_rows_f32(ds, sub[1], dx1, M=Mall, D=D, src_is_f32=True)       # dx1 is free again: residual gradient
-            ds_all = dx1
-        if seq is not None:
-            self._attn_bwd(a.qkv, a.o, do, a.lse, dqkv, B=B, T=seq[1], H=H, hd=D // H, seq_off=seq[0], dbias=w.gbqkv)
-        else:
-            self._attn_bwd(a.qkv, a.o, do, a.lse, dqkv, B=B, T=self.T, H=H, hd=D // H, key_mask=mask, dbias=w.gbqkv)
-        bw["pending"] += [(dsb1, o_in, w.gwo, D, D, M), (dqkv, a.x1b, w.gwqkv, 3 * D, D, Mall)]
-        bw["pending_slots"].append(parity)
-        if flush:
-            probs, slots = bw["pending"], bw["pending_slots"]
-            bw["pending"], bw["pending_slots"] = [], []
-
-            def wgrads():
-                for i in range(0, len(probs), 8):
-                    if self.deterministic:
-                        ops.wgrad_grouped(probs[i:i + 8], workspace=self._det_ws(), deterministic=True)
-                    else:
-                        ops.wgrad_grouped(probs[i:i + 8])
-                if self.use_side:
-                    for sl in slots:
-                        bw["done"][sl].record(self.side)
-                        bw["used"][sl] = True
-            self._on_side(wgrads)
-        self._dgrad(dqkv, w, "wqkv", dxb, M=Mall, N=D, K=3 * D)
+        ds_all = self._attn_block_bwd(w, a, a.x1b, bw, parity, M, D, H, B, mask, seq, sub)
+        self._wgrads(bw, parity, flush)
+        self._dgrad(bw["dqkv"][parity], w, "wqkv", dxb, M=M, N=D, K=3 * D)
         # norm1: d(s0) = d(s1) + LN1'(d LN1(s0)).  Above a layer it is that layer's d(s2): fp32 in bw["ds"], bf16 (linear2's dY) in the
         # layer's own slot, column sums = its linear2.bias gradient -- every gradient of THIS layer is out when the call returns
         if below is None:
-            self._ln_pre_bwd(dxb, s0, w.g1, a.m1, a.r1, M=Mall, D=D, dres=ds_all, dy_is_bf16=True, ds_f32=dx_out,
+            self._ln_pre_bwd(dxb, s0, w.g1, a.m1, a.r1, M=M, D=D, dres=ds_all, dy_is_bf16=True, ds_f32=dx_out,
                              dgamma=w.gg1, dbeta=w.gbe1)
             return dx_out, flush
         pb = (parity - 1) % bw["nbuf"]
-        if self.use_side and bw["used"][pb]:
-            torch.cuda.current_stream().wait_event(bw["done"][pb])       # (slot pb's last readers went out at least a layer ago)
-        self._ln_pre_bwd(dxb, s0, w.g1, a.m1, a.r1, M=Mall, D=D, dres=ds_all, dy_is_bf16=True, ds_f32=ds, ds_bf16=bw["dsb2"][pb],
+        self._slot_wait(bw, pb)              # (slot pb's last readers went out at least a layer ago)
+        self._ln_pre_bwd(dxb, s0, w.g1, a.m1, a.r1, M=M, D=D, dres=ds_all, dy_is_bf16=True, ds_f32=ds, ds_bf16=bw["dsb2"][pb],
                          dgamma=w.gg1, dbeta=w.gbe1, dbias=below.gb2)
         return ds, flush
 
-    def _stack_bwd_top_pre(self, dy, sf, norm: str, fm, fr, top: _Layer, bw: dict, parity: int, M: int, D: int) -> None:
-        """Backward of a pre-norm stack's final norm (dy: fp32 gradient of its output; nothing bypasses it): d(stream) for the top
-        layer -- fp32 in bw["ds"], bf16 in its slot -- and that layer's linear2.bias gradient."""
-        f = self.flat
-        self._ln_pre_bwd(dy, sf, f.ptr32(norm + ".weight"), fm, fr, M=M, D=D, ds_f32=bw["ds"], ds_bf16=bw["dsb2"][parity],
-                         dgamma=f.gptr(norm + ".weight"), dbeta=f.gptr(norm + ".bias"), dbias=top.gb2)
+    # ---- a whole stack: the layers and the final norm, in either norm order
+    def _stack(self, stack: str):
+        """(layers, width, heads, norm_first, name of the final norm) of the student ("enc") or the predictor ("dec")"""
+        c = self.cfg
+        if stack == "enc":
+            return self.enc_layers, c.d_enc, c.h_enc, c.norm_first_enc, "encoder.norm"
+        return self.dec_layers, c.d_dec, c.h_dec, c.norm_first_dec, "decoder.norm"
+
+    def _stack_fwd(self, stack: str, x: torch.Tensor, xb: torch.Tensor, M: int, B: int, mask: Optional[torch.Tensor],
+                   seq: Optional[Tuple[torch.Tensor, int]] = None, *, acts: Optional[List[_Acts]] = None,
+                   sub: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None, lean: bool = False, **out) -> None:
+        """Walk a stack's layers forward from the stream x (fp32; xb: its bf16 copy, which only post-norm layers read), then its final
+        norm, which writes `out` (y_f32 / y_bf16 / mean / rstd).  mask, seq: as _layer_fwd; sub: the rows that go on behind the last
+        layer's attention.  acts: where every layer saves for the backward; None (inference): nothing is saved, every layer runs in
+        self.scratch.  lean: the post-norm final norm may take its capped-grid form (WJ_LN_LEAN names the stack)."""
+        c, f = self.cfg, self.flat
+        layers, D, H, pre, norm = self._stack(stack)
+        save, top = acts is not None, len(layers) - 1
+        gamma, beta = f.ptr32(norm + ".weight"), f.ptr32(norm + ".bias")
+        Mo = M if sub is None else sub[2]                      # rows that leave the stack
+        if pre:
+            r = None
+            for i, w in enumerate(layers):
+                x, r = self._layer_fwd_pre(w, acts[i] if save else self.scratch, x, r, M, D, H, B, mask, seq, save=save,
+                                           sub=sub if i == top else None, stack=stack)
+            # the final norm also performs the last residual add; the stream it normalises is kept for its backward
+            ops.layernorm_pre_fwd(x, gamma, beta, M=Mo, D=D, eps=c.norm_eps, r=r, s_f32=getattr(self, stack + "_sf") if save else None, **out)
+            return
+        xq = False
+        for i, w in enumerate(layers):
+            a = acts[i] if save else self.scratch
+            xq = self._layer_fwd(w, a, x, xb, M, D, H, B, mask, seq, save=save, sub=sub if i == top else None, stack=stack, xq_ready=xq)
+            x, xb = a.x2, a.x2b
+        ops.layernorm_fwd(x, gamma, beta, M=Mo, D=D, eps=c.norm_eps,
+                          workgroups=self.ln_lean_wgs if (lean and self._lean_now and stack in self.ln_lean) else 0, **out)
+
+    def _stack_bwd(self, stack: str, x0: torch.Tensor, xb0: torch.Tensor, M: int, B: int, mask: Optional[torch.Tensor],
+                   seq: Optional[Tuple[torch.Tensor, int]] = None, *, sub: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None,
+                   flushed=None) -> torch.Tensor:
+        """Backward of _stack_fwd: bw["dx1"] holds the fp32 gradient of the final norm's output (nothing bypasses that norm); returns
+        the fp32 gradient of the stack's input (x0, xb0).  The weight gradients of bw["group"] consecutive layers share a grouped
+        launch; `flushed(i)` is called behind layer i when its launch has been queued."""
+        f, bw = self.flat, self.bw[stack]
+        layers, D, H, pre, norm = self._stack(stack)
+        acts = self.enc_acts if stack == "enc" else self.dec_acts
+        fm, fr = getattr(self, stack + "_fm"), getattr(self, stack + "_fr")
+        top, nbuf, group = len(layers) - 1, bw["nbuf"], bw["group"]
+        Mo = M if sub is None else sub[2]                      # rows that left the stack
+        grads = dict(dgamma=f.gptr(norm + ".weight"), dbeta=f.gptr(norm + ".bias"))
+        if pre:
+            # d(stream) for the top layer -- fp32 in bw["ds"], bf16 in its slot -- and that layer's linear2.bias gradient
+            self._ln_pre_bwd(bw["dx1"], getattr(self, stack + "_sf"), f.ptr32(norm + ".weight"), fm, fr, M=Mo, D=D, ds_f32=bw["ds"],
+                             ds_bf16=bw["dsb2"][top % nbuf], dbias=layers[top].gb2, **grads)
+        else:
+            self._ln_bwd_direct(bw["dx1"], acts[top].x2, f.ptr32(norm + ".weight"), fm, fr, M=Mo, D=D, ds_f32=bw["dy"],
+                                workspace=self.red_ws, **grads)
+        dy, dyb = bw["dy"], None
+        for i in range(top, -1, -1):
+            w, a, sub_i = layers[i], acts[i], sub if i == top else None
+            flush = (top - i) % group == group - 1 or i == 0
+            if pre:
+                dy, done = self._layer_bwd_pre(w, a, x0 if i == 0 else a.x1, layers[i - 1] if i > 0 else None, bw["dy"], M, D, H, B, mask,
+                                               bw, i % nbuf, seq, sub=sub_i, flush=flush)
+            else:
+                x_in, xb_in = (x0, xb0) if i == 0 else (acts[i - 1].x2, acts[i - 1].x2b)
+                dy, dyb, done = self._layer_bwd(w, a, x_in, xb_in, dy, dyb, bw["dy"], M, D, H, B, mask, bw, i % nbuf, seq, sub=sub_i,
+                                                flush=flush, bottom=i == 0)
+            if done and flushed is not None:
+                flushed(i)
+        return dy
 
     # ------------------------------------------------------------------------------------------------ front-end
     def _frontend(self, audio: torch.Tensor) -> None:
@@ -1248,7 +1315,6 @@ class JepaEngine:
     # ------------------------------------------------------------------------------------------------ forward
     def forward(self, audio: torch.Tensor, plan: MaskPlan) -> None:
         """Training forward.  Results: self.loss[0], self.preds, self.targets, self.cf[:n_ctx], self.lf."""
-        c, f = self.cfg, self.flat
         N = audio.shape[0]
         if plan.N != N or plan.T != self.T or plan.G < 1:
             raise ValueError(f"mask plan is for {plan.N} clips x {plan.G} groups x {plan.T} tokens; the batch has {N} clips of {self.T} tokens")
@@ -1256,8 +1322,6 @@ class JepaEngine:
         self.alloc(N, train=True, G=plan.G, need_enc=plan.n_ctx if rag else 0, need_dec=plan.n_dec if rag else 0)
         self.plan = plan
         self.audio = audio
-        M, Mp, T, G = self.M, self.Mp, self.T, self.G
-        De, Dd = c.d_enc, c.d_dec
         self._lean_now = self.use_side
         try:
             self._forward_body(audio, plan)
@@ -1269,11 +1333,11 @@ class JepaEngine:
         N = audio.shape[0]
         M, Mp, T, G = self.M, self.Mp, self.T, self.G
         De, Dd = c.d_enc, c.d_dec
+        rag = self.ragged_step = self.ragged and plan.ragged_ok
         self._frontend(audio)
         # EMA teacher on the same local features (no mask, no final norm), joint instance-norm, mean of the last k layers:
         # independent of the student / predictor chain below, so it runs beside it on the side stream
-        rag_now = self.ragged and plan.ragged_ok
-        self.set_wt_need(plan.n_ctx if rag_now else M, plan.n_dec if rag_now else Mp)
+        self.set_wt_need(plan.n_ctx if rag else M, plan.n_dec if rag else Mp)
 
         def beside():
             self._teacher_targets()
@@ -1281,43 +1345,30 @@ class JepaEngine:
                 self.refresh_wt()       # W^T shadows for the backward's row-form dgrads: off the forward's critical path
         self._on_side(beside)
         self.wait_optimizer()           # (an update overlapped with this step's front-end: the transformer stacks' parameters)
-        self.ragged_step = self.ragged and plan.ragged_ok
-        if self.ragged_step and self.sparse_conv and torch.is_grad_enabled():
+        if rag and self.sparse_conv and torch.is_grad_enabled():
             # host-side list building + upload, hidden behind the forward kernels already queued.  (Building the lists later, behind
             # the student / predictor launches, measured the same outside the profiler -- 48.89 against 48.79 ms over three runs each --
             # and opened a 2-ms gap under rocprofv3, whose per-launch overhead makes the host the slower side.)
             self._conv_rows(plan)
         n_ctx = plan.n_ctx
-        if c.norm_first_enc:
-            self._student_fwd_pre(plan)
-        elif self.ragged_step:
+        final = dict(mean=self.enc_fm, rstd=self.enc_fr)
+        if rag:
             # student encoder on the context rows only, packed per clip (non-context rows are dropped at jepa.py:399 and,
             # being key-masked, never influence a context row)
-            Me, eseq = n_ctx, (plan.enc_off, max(plan.max_enc, 1))
             ops.mask_gather_rows(self.lf, plan.keep, self.enc_in, n_rows=n_ctx, D=De, elem_bytes=4)
-            ops.mask_gather_rows(self.lf_b, plan.keep, self.enc_in_b, n_rows=n_ctx, D=De, elem_bytes=2)
-            x, xb = self.enc_in, self.enc_in_b
-            xq = False
-            for w, a in zip(self.enc_layers, self.enc_acts):
-                xq = self._layer_fwd(w, a, x, xb, Me, De, c.h_enc, N, None, eseq, xq_ready=xq)
-                x, xb = a.x2, a.x2b
-            ops.layernorm_fwd(x, f.ptr32("encoder.norm.weight"), f.ptr32("encoder.norm.bias"), M=Me, D=De, eps=c.norm_eps,
-                              y_bf16=self.ctx_in, mean=self.enc_fm, rstd=self.enc_fr,
-                              workgroups=self.ln_lean_wgs if (self._lean_now and "enc" in self.ln_lean) else 0)
+            if not c.norm_first_enc:        # (a pre-norm stack's first norm1 makes the bf16 GEMM operand itself)
+                ops.mask_gather_rows(self.lf_b, plan.keep, self.enc_in_b, n_rows=n_ctx, D=De, elem_bytes=2)
+            self._stack_fwd("enc", self.enc_in, self.enc_in_b, n_ctx, N, None, (plan.enc_off, max(plan.max_enc, 1)), acts=self.enc_acts,
+                            lean=True, y_bf16=self.ctx_in, **final)
         else:
             # student encoder over every token (keys restricted to the context), then the boolean-mask gather
-            x, xb = self.lf, self.lf_b
-            xq = False
-            for w, a in zip(self.enc_layers, self.enc_acts):
-                xq = self._layer_fwd(w, a, x, xb, M, De, c.h_enc, N, plan.ctx_u8, xq_ready=xq)
-                x, xb = a.x2, a.x2b
-            ops.layernorm_fwd(x, f.ptr32("encoder.norm.weight"), f.ptr32("encoder.norm.bias"), M=M, D=De, eps=c.norm_eps,
-                              y_f32=self.enc_out, y_bf16=self.enc_out_b, mean=self.enc_fm, rstd=self.enc_fr)
+            self._stack_fwd("enc", self.lf, self.lf_b, M, N, plan.ctx_u8, acts=self.enc_acts,
+                            y_f32=None if c.norm_first_enc else self.enc_out, y_bf16=self.enc_out_b, **final)
             ops.mask_gather_rows(self.enc_out_b, plan.keep, self.ctx_in, n_rows=n_ctx, D=De, elem_bytes=2)
         ops.gemm(self.ctx_in, f.ptr16("encoder_to_decoder_mapper.weight"), self.cf, M=n_ctx, N=Dd, K=De, lda=De, ldb=De, ldc=Dd,
                  bias=f.ptr32("encoder_to_decoder_mapper.bias"))
         # predictor over (context U group targets), one sequence per (clip, group)
-        if self.ragged_step:
+        if rag:
             Md, dseq = plan.n_dec, (plan.dec_off, max(plan.max_dec, 1))
             ops.mask_scatter_fill_pos(self.cf, plan.inv, f.ptr32("mask_token"), self.pos_dec, B=N, T=T, D=Dd, G=G,
                                       out_f32=self.dec_in, out_bf16=self.dec_in_b, rows=plan.dec_rows, n_rows=Md)
@@ -1325,50 +1376,14 @@ class JepaEngine:
             Md, dseq = Mp, None
             ops.mask_scatter_fill_pos(self.cf, plan.inv, f.ptr32("mask_token"), self.pos_dec, B=N, T=T, D=Dd, G=G,
                                       out_f32=self.dec_in, out_bf16=self.dec_in_b)
-        x, xb = self.dec_in, self.dec_in_b
-        self.tail = (plan.tgt_rows, plan.tgt_inv, plan.n_tgt) if (self.ragged_step and self.trim_tail and plan.n_tgt > 0) else None
+        self.tail = (plan.tgt_rows, plan.tgt_inv, plan.n_tgt) if (rag and self.trim_tail and plan.n_tgt > 0) else None
         Mo = plan.n_tgt if self.tail is not None else Md      # rows that leave the predictor
-        if c.norm_first_dec:
-            r = None
-            for i, (w, a) in enumerate(zip(self.dec_layers, self.dec_acts)):
-                x, r = self._layer_fwd_pre(w, a, x, r, Md, Dd, c.h_dec, N * G, plan.vis_u8, dseq,
-                                           sub=self.tail if i == c.l_dec - 1 else None, stack="dec")
-            # the final norm also performs the last residual add; the stream it normalises is kept for its backward
-            ops.layernorm_pre_fwd(x, f.ptr32("decoder.norm.weight"), f.ptr32("decoder.norm.bias"), M=Mo, D=Dd, eps=c.norm_eps, r=r,
-                                  s_f32=self.dec_sf, y_bf16=self.dec_out_b, mean=self.dec_fm, rstd=self.dec_fr)
-        else:
-            xq = False
-            for i, (w, a) in enumerate(zip(self.dec_layers, self.dec_acts)):
-                last = i == c.l_dec - 1
-                xq = self._layer_fwd(w, a, x, xb, Md, Dd, c.h_dec, N * G, plan.vis_u8, dseq, sub=self.tail if last else None, stack="dec",
-                                     xq_ready=xq)
-                x, xb = a.x2, a.x2b
-            ops.layernorm_fwd(x, f.ptr32("decoder.norm.weight"), f.ptr32("decoder.norm.bias"), M=Mo, D=Dd, eps=c.norm_eps,
-                              y_bf16=self.dec_out_b, mean=self.dec_fm, rstd=self.dec_fr,
-                              workgroups=self.ln_lean_wgs if (self._lean_now and "dec" in self.ln_lean) else 0)
+        self._stack_fwd("dec", self.dec_in, self.dec_in_b, Md, N * G, plan.vis_u8, dseq, acts=self.dec_acts, sub=self.tail, lean=True,
+                        y_bf16=self.dec_out_b, mean=self.dec_fm, rstd=self.dec_fr)
         ops.gemm(self.dec_out_b, f.ptr16("decoder_to_encoder_mapper.weight"), self.preds, M=Mo, N=De, K=Dd, lda=Dd, ldb=Dd,
                  ldc=De, bias=f.ptr32("decoder_to_encoder_mapper.bias"))
         self._join_side()               # teacher targets (side stream) are needed by the loss
         self._mse(None, None)
-
-    def _student_fwd_pre(self, plan: MaskPlan) -> None:
-        """Pre-norm student: the context rows packed per clip (ragged step), or every token with the keys restricted to the context and
-        the boolean-mask gather behind the final norm -> self.ctx_in.  The first norm1 makes the bf16 GEMM operand itself, so only the
-        fp32 rows are gathered."""
-        c, f, N, De = self.cfg, self.flat, self.N, self.cfg.d_enc
-        if self.ragged_step:
-            Me, eseq, mask, x = plan.n_ctx, (plan.enc_off, max(plan.max_enc, 1)), None, self.enc_in
-            ops.mask_gather_rows(self.lf, plan.keep, self.enc_in, n_rows=plan.n_ctx, D=De, elem_bytes=4)
-        else:
-            Me, eseq, mask, x = self.M, None, plan.ctx_u8, self.lf
-        r = None
-        for w, a in zip(self.enc_layers, self.enc_acts):
-            x, r = self._layer_fwd_pre(w, a, x, r, Me, De, c.h_enc, N, mask, eseq)
-        ops.layernorm_pre_fwd(x, f.ptr32("encoder.norm.weight"), f.ptr32("encoder.norm.bias"), M=Me, D=De, eps=c.norm_eps, r=r,
-                              s_f32=self.enc_sf, y_bf16=self.ctx_in if self.ragged_step else self.enc_out_b, mean=self.enc_fm,
-                              rstd=self.enc_fr)
-        if not self.ragged_step:
-            ops.mask_gather_rows(self.enc_out_b, plan.keep, self.ctx_in, n_rows=plan.n_ctx, D=De, elem_bytes=2)
 
     def _mse(self, dpreds, gscale_ptr) -> None:
         c, plan = self.cfg, self.plan
@@ -1476,7 +1491,7 @@ class JepaEngine:
             section_final(tag)
         self._folds = []                 # entries an exception in an earlier backward may have left behind must not be folded into this one
         c, f, plan = self.cfg, self.flat, self.plan
-        N, M, Mp, T, G, C = self.N, self.M, self.Mp, self.T, self.G, self.C
+        N, M, Mp, T, G = self.N, self.M, self.Mp, self.T, self.G
         De, Dd = c.d_enc, c.d_dec
         if not getattr(f, "g_clean", False):      # (FusedAdamW.fuse_zero_grad: the last update left the buffer clear)
             f.g32.zero_()
@@ -1495,41 +1510,17 @@ class JepaEngine:
         self._wgrad(self.dpreds, self.dec_out_b, f.gptr("decoder_to_encoder_mapper.weight"), De, Dd, Mo)
         ops.gemm(self.dpreds, f.ptr16("decoder_to_encoder_mapper.weight"), bw["dx1"], M=Mo, N=Dd, K=De, lda=De, ldb=Dd, ldc=Dd,
                  b_trans=1, epilogue=ops.EPI_ADD_F32)
-        last = self.dec_acts[-1]
-        if c.norm_first_dec:
-            self._stack_bwd_top_pre(bw["dx1"], self.dec_sf, "decoder.norm", self.dec_fm, self.dec_fr, self.dec_layers[-1], bw,
-                                    (c.l_dec - 1) % bw["nbuf"], Mo, Dd)
-            for i in range(c.l_dec - 1, -1, -1):
-                dy, _ = self._layer_bwd_pre(self.dec_layers[i], self.dec_acts[i], self.dec_in if i == 0 else self.dec_acts[i].x1,
-                                            self.dec_layers[i - 1] if i > 0 else None, bw["dy"], Md, Dd, c.h_dec, N * G, plan.vis_u8, bw,
-                                            i % bw["nbuf"], dseq, sub=self.tail if (rag and i == c.l_dec - 1) else None)
-        else:
-            self._ln_bwd_direct(bw["dx1"], last.x2, f.ptr32("decoder.norm.weight"), self.dec_fm, self.dec_fr, M=Mo, D=Dd, ds_f32=bw["dy"],
-                                dgamma=f.gptr("decoder.norm.weight"), dbeta=f.gptr("decoder.norm.bias"), workspace=self.red_ws)
-            dy, dyb = bw["dy"], None
-            for i in range(c.l_dec - 1, -1, -1):
-                x_in, xb_in = (self.dec_in, self.dec_in_b) if i == 0 else (self.dec_acts[i - 1].x2, self.dec_acts[i - 1].x2b)
-                dy, dyb, _ = self._layer_bwd(self.dec_layers[i], self.dec_acts[i], x_in, xb_in, dy, dyb, bw["dy"], Md, Dd, c.h_dec, N * G, plan.vis_u8,
-                                             bw, i % bw["nbuf"], dseq, sub=self.tail if (rag and i == c.l_dec - 1) else None, bottom=i == 0)
+        dy = self._stack_bwd("dec", self.dec_in, self.dec_in_b, Md, N * G, plan.vis_u8, dseq, sub=self.tail if rag else None)
         n_ctx = plan.n_ctx
         # the mask-token gradient leaves the kernel as one partial row per workgroup, folded with the other deferred folds (round 4:
-        # 384 global float atomics per workgroup into the same 384 addresses)
+        # 384 global float atomics per workgroup into the same 384 addresses); deterministic mode: never the kernel's own atomics
         sf_rows = ops.scatter_fill_bwd_partial_rows(N, T)
-        if self.defer_folds and Dd <= 2304 and sf_rows * Dd * 4 <= self._red_bytes:
-            ws = self._fold_slot()
-            ops.mask_scatter_fill_pos_bwd(dy, plan.inv, self.d_cf, f.gptr("mask_token"), B=N, T=T, D=Dd, G=G,
-                                          rowmap=plan.dec_map if rag else None, partials=ws)
-            self._folds.append((ws, Dd, sf_rows, Dd, f.gptr("mask_token"), None, None, Dd))
-        elif self.deterministic:
-            # never the kernel's own atomics: partial rows, folded in order at once
-            if sf_rows * Dd * 4 > self.red_ws.numel() * 4:
-                raise RuntimeError("deterministic mode: the mask-token partial rows do not fit the reduction scratch")
-            ops.mask_scatter_fill_pos_bwd(dy, plan.inv, self.d_cf, f.gptr("mask_token"), B=N, T=T, D=Dd, G=G,
-                                          rowmap=plan.dec_map if rag else None, partials=self.red_ws)
-            self._fold_now(self.red_ws, Dd, sf_rows, Dd, f.gptr("mask_token"), None, None, Dd)
-        else:
-            ops.mask_scatter_fill_pos_bwd(dy, plan.inv, self.d_cf, f.gptr("mask_token"), B=N, T=T, D=Dd, G=G,
-                                          rowmap=plan.dec_map if rag else None)
+        form, ws = self._fold_form(Dd, True, fits=sf_rows * Dd * 4 <= self._red_bytes)
+        if form == "now" and sf_rows * Dd * 4 > self.red_ws.numel() * 4:
+            raise RuntimeError("deterministic mode: the mask-token partial rows do not fit the reduction scratch")
+        ops.mask_scatter_fill_pos_bwd(dy, plan.inv, self.d_cf, f.gptr("mask_token"), B=N, T=T, D=Dd, G=G,
+                                      rowmap=plan.dec_map if rag else None, partials=ws)
+        self._fold(form, ws, Dd, sf_rows, f.gptr("mask_token"), None, None, Dd)
         # encoder_to_decoder_mapper (rows = gathered context tokens)
         self._colsum_bf16(self.d_cf, f.gptr("encoder_to_decoder_mapper.bias"), M=n_ctx, N=Dd, ldx=Dd)
         self._wgrad(self.d_cf, self.ctx_in, f.gptr("encoder_to_decoder_mapper.weight"), Dd, De, n_ctx)
@@ -1541,33 +1532,17 @@ class JepaEngine:
             ops.unmask_rows_f32(self.d_ctx_in, None, bw["dx1"], M=Me, D=De)      # packed rows: a widening copy
         else:
             ops.unmask_rows_f32(self.d_ctx_in, plan.inv, bw["dx1"], M=M, D=De)
-        last = self.enc_acts[-1]
-        if c.norm_first_enc:
-            self._stack_bwd_top_pre(bw["dx1"], self.enc_sf, "encoder.norm", self.enc_fm, self.enc_fr, self.enc_layers[-1], bw,
-                                    (c.l_enc - 1) % bw["nbuf"], Me, De)
-        else:
-            self._ln_bwd_direct(bw["dx1"], last.x2, f.ptr32("encoder.norm.weight"), self.enc_fm, self.enc_fr, M=Me, D=De, ds_f32=bw["dy"],
-                                dgamma=f.gptr("encoder.norm.weight"), dbeta=f.gptr("encoder.norm.bias"), workspace=self.red_ws)
-        dy, dyb = bw["dy"], None
         enc_ready = set()
-        for i in range(c.l_enc - 1, -1, -1):
-            first = (self.enc_in, self.enc_in_b) if rag else (self.lf, self.lf_b)
-            flush_i = (c.l_enc - 1 - i) % bw["group"] == bw["group"] - 1 or i == 0
+
+        def flushed(i):
             # the weight gradients of two layers share a grouped launch: a layer's section of the gradient buffer is final (and its
             # all-reduce bucket may go) once the launch that carries it has been queued
-            if c.norm_first_enc:
-                dy, done = self._layer_bwd_pre(self.enc_layers[i], self.enc_acts[i], first[0] if i == 0 else self.enc_acts[i].x1,
-                                               self.enc_layers[i - 1] if i > 0 else None, bw["dy"], Me, De, c.h_enc, N, plan.ctx_u8, bw,
-                                               i % bw["nbuf"], eseq, flush=flush_i)
-            else:
-                x_in, xb_in = first if i == 0 else (self.enc_acts[i - 1].x2, self.enc_acts[i - 1].x2b)
-                dy, dyb, done = self._layer_bwd(self.enc_layers[i], self.enc_acts[i], x_in, xb_in, dy, dyb, bw["dy"], Me, De, c.h_enc, N, plan.ctx_u8,
-                                                bw, i % bw["nbuf"], eseq, flush=flush_i, bottom=i == 0)
-            if done:
-                for j in range(min(c.l_enc - 1, i + bw["group"] - 1), i - 1, -1):
-                    if j not in enc_ready:
-                        enc_ready.add(j)
-                        ready(f"enc:{j}")
+            for j in range(min(c.l_enc - 1, i + bw["group"] - 1), i - 1, -1):
+                if j not in enc_ready:
+                    enc_ready.add(j)
+                    ready(f"enc:{j}")
+        first = (self.enc_in, self.enc_in_b) if rag else (self.lf, self.lf_b)
+        dy = self._stack_bwd("enc", first[0], first[1], Me, N, plan.ctx_u8, eseq, flushed=flushed)
         self._frontend_bwd(dy, rag, plan)
         self._flush_folds()
         self._join_side()                # all weight gradients are final before the optimiser / last all-reduce
@@ -1755,25 +1730,11 @@ class JepaEngine:
 
     def infer(self, audio: torch.Tensor, key_mask_u8: Optional[torch.Tensor]) -> torch.Tensor:
         """Student-only forward (reference jepa.py:456-467): returns fp32 [N, T, d_enc]."""
-        c, f = self.cfg, self.flat
+        c = self.cfg
         N = audio.shape[0]
         if N != self.N:
             self.alloc(N, train=False)
         self.wait_optimizer()
         self._frontend(audio)
-        a = self.scratch
-        if c.norm_first_enc:
-            x, r = self.lf, None
-            for w in self.enc_layers:
-                x, r = self._layer_fwd_pre(w, a, x, r, self.M, c.d_enc, c.h_enc, N, key_mask_u8, save=False)
-            ops.layernorm_pre_fwd(x, f.ptr32("encoder.norm.weight"), f.ptr32("encoder.norm.bias"), M=self.M, D=c.d_enc, eps=c.norm_eps,
-                                  r=r, y_f32=self.enc_out)
-            return self.enc_out.view(N, self.T, c.d_enc)
-        x, xb = self.lf, self.lf_b
-        xq = False
-        for w in self.enc_layers:
-            xq = self._layer_fwd(w, a, x, xb, self.M, c.d_enc, c.h_enc, N, key_mask_u8, save=False, xq_ready=xq)
-            x, xb = a.x2, a.x2b
-        ops.layernorm_fwd(x, f.ptr32("encoder.norm.weight"), f.ptr32("encoder.norm.bias"), M=self.M, D=c.d_enc, eps=c.norm_eps,
-                          y_f32=self.enc_out)
+        self._stack_fwd("enc", self.lf, self.lf_b, self.M, N, key_mask_u8, y_f32=self.enc_out)
         return self.enc_out.view(N, self.T, c.d_enc)
