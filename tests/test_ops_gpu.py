@@ -678,6 +678,72 @@ def test_layernorm_bf16_input_with_row_remap(ops):
     assert float(got[:, T:].abs().max()) == 0.0
 
 
+@pytest.mark.parametrize("dy2_is_bf16", [False, True])
+@pytest.mark.parametrize("M,D", [(67, 384),     # two rows per wave, odd M: a dead second row slot
+                                 (37, 768),     # one row per wave
+                                 (9, 1024)])    # the widest instance, fewer rows than a workgroup
+def test_layernorm_bwd_second_gradient_operand(ops, M, D, dy2_is_bf16):
+    """wj_ln_bwd_args.dy2 (f32, or bf16 with dy2_is_bf16): the backward of LN(x + r) driven with dy + dy2, atomic and workspace forms.
+    Bounds: those of test_layernorm_fwd_bwd for M < 1000."""
+    x = rnd(M, D, seed=130)
+    r = rnd(M, D, dtype=torch.bfloat16, seed=131)
+    gamma = 1 + 0.1 * rnd(D, seed=132)
+    beta = 0.1 * rnd(D, seed=133)
+    dy = rnd(M, D, seed=134)
+    dy2 = rnd(M, D, dtype=torch.bfloat16 if dy2_is_bf16 else torch.float32, seed=135)
+    mean = torch.empty(M, device=dev())
+    rstd = torch.empty(M, device=dev())
+    ops.layernorm_fwd(x, gamma, beta, M=M, D=D, eps=1e-6, r=r, mean=mean, rstd=rstd)
+    xr = x.clone().requires_grad_(True)
+    g2 = gamma.clone().requires_grad_(True)
+    b2 = beta.clone().requires_grad_(True)
+    F.layer_norm(xr + r.float(), (D,), g2, b2, 1e-6).backward(dy + dy2.float())
+    outs = []
+    for with_ws in (False, True):
+        ds = torch.empty(M, D, device=dev())
+        dsb = torch.empty(M, D, dtype=torch.bfloat16, device=dev())
+        dgamma, dbeta, dbias = (torch.zeros(D, device=dev()) for _ in range(3))
+        wsp = torch.empty(ops.ln_bwd_partial_rows(M, D) * 3 * D, device=dev()) if with_ws else None
+        ops.layernorm_bwd(dy, x, gamma, mean, rstd, M=M, D=D, r=r, dy2=dy2, dy2_is_bf16=dy2_is_bf16, ds_f32=ds, ds_bf16=dsb,
+                          dgamma=dgamma, dbeta=dbeta, dbias=dbias, workspace=wsp)
+        assert relerr(ds, xr.grad) < 2e-5
+        assert relerr(dgamma, g2.grad) < 2e-5
+        assert relerr(dbeta, b2.grad) < 2e-5
+        assert torch.equal(dsb, ds.to(torch.bfloat16))
+        assert relerr(dbias, dsb.float().sum(0)) < 1e-5
+        outs.append((dgamma, dbeta, dbias))
+    for atomic, folded in zip(*outs):
+        assert relerr(folded, atomic) < 1e-5
+
+
+def test_layernorm_channel_major_row_remap(ops):
+    """in_chan / chan = S > 1: token m = (n*S + c)*T + t lives at row (c*N + n)*P + t of the channel-major padded conv buffer."""
+    N, S, T, P, D = 3, 2, 10, 11, 64
+    M = N * S * T
+    buf = rnd(S * N * P, D, dtype=torch.bfloat16, seed=140)
+    gamma = 1 + 0.1 * rnd(D, seed=141)
+    beta = 0.1 * rnd(D, seed=142)
+    yb = torch.empty(M, D, dtype=torch.bfloat16, device=dev())
+    mean = torch.empty(M, device=dev())
+    rstd = torch.empty(M, device=dev())
+    ops.layernorm_fwd(buf, gamma, beta, M=M, D=D, eps=1e-5, y_bf16=yb, mean=mean, rstd=rstd, x_is_bf16=True, in_seg=P, in_valid=T, in_chan=S)
+    # [c][n][p][d] -> tokens in (n, c, t) order
+    xin = buf.float().reshape(S, N, P, D)[:, :, :T].permute(1, 0, 2, 3).reshape(M, D)
+    ref = F.layer_norm(xin, (D,), gamma, beta, 1e-5)
+    assert relerr(yb.float(), ref) < 4e-3
+    dy = rnd(M, D, seed=143)
+    dxb = torch.zeros(S * N * P, D, dtype=torch.bfloat16, device=dev())
+    dg = torch.zeros(D, device=dev())
+    db = torch.zeros(D, device=dev())
+    ops.layernorm_bwd(dy, buf, gamma, mean, rstd, M=M, D=D, ds_bf16=dxb, dgamma=dg, dbeta=db, x_is_bf16=True, in_seg=P, in_valid=T,
+                      out_seg=P, out_valid=T, chan=S)
+    xr = xin.clone().requires_grad_(True)
+    F.layer_norm(xr, (D,), gamma, beta, 1e-5).backward(dy)
+    got = dxb.float().reshape(S, N, P, D)
+    assert relerr(got[:, :, :T].permute(1, 0, 2, 3).reshape(M, D), xr.grad) < 4e-3
+    assert float(got[:, :, T:].abs().max()) == 0.0
+
+
 def test_colsum(ops):
     M, N = 1003, 192
     x = rnd(M, N, dtype=torch.bfloat16, seed=29)
