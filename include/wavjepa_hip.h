@@ -452,6 +452,98 @@ typedef struct {
 } wj_gelu_bwd_args;
 int wj_gelu_bwd_bf16(const wj_gelu_bwd_args*, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Conv front-end in mode="layer_norm" (audio_feature_extractor.py:79-90): every layer is
+ *   Conv1d(+bias) -> LayerNorm over the C channels -> erf-GELU.
+ * The activations are channels-last, so the LayerNorm runs over a row.  fp32 statistics, biased variance; z = LN(pre) * gamma +
+ * beta stays in registers, post = bf16(gelu(z)).  C in {64, 128, 256, 512}: a lane owns 8 channels, C / 8 lanes a row; any other C is
+ * WJ_ERR_UNSUPPORTED before any launch.  No float atomics: parameter-gradient partials are stored per workgroup and folded in order.
+ *
+ * Layers >= 1 (csrc/conv_ln.hip): `pre` is what the conv GEMM (WJ_EPI_BF16, + bias) wrote, bf16 [M][C] with seg_rows rows per clip
+ * of which the first seg_valid are frames (seg_rows = 0: every row is a frame).  Padding rows ((m % seg_rows) >= seg_valid) are never
+ * read; `post` / `dpre` are written as 0 there.  mean / rstd: f32 [M], optional in the forward. */
+typedef struct {
+    const void* pre;
+    const float* gamma;
+    const float* beta;
+    void* post;
+    float* mean;
+    float* rstd;
+    int32_t M, C, seg_rows, seg_valid;
+    float eps;
+} wj_conv_ln_fwd_args;
+int wj_conv_ln_gelu_fwd(const wj_conv_ln_fwd_args*, void* stream);
+
+/* Backward: g = dpost * gelu'(z), dpre = bf16(LN'(g)).  rows == NULL: all M rows; else only rows[0 .. n_rows) (int32 row indices of the
+ * [M][C] buffers; no other row is read or written), with clear_dpost the consumed dpost rows are overwritten with zeros.
+ * workspace (required): f32 [wj_conv_ln_bwd_partial_rows(rows processed, C)][3][C] partial rows dgamma | dbeta | dbias (dbias = column
+ * sums of the bf16 dpre = the conv bias gradient), plain stores, contents before the call irrelevant.  With any of dgamma / dbeta /
+ * dbias the entry also folds the partial rows into them (+=) through wj_colsum_f32_group (`deterministic`: its ordered form); with all
+ * three NULL the rows are left for the caller's own wj_colsum_f32_group. */
+typedef struct {
+    void* dpost;
+    const void* pre;
+    const float* mean;
+    const float* rstd;
+    const float* gamma;
+    const float* beta;
+    void* dpre;
+    const int32_t* rows;
+    float* workspace;
+    float* dgamma;
+    float* dbeta;
+    float* dbias;
+    int32_t M, C, seg_rows, seg_valid, n_rows, clear_dpost, deterministic;
+} wj_conv_ln_bwd_args;
+int wj_conv_ln_gelu_bwd(const wj_conv_ln_bwd_args*, void* stream);
+/* partial rows the backward leaves for `rows` processed rows (M, or n_rows of the listed form) of width C; >= 1; -1: bad arguments */
+int wj_conv_ln_bwd_partial_rows(int rows, int C);
+
+/* Layer 0: one fused pass per output row: C_in*k taps -> C channels (+ bias, rounded to bf16 as the conv output of the autocast flow)
+ * -> LayerNorm -> GELU -> act bf16 [N][P][C] (rows >= L_out of every clip are written as 0); mean / rstd f32 [N][P], one per row.
+ * audio / w / audio_clip_stride as in wj_conv0_fwd_args; bias f32 [C] or NULL.  C_in*k in {10, 20}. */
+typedef struct {
+    const void* audio;
+    const void* w;
+    const float* bias;
+    const float* gamma;
+    const float* beta;
+    void* act;
+    float* mean;
+    float* rstd;
+    int64_t audio_clip_stride;
+    int32_t N, C_in, L, C, k, stride, L_out, P;
+    float eps;
+} wj_conv0_ln_fwd_args;
+int wj_conv0_ln_gelu_fwd(const wj_conv0_ln_fwd_args*, void* stream);
+
+/* Backward of layer 0: recomputes the conv output from the audio; dw f32 [C][C_in][k], dbias (NULL without a conv bias), dgamma,
+ * dbeta are accumulated (+=) from per-workgroup partial records folded in a fixed order (chunks of a clip, then clips).
+ * rows / row_off / max_rows: the listed form of wj_conv0_bwd_args (global row indices n*P + t grouped by clip; int32 [N+1] offsets;
+ * the longest clip list); rows == NULL reads every row t < L_out.  Rows off the list are not read.
+ * workspace: wj_workspace_bytes("wj_conv0_ln_gelu_bwd") bytes for the same N / C / taps / L_out / max_rows (0: the dense form). */
+typedef struct {
+    const void* audio;
+    const void* w;
+    const float* bias;
+    const float* gamma;
+    const float* beta;
+    const float* mean;
+    const float* rstd;
+    const void* dact;
+    const int32_t* rows;
+    const int32_t* row_off;
+    float* dw;
+    float* dbias;
+    float* dgamma;
+    float* dbeta;
+    float* workspace;
+    int64_t audio_clip_stride;
+    int32_t N, C_in, L, C, k, stride, L_out, P;
+    int32_t max_rows;
+} wj_conv0_ln_bwd_args;
+int wj_conv0_ln_gelu_bwd(const wj_conv0_ln_bwd_args*, void* stream);
+
 /* One wave that busy-waits for `ticks` s_memtime ticks.  Not compute: the engine uses two of these to find a second HIP
  * stream that really runs beside the main one (HIP maps streams onto a few hardware queues round-robin; two streams on
  * one queue serialise -- seen as soon as RCCL had created its own streams first). */
@@ -606,7 +698,7 @@ int wj_masked_mse(const wj_mse_args*, void* stream);
  * query tells the caller how many BYTES the call described by the SAME argument struct needs (pointers in it are
  * ignored).  `fn` is the entry point's name: "wj_gemm_bf16" / "wj_wgrad_grouped" / "wj_colsum_bf16" (the K-split pair scratch, or with
  * `deterministic` the slabs / partial rows of the store-and-sum forms), "wj_layernorm_bwd", "wj_attn_bwd" (its dbias_ws), "wj_conv0_gn_gelu_fwd",
- * "wj_conv0_gn_gelu_bwd", "wj_masked_mse", "wj_grad_sumsq", "wj_audio_prepare", "wj_noise_prepare".  Returns 0 for entry points without scratch, -1 for an unknown
+ * "wj_conv0_gn_gelu_bwd", "wj_conv_ln_gelu_bwd" (its partial rows), "wj_conv0_ln_gelu_bwd", "wj_masked_mse", "wj_grad_sumsq", "wj_audio_prepare", "wj_noise_prepare".  Returns 0 for entry points without scratch, -1 for an unknown
  * name or NULL arguments.
  * -----------------------------------------------------------------------------------------------------------*/
 int64_t wj_workspace_bytes(const char* fn, const void* args);

@@ -36,11 +36,12 @@ class ComponentFactory:
         cls = EXTRACTORS.get(cfg.extractor.name)
         if cls is None:
             raise ValueError(f"Unknown extractor type: {cfg.extractor.name}. Available extractors: {list(EXTRACTORS.keys())}")
+        norm = dict(mode=str(cfg.extractor.get("mode", "default")), conv_bias=bool(cfg.extractor.get("conv_bias", False)))
         if cls is ConvChannelFeatureExtractor:
             return cls(conv_layers_spec=parse_conv_spec(cfg.extractor.conv_layers_spec), in_channels=cfg.data.in_channels,
-                       share_weights_over_channels=bool(cfg.extractor.get("share_weights_over_channels", False)))
+                       share_weights_over_channels=bool(cfg.extractor.get("share_weights_over_channels", False)), **norm)
         return cls(conv_layers_spec=parse_conv_spec(cfg.extractor.conv_layers_spec), in_channels=cfg.data.in_channels,
-                   depthwise=cfg.extractor.depthwise)
+                   depthwise=cfg.extractor.depthwise, **norm)
 
     @staticmethod
     def create_masker(cfg):

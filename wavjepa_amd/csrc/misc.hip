@@ -601,6 +601,7 @@ extern "C" int wj_struct_size(const char* name) {
     WJ_SZ(wj_unmask_rows_args) WJ_SZ(wj_instnorm_args) WJ_SZ(wj_mse_args) WJ_SZ(wj_ema_args) WJ_SZ(wj_sumsq_args)
     WJ_SZ(wj_adamw_args) WJ_SZ(wj_cast_args) WJ_SZ(wj_crop_args) WJ_SZ(wj_zero_rows_args) WJ_SZ(wj_instnorm_mean_args) WJ_SZ(wj_spin_args)
     WJ_SZ(wj_gemm_fp8_args) WJ_SZ(wj_quantize_fp8_args) WJ_SZ(wj_wgrad_group_args) WJ_SZ(wj_rir_conv_args) WJ_SZ(wj_snr_mix_args) WJ_SZ(wj_resample_args) WJ_SZ(wj_mse_groups_args) WJ_SZ(wj_transpose_args) WJ_SZ(wj_colsum_group_args) WJ_SZ(wj_rccl_init_args) WJ_SZ(wj_rccl_launch_args) WJ_SZ(wj_rccl_wait_args) WJ_SZ(wj_audio_prepare_args) WJ_SZ(wj_noise_prepare_args)
+    WJ_SZ(wj_conv_ln_fwd_args) WJ_SZ(wj_conv_ln_bwd_args) WJ_SZ(wj_conv0_ln_fwd_args) WJ_SZ(wj_conv0_ln_bwd_args)
 #ifdef WJ_LAB
     WJ_SZ(wj_collective_footprint_args)
 #endif
@@ -618,6 +619,7 @@ int64_t wj_snr_mix_ws_bytes(const wj_snr_mix_args* a);
 int64_t wj_mse_groups_ws_bytes(const wj_mse_groups_args* a);  // csrc/denoise.hip
 int64_t wj_audio_prepare_ws_bytes(const wj_audio_prepare_args* a);  // csrc/audio_prep.hip
 int64_t wj_noise_prepare_ws_bytes(const wj_noise_prepare_args* a);  // csrc/noise_prep.hip
+int64_t wj_conv0_ln_bwd_ws_bytes(const wj_conv0_ln_bwd_args* a);    // csrc/conv_ln.hip
 
 extern "C" int64_t wj_workspace_bytes(const char* fn, const void* args) {
     if (!fn || !args) return -1;
@@ -646,7 +648,13 @@ extern "C" int64_t wj_workspace_bytes(const char* fn, const void* args) {
     if (!strcmp(fn, "wj_mse_groups")) return wj_mse_groups_ws_bytes((const wj_mse_groups_args*)args);
     if (!strcmp(fn, "wj_audio_prepare")) return wj_audio_prepare_ws_bytes((const wj_audio_prepare_args*)args);
     if (!strcmp(fn, "wj_noise_prepare")) return wj_noise_prepare_ws_bytes((const wj_noise_prepare_args*)args);
-    static const char* const none[] = {"wj_layernorm_fwd", "wj_layernorm_pre_fwd", "wj_colsum_f32", "wj_attn_fwd", "wj_gelu_bwd_bf16",
+    if (!strcmp(fn, "wj_conv0_ln_gelu_bwd")) return wj_conv0_ln_bwd_ws_bytes((const wj_conv0_ln_bwd_args*)args);
+    if (!strcmp(fn, "wj_conv_ln_gelu_bwd")) {                     // its partial rows [rows][3][C]
+        const wj_conv_ln_bwd_args* a = (const wj_conv_ln_bwd_args*)args;
+        const int rows = wj_conv_ln_bwd_partial_rows(a->rows ? a->n_rows : a->M, a->C);
+        return rows < 0 ? -1 : (int64_t)rows * 3 * a->C * 4;
+    }
+    static const char* const none[] = {"wj_conv_ln_gelu_fwd", "wj_conv0_ln_gelu_fwd", "wj_layernorm_fwd", "wj_layernorm_pre_fwd", "wj_colsum_f32", "wj_attn_fwd", "wj_gelu_bwd_bf16",
         "wj_conv_weight_layout", "wj_add_pos", "wj_mask_gather_rows", "wj_mask_scatter_fill_pos",
         "wj_unmask_rows_f32", "wj_instnorm_accumulate", "wj_instnorm_mean", "wj_ema_update", "wj_adamw_step", "wj_cast_f32_to_bf16",
         "wj_crop_normalize_bf16", "wj_zero_rows", "wj_spin", "wj_gemm_mxfp8", "wj_quantize_mxfp8", "wj_resample_fir", "wj_transpose_bf16", "wj_colsum_f32_group", "wj_rccl_bucket_allreduce_launch", "wj_rccl_bucket_allreduce_wait", "wj_collective_footprint"};

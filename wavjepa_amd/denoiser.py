@@ -112,6 +112,9 @@ class Denoiser(_ModuleBase):
                                      nr_samples_per_audio=nr_samples_per_audio, size=size, alpha=alpha)
             self.global_step = 0
             self.trainer = _NullTrainer()
+        if getattr(feature_extractor, "mode", "default") != "default" or getattr(feature_extractor, "conv_bias", False):
+            raise NotImplementedError("the Denoiser stage runs the default conv front-end only (mode='default', conv_bias=False); "
+                                      "mode='layer_norm' is a JEPA pre-training option")
         self.extract_audio = feature_extractor
         self.feature_norms = nn.LayerNorm(self.extract_audio.embedding_dim)
         enc_l, enc_c = dict(transformer_encoder_layers_cfg), dict(transformer_encoder_cfg)

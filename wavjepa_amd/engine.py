@@ -51,6 +51,8 @@ class EngineConfig:
     norm_eps: float = 1e-5  # feature_norms / final norms (nn.LayerNorm default)
     norm_first_enc: bool = False   # pre-norm layers x = x + branch(LN(x)) in the student AND the teacher (nn.TransformerEncoderLayer norm_first)
     norm_first_dec: bool = False   # ... in the predictor
+    conv_mode: str = "default"     # "default": GroupNorm on conv layer 0 only; "layer_norm": LayerNorm over channels behind EVERY conv layer
+    conv_bias: bool = False        # conv layers carry a bias (mode "layer_norm" only)
 
 
 @dataclass
@@ -327,6 +329,14 @@ class JepaEngine:
         assert len(self.stacks) in (1, self.S)
         self.C = cfg.conv_spec[-1][0]
         assert all(c == self.C for c, _, _ in cfg.conv_spec), "all conv layers must have the same width"
+        if cfg.conv_mode not in ("default", "layer_norm"):
+            raise ValueError(f"conv_mode must be 'default' or 'layer_norm', not {cfg.conv_mode!r}")
+        # mode="layer_norm": Conv1d(+bias) -> LayerNorm over channels -> GELU in every conv layer (csrc/conv_ln.hip)
+        self.conv_ln = cfg.conv_mode == "layer_norm"
+        if cfg.conv_bias and not self.conv_ln:
+            raise NotImplementedError("conv_bias=True needs mode='layer_norm': the GroupNorm front-end's kernels carry no conv bias")
+        if self.conv_ln and self.C not in (64, 128, 256, 512):
+            raise NotImplementedError(f"mode='layer_norm' runs conv widths 64 / 128 / 256 / 512, not {self.C}")
         assert cfg.d_enc % cfg.h_enc == 0 and cfg.d_dec % cfg.h_dec == 0
         self.N = 0
         self.G = 0              # target groups per clip of the arena (taken from the mask plan)
@@ -515,6 +525,8 @@ class JepaEngine:
     def _check_fp8(self) -> None:
         if self.fp8 and (self.cfg.norm_first_enc or self.cfg.norm_first_dec):
             raise RuntimeError("fp8 mode (WJ_FP8=1 / engine.fp8) covers post-norm stacks only: a norm_first=True stack runs in bf16")
+        if self.fp8 and self.cfg.conv_mode == "layer_norm":
+            raise RuntimeError("fp8 mode (WJ_FP8=1 / engine.fp8) is not combined with the mode='layer_norm' conv front-end")
 
     def _fp8_weights(self) -> None:
         """(Re-)quantise the forward weights of the transformer stacks from their bf16 shadows (once per step in fp8 mode)."""
@@ -663,13 +675,19 @@ class JepaEngine:
             # zero-filled ONCE; the library keeps its flags at zero between launches.  Sized for the largest problem that splits.
             self.pair_ws = torch.zeros(ops.workspace_bytes("wj_gemm_bf16", M=256 * (self.PAIR_TILES[1] // 2), N=512, K=2048, lda=2048, ldb=2048,
                                                            ldc=512, epilogue=ops.EPI_BF16), dtype=torch.uint8, device=dev)
-        self.gn_stats = _empty(2, Nc, C, dtype=f32, device=dev)
         taps = c.in_channels * c.conv_spec[0][1]
         conv0_dims = dict(N=N, C_in=c.in_channels, C=C, k=c.conv_spec[0][1], L_out=self.L[0])      # per stream: N clips a call
-        self.gn_ws = _empty(ops.workspace_bytes("wj_conv0_gn_gelu_fwd", **conv0_dims) // 4, dtype=f32, device=dev)
-        self.gn_ws_b = _empty(ops.workspace_bytes("wj_conv0_gn_gelu_bwd", max_rows=0, **conv0_dims) // 4, dtype=f32, device=dev) if train else None
-        self.gn_yx = _empty(Nc, C, taps, dtype=f32, device=dev) if train else None     # forward sums the backward needs
-        self.gn_x1 = _empty(Nc, taps, dtype=f32, device=dev) if train else None
+        if self.conv_ln:
+            # per-row LayerNorm statistics of every conv layer; layer 0's backward scratch (dense form: the largest)
+            self.cl_mean = [_empty(Nc * self.P[l], dtype=f32, device=dev) for l in range(nl)]
+            self.cl_rstd = [_empty(Nc * self.P[l], dtype=f32, device=dev) for l in range(nl)]
+            self.cl_ws_b = _empty(ops.workspace_bytes("wj_conv0_ln_gelu_bwd", max_rows=0, **conv0_dims) // 4, dtype=f32, device=dev) if train else None
+        else:
+            self.gn_stats = _empty(2, Nc, C, dtype=f32, device=dev)
+            self.gn_ws = _empty(ops.workspace_bytes("wj_conv0_gn_gelu_fwd", **conv0_dims) // 4, dtype=f32, device=dev)
+            self.gn_ws_b = _empty(ops.workspace_bytes("wj_conv0_gn_gelu_bwd", max_rows=0, **conv0_dims) // 4, dtype=f32, device=dev) if train else None
+            self.gn_yx = _empty(Nc, C, taps, dtype=f32, device=dev) if train else None     # forward sums the backward needs
+            self.gn_x1 = _empty(Nc, taps, dtype=f32, device=dev) if train else None
         self.fn_b = _empty(M, C, dtype=bf, device=dev)
         self.fn_mean = _empty(M, dtype=f32, device=dev)
         self.fn_rstd = _empty(M, dtype=f32, device=dev)
@@ -1272,6 +1290,55 @@ class JepaEngine:
     def _frontend(self, audio: torch.Tensor) -> None:
         """audio bf16 [N, C_in, L] -> lf (fp32) / lf_b (bf16) [N*T, d_enc]   (reference jepa.py:391-396)"""
         c, f, N, C, S = self.cfg, self.flat, self.N, self.C, self.S
+        if self.conv_ln:
+            self._conv_stack_ln(audio)
+        else:
+            self._conv_stack_gn(audio)
+        M, T = self.M, self.T
+        ops.layernorm_fwd(self.post_ptr[-1], f.ptr32("feature_norms.weight"), f.ptr32("feature_norms.bias"), M=M, D=C,
+                          eps=c.norm_eps, y_bf16=self.fn_b, mean=self.fn_mean, rstd=self.fn_rstd, x_is_bf16=True,
+                          in_seg=self.P[-1], in_valid=self.Tc, in_chan=S if S > 1 else 0)
+        if self.has_mapper and self.fuse_add_pos and c.d_enc % 256 == 0 and C % 128 == 0:
+            # mapper + positions in one launch (SURVEY K8 + K9): the position add rides in the GEMM's epilogue
+            ops.gemm(self.fn_b, f.ptr16("post_extraction_mapper.weight"), self.lf_b, C2=self.lf, M=M, N=c.d_enc, K=C, lda=C, ldb=C,
+                     ldc=c.d_enc, bias=f.ptr32("post_extraction_mapper.bias"), epilogue=ops.EPI_BF16_ADD_POS, aux=self.pos_enc, seg_rows=T)
+            return
+        if self.has_mapper:
+            ops.gemm(self.fn_b, f.ptr16("post_extraction_mapper.weight"), self.map_b, M=M, N=c.d_enc, K=C, lda=C, ldb=C,
+                     ldc=c.d_enc, bias=f.ptr32("post_extraction_mapper.bias"))
+            src = self.map_b
+        else:
+            src = self.fn_b
+        ops.add_pos(src, self.pos_enc, M=M, T=T, D=c.d_enc, y_f32=self.lf, y_bf16=self.lf_b)
+
+    def _conv_stack_ln(self, audio: torch.Tensor) -> None:
+        """mode="layer_norm": the fused layer-0 kernel, then per layer the conv GEMM (bf16 pre-activations, + bias) and one
+        LayerNorm + GELU pass over its rows -> post[l] (bf16, clip padding rows 0); per-row mean / rstd kept for the backward."""
+        c, f, N, C, S = self.cfg, self.flat, self.N, self.C, self.S
+        _, k0, s0 = c.conv_spec[0]
+        audio_p = audio.data_ptr()
+        bias = (lambda pre, l: f.ptr32(f"{pre}{l}.0.bias")) if c.conv_bias else (lambda pre, l: None)
+        for ch in range(S):
+            pre = self.stacks[min(ch, len(self.stacks) - 1)]
+            r0 = ch * N * self.P[0]
+            ops.conv0_ln_fwd(audio_p + ch * c.n_samples * 2 if S > 1 else audio, f.ptr16(f"{pre}0.0.weight"), bias(pre, 0),
+                             f.ptr32(f"{pre}0.2.1.weight"), f.ptr32(f"{pre}0.2.1.bias"), self.post_ptr[0] + r0 * C * 2, self.cl_mean[0][r0:],
+                             self.cl_rstd[0][r0:], N=N, C_in=c.in_channels, L=c.n_samples, C=C, k=k0, stride=s0, L_out=self.L[0], P=self.P[0],
+                             audio_clip_stride=S * c.in_channels * c.n_samples if S > 1 else 0)
+        self._conv_weight_layouts()
+        for l in range(1, len(c.conv_spec)):
+            _, k, s = c.conv_spec[l]
+            for si, c0, nclips in self._stack_groups():
+                pre, r0, rows = self.stacks[si], c0 * self.P[l], nclips * self.P[l]
+                ops.gemm(self.post_ptr[l - 1] + c0 * self.P[l - 1] * C * 2, self._conv_w[f"{si}:wp{l}"], self.pre_ptr[l] + r0 * C * 2,
+                         M=rows, N=C, K=k * C, lda=s * C, ldb=k * C, ldc=C, bias=bias(pre, l), epilogue=ops.EPI_BF16)
+                ops.conv_ln_gelu_fwd(self.pre_ptr[l] + r0 * C * 2, f.ptr32(f"{pre}{l}.2.1.weight"), f.ptr32(f"{pre}{l}.2.1.bias"),
+                                     self.post_ptr[l] + r0 * C * 2, M=rows, C=C, mean=self.cl_mean[l][r0:], rstd=self.cl_rstd[l][r0:],
+                                     seg_rows=self.P[l], seg_valid=self.L[l])
+
+    def _conv_stack_gn(self, audio: torch.Tensor) -> None:
+        """mode="default": conv0 + GroupNorm + GELU, then one implicit GEMM with the fused GELU epilogue per layer."""
+        c, f, N, C, S = self.cfg, self.flat, self.N, self.C, self.S
         _, k0, s0 = c.conv_spec[0]
         taps = c.in_channels * k0
         grad = torch.is_grad_enabled() and self.gn_yx is not None      # (an inference arena keeps no backward sums)
@@ -1295,22 +1362,6 @@ class JepaEngine:
         for l in range(1, len(c.conv_spec)):
             for si, c0, nclips in self._stack_groups():
                 conv_layer(l, si, c0, nclips)
-        M, T = self.M, self.T
-        ops.layernorm_fwd(self.post_ptr[-1], f.ptr32("feature_norms.weight"), f.ptr32("feature_norms.bias"), M=M, D=C,
-                          eps=c.norm_eps, y_bf16=self.fn_b, mean=self.fn_mean, rstd=self.fn_rstd, x_is_bf16=True,
-                          in_seg=self.P[-1], in_valid=self.Tc, in_chan=S if S > 1 else 0)
-        if self.has_mapper and self.fuse_add_pos and c.d_enc % 256 == 0 and C % 128 == 0:
-            # mapper + positions in one launch (SURVEY K8 + K9): the position add rides in the GEMM's epilogue
-            ops.gemm(self.fn_b, f.ptr16("post_extraction_mapper.weight"), self.lf_b, C2=self.lf, M=M, N=c.d_enc, K=C, lda=C, ldb=C,
-                     ldc=c.d_enc, bias=f.ptr32("post_extraction_mapper.bias"), epilogue=ops.EPI_BF16_ADD_POS, aux=self.pos_enc, seg_rows=T)
-            return
-        if self.has_mapper:
-            ops.gemm(self.fn_b, f.ptr16("post_extraction_mapper.weight"), self.map_b, M=M, N=c.d_enc, K=C, lda=C, ldb=C,
-                     ldc=c.d_enc, bias=f.ptr32("post_extraction_mapper.bias"))
-            src = self.map_b
-        else:
-            src = self.fn_b
-        ops.add_pos(src, self.pos_enc, M=M, T=T, D=c.d_enc, y_f32=self.lf, y_bf16=self.lf_b)
 
     # ------------------------------------------------------------------------------------------------ forward
     def forward(self, audio: torch.Tensor, plan: MaskPlan) -> None:
@@ -1587,6 +1638,10 @@ class JepaEngine:
             self._conv_grads_dirty = True
         groups = self._stack_groups()        # (stack, first conv clip, clips): one group, or one per channel stream
         side_wgrad = sparse and self.use_side and self.conv_wgrad_side
+        ln = self.conv_ln
+        # mode="layer_norm": the LayerNorm sits between GELU' and the convolution, so GELU' cannot ride in the dgrad epilogue: plain dgrads
+        # into d(post[l - 1]) and one wj_conv_ln_gelu_bwd per layer where the default mode runs wj_gelu_bwd_bf16
+        fuse_gelu = self.fuse_conv_gelu_bwd and not ln
         late_clear = []
         for l in range(nl - 1, 0, -1):
             _, k, s = c.conv_spec[l]
@@ -1604,7 +1659,9 @@ class JepaEngine:
                     # the rows written this step (they are cleared again below), so the dgrad taps may read neighbours freely.
                     # The lists hold rows of the WHOLE buffer; a group takes its contiguous slice of them.
                     act, n_act, ext, n_ext = act_rows[l][gi]
-                    if not (self.fuse_conv_gelu_bwd and l < nl - 1):
+                    if ln:
+                        self._conv_ln_bwd(l, si, 0, self.N * S * self.P[l], rows=act, n_rows=n_act, clear_dpost=l < nl - 1)
+                    elif not (fuse_gelu and l < nl - 1):
                         # (layers below the top one: d(pre) was written by the dgrad of the layer above, GELU' fused in its epilogue)
                         ops.gelu_bwd_bf16(self.dpost_ptr[l], self.pre_ptr[l], self.dpre_ptr[l], 0, rows=act, n_rows=n_act, row_elems=C,
                                           clear_dpost=l < nl - 1)
@@ -1622,7 +1679,10 @@ class JepaEngine:
                         ops.gemm(self.dpre_ptr[l], self.post_ptr[l - 1], dwp, M=C, N=k * C, K=n_act, lda=C, ldb=s * C, ldc=k * C, a_trans=1,
                                  b_trans=1, epilogue=ops.EPI_ATOMIC_F32, split_k=ops.pick_split_k(C, k * C, n_act), rowmap=act, **self._det_kw())
                 else:
-                    ops.gelu_bwd_bf16(self.dpost_ptr[l] + r0, self.pre_ptr[l] + r0, self.dpre_ptr[l] + r0, rows * C)
+                    if ln:
+                        self._conv_ln_bwd(l, si, c0 * self.P[l], rows)
+                    else:
+                        ops.gelu_bwd_bf16(self.dpost_ptr[l] + r0, self.pre_ptr[l] + r0, self.dpre_ptr[l] + r0, rows * C)
                     ops.gemm(self.dpre_ptr[l] + r0, self.post_ptr[l - 1] + r0p, dwp, M=C, N=k * C, K=rows, lda=C, ldb=s * C, ldc=k * C,
                              a_trans=1, b_trans=1, epilogue=ops.EPI_ATOMIC_F32, split_k=ops.pick_split_k(C, k * C, rows), **self._det_kw())
                 if not side_wgrad:
@@ -1632,7 +1692,7 @@ class JepaEngine:
                     if U == 0:
                         continue
                     if sparse:
-                        if n_ext > 0 and self.fuse_conv_gelu_bwd and l - 1 >= 1:
+                        if n_ext > 0 and fuse_gelu and l - 1 >= 1:
                             # the rows this GEMM writes (s g + rho, g in ext) are exactly act[l - 1]: d(pre[l - 1]) = bf16(d(post)) * gelu'(pre)
                             # straight from its epilogue -- the bits a bf16 d(post) tensor + wj_gelu_bwd_bf16 over act[l - 1] would give
                             ops.gemm(self.dpre_ptr[l] - (U - 1) * C * 2, self._conv_w[f"{si}:wd{l}_{rho}"], self.dpre_ptr[l - 1] + rho * C * 2,
@@ -1657,6 +1717,18 @@ class JepaEngine:
             if sparse:
                 rows0, n0, off0, max0 = act_rows[0][ch]
                 lists = dict(rows=rows0, row_off=off0, max_rows=max0)
+            if ln:
+                r0 = c0 * self.P[0]
+                bias = c.conv_bias
+                ops.conv0_ln_bwd(audio_p + ch * c.n_samples * 2 if S > 1 else self.audio, f.ptr16(f"{pre}0.0.weight"),
+                                 f.ptr32(f"{pre}0.0.bias") if bias else None, f.ptr32(f"{pre}0.2.1.weight"), f.ptr32(f"{pre}0.2.1.bias"),
+                                 self.cl_mean[0][r0:], self.cl_rstd[0][r0:], self.dpost_ptr[0] + r0 * C * 2, f.gptr(f"{pre}0.0.weight"),
+                                 f.gptr(f"{pre}0.0.bias") if bias else None, f.gptr(f"{pre}0.2.1.weight"), f.gptr(f"{pre}0.2.1.bias"),
+                                 self.cl_ws_b, N=N, C_in=c.in_channels, L=c.n_samples, C=C, k=k0, stride=s0, L_out=self.L[0], P=self.P[0],
+                                 audio_clip_stride=S * c.in_channels * c.n_samples if S > 1 else 0, **lists)
+                if sparse:
+                    ops.zero_rows(self.dpost_ptr[0] + r0 * C * 2, rows0, n_rows=n0, row_bytes=C * 2)
+                continue
             ops.conv0_bwd(audio_p + ch * c.n_samples * 2 if S > 1 else self.audio, f.ptr16(f"{pre}0.0.weight"), f.ptr32(f"{pre}0.2.weight"),
                           f.ptr32(f"{pre}0.2.bias"), self.gn_stats[0, c0:], self.gn_stats[1, c0:], self.dpost_ptr[0] + c0 * self.P[0] * C * 2,
                           f.gptr(f"{pre}0.0.weight"), f.gptr(f"{pre}0.2.weight"), f.gptr(f"{pre}0.2.bias"), self.gn_ws_b,
@@ -1668,6 +1740,23 @@ class JepaEngine:
             self._join_side()                # the side stream's conv weight gradients have read d(pre[l]): clear the rows now
             for ptr, act, n_act in late_clear:
                 ops.zero_rows(ptr, act, n_rows=n_act, row_bytes=C * 2)
+
+    def _conv_ln_bwd(self, l: int, si: int, row0: int, M: int, rows=None, n_rows: int = 0, clear_dpost: bool = False) -> None:
+        """wj_conv_ln_gelu_bwd of conv layer l >= 1 over the M rows from row `row0` of the layer's buffers (listed form: `rows` index
+        those M rows); its dgamma | dbeta | dbias partial rows take the fold forms of _ln_bwd."""
+        f, C, pre = self.flat, self.C, self.stacks[si]
+        off = row0 * C * 2
+        dg, db = f.gptr(f"{pre}{l}.2.1.weight"), f.gptr(f"{pre}{l}.2.1.bias")
+        dbias = f.gptr(f"{pre}{l}.0.bias") if self.cfg.conv_bias else None
+        args = (self.dpost_ptr[l] + off, self.pre_ptr[l] + off, self.cl_mean[l][row0:], self.cl_rstd[l][row0:], f.ptr32(f"{pre}{l}.2.1.weight"),
+                f.ptr32(f"{pre}{l}.2.1.bias"), self.dpre_ptr[l] + off)
+        kw = dict(M=M, C=C, seg_rows=self.P[l], seg_valid=self.L[l], rows=rows, n_rows=n_rows, clear_dpost=clear_dpost)
+        form, ws = self._fold_form(3 * C, True)
+        if form == "slot":
+            ops.conv_ln_gelu_bwd(*args, ws, **kw)
+            self._fold(form, ws, 3 * C, ops.conv_ln_bwd_partial_rows(n_rows if rows is not None else M, C), dg, db, dbias, C)
+        else:                                # the entry folds its partial rows itself (in order when deterministic)
+            ops.conv_ln_gelu_bwd(*args, self.red_ws, dgamma=dg, dbeta=db, dbias=dbias, deterministic=self.deterministic, **kw)
 
     def _conv_rows(self, plan: MaskPlan):
         """Device copies of conv_active_rows for this plan (cached on the plan: mask sets are reused by the data source).

@@ -15,6 +15,7 @@ import torch
 from torch import nn
 
 from .audio_extractor import Extractor
+from .audio_feature_extractor import check_conv_options, conv_block
 
 
 class ConvChannelFeatureExtractor(Extractor, nn.Module):
@@ -22,14 +23,10 @@ class ConvChannelFeatureExtractor(Extractor, nn.Module):
                  mode: str = "default", conv_bias: bool = False, depthwise: bool = False, share_weights_over_channels: bool = False,
                  **kwargs):
         nn.Module.__init__(self)
-        if mode != "default":
-            raise NotImplementedError("only mode='default' (GroupNorm on layer 0) is on the accelerated path")
-        if conv_bias or dropout != 0.0:
-            raise NotImplementedError("conv_bias / dropout are not used by the WavJEPA configs")
         # depthwise: every stack starts from ONE input channel, so groups = n_in is a plain convolution in layer 0; deeper layers
         # (groups = dim) would be true depthwise convolutions, which no WavJEPA config selects
-        if depthwise:
-            raise NotImplementedError("depthwise conv stacks are not on the accelerated path")
+        check_conv_options(mode, conv_bias, depthwise, dropout)
+        self.mode, self.conv_bias = mode, bool(conv_bias)         # one setting for every channel's stack
         self.in_channels = int(in_channels)
         self.depthwise = depthwise
         self.conv_layers_spec = [tuple(int(v) for v in cl) for cl in conv_layers_spec]
@@ -38,12 +35,7 @@ class ConvChannelFeatureExtractor(Extractor, nn.Module):
         for _ in range(1 if self.weight_sharing else self.in_channels):
             layers, c_in = [], 1
             for i, (dim, k, stride) in enumerate(self.conv_layers_spec):
-                conv = nn.Conv1d(c_in, dim, k, stride=stride, bias=False)
-                nn.init.kaiming_normal_(conv.weight)
-                if i == 0:
-                    layers.append(nn.Sequential(conv, nn.Dropout(p=0.0), nn.GroupNorm(dim, dim, affine=True), nn.GELU()))
-                else:
-                    layers.append(nn.Sequential(conv, nn.Dropout(p=0.0), nn.GELU()))
+                layers.append(conv_block(c_in, dim, k, stride, mode, self.conv_bias, first=i == 0))
                 c_in = dim
             self.cnns.append(nn.Sequential(*layers))
         self.embedding_dim = self.conv_layers_spec[-1][0]

@@ -427,7 +427,8 @@ class JEPA(_ModuleBase):
                            d_enc=self.encoder_embedding_dim, h_enc=self.n_encoder_heads, l_enc=self.encoder.num_layers,
                            d_dec=self.decoder_embedding_dim, h_dec=self.n_decoder_heads, l_dec=self.decoder.num_layers,
                            top_k=int(self.hparams.average_top_k_layers), ln_eps=self.encoder.layer_norm_eps,
-                           norm_first_enc=self.encoder.norm_first, norm_first_dec=self.decoder.norm_first)
+                           norm_first_enc=self.encoder.norm_first, norm_first_dec=self.decoder.norm_first,
+                           conv_mode=getattr(ext, "mode", "default"), conv_bias=bool(getattr(ext, "conv_bias", False)))
         self._engine = JepaEngine(cfg, self._flat, self.pos_encoding_encoder.data, self.pos_encoding_decoder.data)
         self._anchor = torch.zeros(1, device=self.device, requires_grad=True)
         self._student_bf16_fresh = False

@@ -113,7 +113,8 @@ def workspace_bytes(fn: str, **dims) -> int:
     struct_name = {"wj_gemm_bf16": "wj_gemm_args", "wj_colsum_bf16": "wj_colsum_args", "wj_mask_scatter_fill_pos_bwd": "wj_scatter_fill_bwd_args", "wj_layernorm_bwd": "wj_ln_bwd_args", "wj_layernorm_pre_bwd": "wj_ln_pre_bwd_args", "wj_attn_bwd": "wj_attn_bwd_args", "wj_conv0_gn_gelu_fwd": "wj_conv0_fwd_args",
                    "wj_conv0_gn_gelu_bwd": "wj_conv0_bwd_args", "wj_masked_mse": "wj_mse_args", "wj_grad_sumsq": "wj_sumsq_args",
                    "wj_rir_convolve": "wj_rir_conv_args", "wj_snr_mix": "wj_snr_mix_args", "wj_mse_groups": "wj_mse_groups_args",
-                   "wj_audio_prepare": "wj_audio_prepare_args", "wj_noise_prepare": "wj_noise_prepare_args"}[fn]
+                   "wj_audio_prepare": "wj_audio_prepare_args", "wj_noise_prepare": "wj_noise_prepare_args",
+                   "wj_conv_ln_gelu_bwd": "wj_conv_ln_bwd_args", "wj_conv0_ln_gelu_bwd": "wj_conv0_ln_bwd_args"}[fn]
     a = STRUCTS[struct_name]()
     for k, v in dims.items():
         setattr(a, k, v)
@@ -401,6 +402,47 @@ def gelu_bwd_bf16(dpost: Ptr, pre: Ptr, dpre: Ptr, n: int, *, rows: Ptr = None, 
     """rows (int32 [n_rows]) selects the listed-rows form over [.][row_elems] matrices."""
     _run("wj_gelu_bwd_bf16", "wj_gelu_bwd_args", stream, dpost=_p(dpost), pre=_p(pre), dpre=_p(dpre), rows=_p(rows), n=n,
          n_rows=n_rows, row_elems=row_elems, clear_dpost=int(clear_dpost))
+
+
+# ---- mode="layer_norm": every conv layer is Conv1d(+bias) -> LayerNorm over channels -> GELU (csrc/conv_ln.hip)
+def conv_ln_gelu_fwd(pre: Ptr, gamma: Ptr, beta: Ptr, post: Ptr, *, M: int, C: int, mean: Ptr = None, rstd: Ptr = None, seg_rows: int = 0,
+                     seg_valid: int = 0, eps: float = 1e-5, stream: Optional[int] = None) -> None:
+    """post = bf16(gelu(LN(pre) * gamma + beta)) over the rows of a conv GEMM's bf16 output; clip padding rows are written as 0."""
+    _run("wj_conv_ln_gelu_fwd", "wj_conv_ln_fwd_args", stream, pre=_p(pre), gamma=_p(gamma), beta=_p(beta), post=_p(post), mean=_p(mean),
+         rstd=_p(rstd), M=M, C=C, seg_rows=seg_rows, seg_valid=seg_valid, eps=eps)
+
+
+def conv_ln_gelu_bwd(dpost: Ptr, pre: Ptr, mean: Ptr, rstd: Ptr, gamma: Ptr, beta: Ptr, dpre: Ptr, workspace: Ptr, *, M: int, C: int,
+                     seg_rows: int = 0, seg_valid: int = 0, rows: Ptr = None, n_rows: int = 0, clear_dpost: bool = False,
+                     dgamma: Ptr = None, dbeta: Ptr = None, dbias: Ptr = None, deterministic: bool = False,
+                     stream: Optional[int] = None) -> None:
+    """dpre = bf16(LN'(dpost * gelu'(z))); rows (int32 [n_rows]) selects the listed-rows form.  workspace: conv_ln_bwd_partial_rows rows
+    of [3][C] partials (dgamma | dbeta | dbias), folded by the call itself when a gradient output is given."""
+    _run("wj_conv_ln_gelu_bwd", "wj_conv_ln_bwd_args", stream, dpost=_p(dpost), pre=_p(pre), mean=_p(mean), rstd=_p(rstd), gamma=_p(gamma),
+         beta=_p(beta), dpre=_p(dpre), rows=_p(rows), workspace=_p(workspace), dgamma=_p(dgamma), dbeta=_p(dbeta), dbias=_p(dbias), M=M, C=C,
+         seg_rows=seg_rows, seg_valid=seg_valid, n_rows=n_rows, clear_dpost=int(clear_dpost), deterministic=int(deterministic))
+
+
+def conv_ln_bwd_partial_rows(rows: int, C: int) -> int:
+    """Partial rows conv_ln_gelu_bwd leaves in its workspace ([rows][3][C]) for `rows` processed rows of width C."""
+    return int(_abi.load().wj_conv_ln_bwd_partial_rows(int(rows), int(C)))
+
+
+def conv0_ln_fwd(audio: Ptr, w: Ptr, bias: Ptr, gamma: Ptr, beta: Ptr, act: Ptr, mean: Ptr, rstd: Ptr, *, N: int, C_in: int, L: int, C: int,
+                 k: int, stride: int, L_out: int, P: int, eps: float = 1e-5, audio_clip_stride: int = 0, stream: Optional[int] = None) -> None:
+    _run("wj_conv0_ln_gelu_fwd", "wj_conv0_ln_fwd_args", stream, audio=_p(audio), w=_p(w), bias=_p(bias), gamma=_p(gamma), beta=_p(beta),
+         act=_p(act), mean=_p(mean), rstd=_p(rstd), N=N, C_in=C_in, L=L, C=C, k=k, stride=stride, L_out=L_out, P=P, eps=eps,
+         audio_clip_stride=audio_clip_stride)
+
+
+def conv0_ln_bwd(audio: Ptr, w: Ptr, bias: Ptr, gamma: Ptr, beta: Ptr, mean: Ptr, rstd: Ptr, dact: Ptr, dw: Ptr, dbias: Ptr, dgamma: Ptr,
+                 dbeta: Ptr, workspace: Ptr, *, N: int, C_in: int, L: int, C: int, k: int, stride: int, L_out: int, P: int, rows: Ptr = None,
+                 row_off: Ptr = None, max_rows: int = 0, audio_clip_stride: int = 0, stream: Optional[int] = None) -> None:
+    """rows / row_off / max_rows: read the output gradient on the listed rows only (see include/wavjepa_hip.h)."""
+    _run("wj_conv0_ln_gelu_bwd", "wj_conv0_ln_bwd_args", stream, audio=_p(audio), w=_p(w), bias=_p(bias), gamma=_p(gamma), beta=_p(beta),
+         mean=_p(mean), rstd=_p(rstd), dact=_p(dact), rows=_p(rows), row_off=_p(row_off), dw=_p(dw), dbias=_p(dbias), dgamma=_p(dgamma),
+         dbeta=_p(dbeta), workspace=_p(workspace), N=N, C_in=C_in, L=L, C=C, k=k, stride=stride, L_out=L_out, P=P, max_rows=max_rows,
+         audio_clip_stride=audio_clip_stride)
 
 
 def spin(ticks: int, stream: Optional[int] = None) -> None:
