@@ -383,6 +383,20 @@ typedef struct {
 } wj_attn_bwd_args;
 int wj_attn_bwd(const wj_attn_bwd_args*, void* stream);
 
+/* Block-streamed attention for sequences of up to 1024 tokens (csrc/attention_stream.hip): the SAME argument structs and the same
+ * semantics as wj_attn_fwd / wj_attn_bwd above -- packed q|k|v, the three forms (no mask, key mask with mask_group, ragged through
+ * seq_off), lse [B][H][T] or [rows][H], out = 0 / lse = +inf / dq = 0 for a query row with no attended key, dk = dv = 0 exactly for
+ * masked keys, masked and padding keys removed inside the exponent, dbias / dbias_ws ([B][3*H*hd], one row per sequence) / defer_fold.
+ * K / V (backward: also Q / dO) pass through LDS in blocks of 128 rows, so LDS per workgroup does not depend on T.
+ * hd in {32, 64} (16: WJ_ERR_UNSUPPORTED);  1 <= T <= 1024 (above: WJ_ERR_ARG) -- T <= 416 is accepted on purpose, so that the two
+ * families can be held against each other on the same operands; the engine uses these entries for T > 416 only.
+ * The forward takes two passes over the keys (row maximum and sum, then P = exp(s - m) / sum rounded to bf16 after the normalisation),
+ * so its rounding points are those of wj_attn_fwd.  The backward has one owner per dqkv row (no atomics: dqkv is bit-identical from
+ * launch to launch) and adds the dbias column sums in wave order in BOTH modes; `deterministic` selects the ordered fold into dbias.
+ * Every argument error is answered before a launch.  wj_workspace_bytes("wj_attn_stream_bwd") = the dbias_ws bytes. */
+int wj_attn_stream_fwd(const wj_attn_fwd_args*, void* stream);
+int wj_attn_stream_bwd(const wj_attn_bwd_args*, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Conv layer 0 (C_in x k x stride, no bias) + GroupNorm(C, C) + erf-GELU, channels-last output.
  * Replaces cnn[0] = Conv1d -> Dropout(0) -> GroupNorm(dim, dim) -> GELU (audio_feature_extractor.py:90-96).

@@ -632,7 +632,7 @@ extern "C" int64_t wj_workspace_bytes(const char* fn, const void* args) {
     }
     if (!strcmp(fn, "wj_layernorm_bwd")) return 1536LL * 3 * ((const wj_ln_bwd_args*)args)->D * 4;
     if (!strcmp(fn, "wj_layernorm_pre_bwd")) return 1536LL * 3 * ((const wj_ln_pre_bwd_args*)args)->D * 4;   // the same grid cap
-    if (!strcmp(fn, "wj_attn_bwd")) {
+    if (!strcmp(fn, "wj_attn_bwd") || !strcmp(fn, "wj_attn_stream_bwd")) {      // dbias_ws: one row per sequence in both families
         const wj_attn_bwd_args* a = (const wj_attn_bwd_args*)args;
         return (int64_t)a->B * 3 * a->H * a->hd * 4;
     }
@@ -654,7 +654,7 @@ extern "C" int64_t wj_workspace_bytes(const char* fn, const void* args) {
         const int rows = wj_conv_ln_bwd_partial_rows(a->rows ? a->n_rows : a->M, a->C);
         return rows < 0 ? -1 : (int64_t)rows * 3 * a->C * 4;
     }
-    static const char* const none[] = {"wj_conv_ln_gelu_fwd", "wj_conv0_ln_gelu_fwd", "wj_layernorm_fwd", "wj_layernorm_pre_fwd", "wj_colsum_f32", "wj_attn_fwd", "wj_gelu_bwd_bf16",
+    static const char* const none[] = {"wj_conv_ln_gelu_fwd", "wj_conv0_ln_gelu_fwd", "wj_layernorm_fwd", "wj_layernorm_pre_fwd", "wj_colsum_f32", "wj_attn_fwd", "wj_attn_stream_fwd", "wj_gelu_bwd_bf16",
         "wj_conv_weight_layout", "wj_add_pos", "wj_mask_gather_rows", "wj_mask_scatter_fill_pos",
         "wj_unmask_rows_f32", "wj_instnorm_accumulate", "wj_instnorm_mean", "wj_ema_update", "wj_adamw_step", "wj_cast_f32_to_bf16",
         "wj_crop_normalize_bf16", "wj_zero_rows", "wj_spin", "wj_gemm_mxfp8", "wj_quantize_mxfp8", "wj_resample_fir", "wj_transpose_bf16", "wj_colsum_f32_group", "wj_rccl_bucket_allreduce_launch", "wj_rccl_bucket_allreduce_wait", "wj_collective_footprint"};

@@ -338,6 +338,14 @@ class JepaEngine:
         if self.conv_ln and self.C not in (64, 128, 256, 512):
             raise NotImplementedError(f"mode='layer_norm' runs conv widths 64 / 128 / 256 / 512, not {self.C}")
         assert cfg.d_enc % cfg.h_enc == 0 and cfg.d_dec % cfg.h_dec == 0
+        # clips of more than 416 tokens run the block-streamed attention kernels (ops.attn_entries), which take 32- and 64-wide heads
+        if self.T > ops.ATTN_STREAM_T_MAX:
+            raise NotImplementedError(f"{self.T} tokens per clip: the attention kernels take at most {ops.ATTN_STREAM_T_MAX}")
+        if self.T > ops.ATTN_WHOLE_T_MAX:
+            for what, hd, layers in (("encoder", cfg.d_enc // cfg.h_enc, cfg.l_enc), ("decoder", cfg.d_dec // cfg.h_dec, cfg.l_dec)):
+                if layers > 0 and hd not in (32, 64):
+                    raise NotImplementedError(f"{self.T} tokens per clip with {hd}-wide {what} heads: attention beyond "
+                                              f"{ops.ATTN_WHOLE_T_MAX} tokens (wj_attn_stream_fwd / _bwd) takes head widths 32 and 64")
         self.N = 0
         self.G = 0              # target groups per clip of the arena (taken from the mask plan)
         # second HIP stream: work that is off the critical path (teacher forward; all weight-gradient GEMMs of the
@@ -776,9 +784,11 @@ class JepaEngine:
         """a.o = attention(a.qkv): packed sequences (`seq`) or T tokens per sequence under a key mask; `save` keeps the softmax statistics."""
         lse = a.lse if save else None
         if seq is not None:
-            ops.attn_fwd(a.qkv, a.o, B=B, T=seq[1], H=H, hd=D // H, seq_off=seq[0], lse=lse)
+            fwd = getattr(ops, ops.attn_entries(seq[1])[0][3:])      # by the length bound of THIS call: a short ragged stack keeps the whole-image kernels
+            fwd(a.qkv, a.o, B=B, T=seq[1], H=H, hd=D // H, seq_off=seq[0], lse=lse)
         else:
-            ops.attn_fwd(a.qkv, a.o, B=B, T=self.T, H=H, hd=D // H, key_mask=mask, lse=lse)
+            fwd = getattr(ops, ops.attn_entries(self.T)[0][3:])
+            fwd(a.qkv, a.o, B=B, T=self.T, H=H, hd=D // H, key_mask=mask, lse=lse)
 
     def _tail_gather(self, a: _Acts, x: torch.Tensor, sub: Tuple[torch.Tensor, torch.Tensor, int], D: int):
         """The `sub` rows of the attention output and of the residual source x: (tail_o, tail_x, the number of rows that go on)."""
@@ -1038,16 +1048,18 @@ class JepaEngine:
             self._fold(form, ws, 3 * D, ops.ln_pre_bwd_partial_rows(M, D), dgamma, dbeta, dbias, D)
 
     def _attn_bwd(self, qkv, out, dout, lse, dqkv, *, B: int, H: int, hd: int, dbias, **kw) -> None:
-        """wj_attn_bwd: the in_proj bias partials go to a slot, or the kernel folds them itself out of red_ws (in order when deterministic)."""
+        """wj_attn_bwd (wj_attn_stream_bwd above 416 tokens, the same arguments and the same [B][3D] partial rows): the in_proj bias partials
+        go to a slot, or the kernel folds them itself out of red_ws (in order when deterministic)."""
         D3 = 3 * H * hd
+        attn_bwd = getattr(ops, ops.attn_entries(kw["T"])[1][3:])
         if self.deterministic:
             kw = dict(kw, deterministic=True)
         form, ws = self._fold_form(D3, bool(dbias))
         if form == "slot":
-            ops.attn_bwd(qkv, out, dout, lse, dqkv, B=B, H=H, hd=hd, dbias=dbias, dbias_ws=ws, defer_fold=True, **kw)
+            attn_bwd(qkv, out, dout, lse, dqkv, B=B, H=H, hd=hd, dbias=dbias, dbias_ws=ws, defer_fold=True, **kw)
             self._fold(form, ws, D3, B, dbias, None, None, D3)
         else:
-            ops.attn_bwd(qkv, out, dout, lse, dqkv, B=B, H=H, hd=hd, dbias=dbias, dbias_ws=self.red_ws, **kw)
+            attn_bwd(qkv, out, dout, lse, dqkv, B=B, H=H, hd=hd, dbias=dbias, dbias_ws=self.red_ws, **kw)
 
     def _wgrad(self, dY, X, gW, n_out: int, k_in: int, m_tok: int) -> None:
         """gW[n_out, k_in] += dY[m_tok, n_out]^T @ X[m_tok, k_in]   (the three mapper weights: nothing on the main chain reads the result, so

@@ -7,7 +7,7 @@ host and nothing falls back to PyTorch ops: a missing library or a non-zero retu
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Union
+from typing import Optional, Tuple, Union
 
 import torch
 
@@ -110,7 +110,7 @@ def require_gpu() -> None:
 
 def workspace_bytes(fn: str, **dims) -> int:
     """Scratch bytes entry point `fn` needs for the given dimensions (fields of its argument struct), from the library."""
-    struct_name = {"wj_gemm_bf16": "wj_gemm_args", "wj_colsum_bf16": "wj_colsum_args", "wj_mask_scatter_fill_pos_bwd": "wj_scatter_fill_bwd_args", "wj_layernorm_bwd": "wj_ln_bwd_args", "wj_layernorm_pre_bwd": "wj_ln_pre_bwd_args", "wj_attn_bwd": "wj_attn_bwd_args", "wj_conv0_gn_gelu_fwd": "wj_conv0_fwd_args",
+    struct_name = {"wj_gemm_bf16": "wj_gemm_args", "wj_colsum_bf16": "wj_colsum_args", "wj_mask_scatter_fill_pos_bwd": "wj_scatter_fill_bwd_args", "wj_layernorm_bwd": "wj_ln_bwd_args", "wj_layernorm_pre_bwd": "wj_ln_pre_bwd_args", "wj_attn_bwd": "wj_attn_bwd_args", "wj_attn_stream_bwd": "wj_attn_bwd_args", "wj_conv0_gn_gelu_fwd": "wj_conv0_fwd_args",
                    "wj_conv0_gn_gelu_bwd": "wj_conv0_bwd_args", "wj_masked_mse": "wj_mse_args", "wj_grad_sumsq": "wj_sumsq_args",
                    "wj_rir_convolve": "wj_rir_conv_args", "wj_snr_mix": "wj_snr_mix_args", "wj_mse_groups": "wj_mse_groups_args",
                    "wj_audio_prepare": "wj_audio_prepare_args", "wj_noise_prepare": "wj_noise_prepare_args",
@@ -373,6 +373,36 @@ def attn_bwd(qkv: Ptr, out: Ptr, dout: Ptr, lse: Ptr, dqkv: Ptr, *, B: int, T: i
              mask_group: int = 1, dbias: Ptr = None, dbias_ws: Ptr = None, seq_off: Ptr = None, defer_fold: bool = False,
              stream: Optional[int] = None, deterministic: bool = False) -> None:
     _run("wj_attn_bwd", "wj_attn_bwd_args", stream, qkv=_p(qkv), key_mask=_p(key_mask), seq_off=_p(seq_off), out=_p(out), dout=_p(dout),
+         lse=_p(lse), dqkv=_p(dqkv), dbias=_p(dbias), dbias_ws=_p(dbias_ws), B=B, T=T, H=H, hd=hd, mask_group=mask_group,
+         defer_fold=int(defer_fold), deterministic=int(deterministic))
+
+
+ATTN_WHOLE_T_MAX = 416     # wj_attn_fwd / wj_attn_bwd keep the whole K / V of a head in LDS: their longest sequence
+ATTN_STREAM_T_MAX = 1024   # wj_attn_stream_fwd / wj_attn_stream_bwd
+
+
+def attn_entries(T: int) -> Tuple[str, str]:
+    """(forward, backward) entry points for sequences of (at most) T tokens: the whole-image kernels up to 416 tokens, exactly as
+    before the streamed ones existed, and the block-streamed kernels above."""
+    if T <= ATTN_WHOLE_T_MAX:
+        return "wj_attn_fwd", "wj_attn_bwd"
+    if T <= ATTN_STREAM_T_MAX:
+        return "wj_attn_stream_fwd", "wj_attn_stream_bwd"
+    raise NotImplementedError(f"attention over {T} tokens: the streamed kernels take at most {ATTN_STREAM_T_MAX}")
+
+
+def attn_stream_fwd(qkv: Ptr, out: Ptr, *, B: int, T: int, H: int, hd: int, key_mask: Ptr = None, lse: Ptr = None,
+                    mask_group: int = 1, seq_off: Ptr = None, stream: Optional[int] = None) -> None:
+    """wj_attn_stream_fwd: attn_fwd's arguments and semantics, K / V streamed through LDS in 128-key blocks; 1 <= T <= 1024, hd 32 / 64."""
+    _run("wj_attn_stream_fwd", "wj_attn_fwd_args", stream, qkv=_p(qkv), key_mask=_p(key_mask), seq_off=_p(seq_off), out=_p(out),
+         lse=_p(lse), B=B, T=T, H=H, hd=hd, mask_group=mask_group)
+
+
+def attn_stream_bwd(qkv: Ptr, out: Ptr, dout: Ptr, lse: Ptr, dqkv: Ptr, *, B: int, T: int, H: int, hd: int, key_mask: Ptr = None,
+                    mask_group: int = 1, dbias: Ptr = None, dbias_ws: Ptr = None, seq_off: Ptr = None, defer_fold: bool = False,
+                    stream: Optional[int] = None, deterministic: bool = False) -> None:
+    """wj_attn_stream_bwd: attn_bwd's arguments and semantics (dbias_ws [B][3*H*hd] as there)."""
+    _run("wj_attn_stream_bwd", "wj_attn_bwd_args", stream, qkv=_p(qkv), key_mask=_p(key_mask), seq_off=_p(seq_off), out=_p(out), dout=_p(dout),
          lse=_p(lse), dqkv=_p(dqkv), dbias=_p(dbias), dbias_ws=_p(dbias_ws), B=B, T=T, H=H, hd=hd, mask_group=mask_group,
          defer_fold=int(defer_fold), deterministic=int(deterministic))
 
