@@ -67,7 +67,8 @@ def fwd_instantiation(f) -> str:
 
 
 def bwd_instantiation(f) -> str:
-    """the kernel wj_attn_bwd launches in the release library (the if-chain of wj_attn_bwd; WJ_ATTN_BWD_FRAG is a laboratory switch)"""
+    """the kernel wj_attn_bwd launches in the release library (the if-chain of launch_bwd, spelled as there without its last argument DET;
+    WJ_ATTN_BWD_FRAG is a laboratory switch)"""
     T, hd = f["T"], f["hd"]
     m = "true" if f["form"] == "mask" else "false"
     if hd == 16:
@@ -75,12 +76,12 @@ def bwd_instantiation(f) -> str:
             return f"attn_bwd_frag_kernel<32, NWB32, 8, {m}, 16>"
         return f"attn_bwd_frag_kernel<32, NWB32, 12, {m}, 16>" if T <= 192 else "attn_bwd_kernel<32, NWB32, 14, 16>"
     if T > 224:
-        return f"attn_bwd_kernel<{hd}, NWB{hd}, 26>"
+        return f"attn_bwd_kernel<{hd}, NWB{hd}, 26, {hd}>"
     if T <= 128:
-        return f"attn_bwd_frag_kernel<{hd}, NWB{hd}, 8, {m}>"
+        return f"attn_bwd_frag_kernel<{hd}, NWB{hd}, 8, {m}, {hd}>"
     if hd == 64:
-        return "attn_bwd_kernel<64, NWB64, 14>"
-    return f"attn_bwd_frag_kernel<32, NWB32, 12, {m}>" if T <= 192 else "attn_bwd_kernel<32, NWB32, 14>"
+        return "attn_bwd_kernel<64, NWB64, 14, 64>"
+    return f"attn_bwd_frag_kernel<32, NWB32, 12, {m}, 32>" if T <= 192 else "attn_bwd_kernel<32, NWB32, 14, 32>"
 
 
 BOUNDARIES = (1, 15, 16, 17, 31, 32, 33, 127, 128, 129, 191, 192, 193, 223, 224, 225, 415, 416)
@@ -95,21 +96,23 @@ BRANCHES = {
     "attn_bwd_frag_kernel<32, NWB32, 8, true, 16>": (16, 1, 128), "attn_bwd_frag_kernel<32, NWB32, 8, false, 16>": (16, 1, 128),
     "attn_bwd_frag_kernel<32, NWB32, 12, true, 16>": (16, 129, 192), "attn_bwd_frag_kernel<32, NWB32, 12, false, 16>": (16, 129, 192),
     "attn_bwd_kernel<32, NWB32, 14, 16>": (16, 193, 224),
-    "attn_bwd_kernel<64, NWB64, 26>": (64, 225, 416), "attn_bwd_kernel<32, NWB32, 26>": (32, 225, 416),
-    "attn_bwd_frag_kernel<64, NWB64, 8, true>": (64, 1, 128), "attn_bwd_frag_kernel<64, NWB64, 8, false>": (64, 1, 128),
-    "attn_bwd_frag_kernel<32, NWB32, 8, true>": (32, 1, 128), "attn_bwd_frag_kernel<32, NWB32, 8, false>": (32, 1, 128),
-    "attn_bwd_kernel<64, NWB64, 14>": (64, 129, 224),
-    "attn_bwd_frag_kernel<32, NWB32, 12, true>": (32, 129, 192), "attn_bwd_frag_kernel<32, NWB32, 12, false>": (32, 129, 192),
-    "attn_bwd_kernel<32, NWB32, 14>": (32, 193, 224),
+    "attn_bwd_kernel<64, NWB64, 26, 64>": (64, 225, 416), "attn_bwd_kernel<32, NWB32, 26, 32>": (32, 225, 416),
+    "attn_bwd_frag_kernel<64, NWB64, 8, true, 64>": (64, 1, 128), "attn_bwd_frag_kernel<64, NWB64, 8, false, 64>": (64, 1, 128),
+    "attn_bwd_frag_kernel<32, NWB32, 8, true, 32>": (32, 1, 128), "attn_bwd_frag_kernel<32, NWB32, 8, false, 32>": (32, 1, 128),
+    "attn_bwd_kernel<64, NWB64, 14, 64>": (64, 129, 224),
+    "attn_bwd_frag_kernel<32, NWB32, 12, true, 32>": (32, 129, 192), "attn_bwd_frag_kernel<32, NWB32, 12, false, 32>": (32, 129, 192),
+    "attn_bwd_kernel<32, NWB32, 14, 32>": (32, 193, 224),
 }
 # reached only with WJ_ATTN_BWD_FRAG = 0 in the laboratory library (the suite loads the release one); their code is the general kernel's,
 # which the T > 128 cases run at 14 and 26 tiles
-LAB_ONLY = {"attn_bwd_kernel<64, NWB64, 8>", "attn_bwd_kernel<32, NWB32, 8>"}
+LAB_ONLY = {"attn_bwd_kernel<64, NWB64, 8, 64>", "attn_bwd_kernel<32, NWB32, 8, 32>"}
 
 
 def test_branch_table_lists_every_launch_of_the_source():
     src = open(os.path.join(ROOT, "wavjepa_amd", "csrc", "attention.hip")).read()
-    launched = set(re.findall(r"hipLaunchKernelGGL\(\((attn_\w+<[^>]*>)\)", src))
+    # launch_bwd is one chain for the default and the deterministic instantiations: every backward launch ends in `, DET>`
+    launched = set(m + ">" for m in re.findall(r"hipLaunchKernelGGL\(\((attn_\w+<[^>]*?)(?:, DET)?>\)", src))
+    assert len(re.findall(r"hipLaunchKernelGGL\(\(attn_bwd\w+<[^>]*, DET>\)", src)) == len(re.findall(r"hipLaunchKernelGGL\(\(attn_bwd", src)) == 17
     assert len(launched) == 27, sorted(launched)
     missing = launched - set(BRANCHES) - LAB_ONLY
     assert not missing, f"launches of attention.hip without a branch (and so without a case) in the sweep: {sorted(missing)}"

@@ -277,6 +277,67 @@ def test_attention_backward_bias_gradient_is_bit_identical(ops, B, T, H, hd, rag
     assert _relerr(dbias, 1 + dqkv.float().sum(0)) < 1e-4
 
 
+def _det_twin_cases():
+    """(instantiation, hd, T, form) for every backward entry of the census module's BRANCHES at the first and last T of its range, in the
+    forms it serves: key mask for the `true` frag kernels, none and ragged for the `false` ones, all three for the general kernel"""
+    from tests.test_attention_census_gpu import BRANCHES
+    cases = []
+    for inst, (hd, lo, hi) in BRANCHES.items():
+        if not inst.startswith("attn_bwd"):
+            continue
+        forms = ("mask",) if ", true" in inst else ("none", "ragged") if ", false" in inst else ("none", "ragged", "mask")
+        cases += [(inst, hd, T, form) for T in (lo, hi) for form in forms]
+    return cases
+
+
+@pytest.mark.parametrize("inst,hd,T,form", _det_twin_cases(), ids=lambda v: str(v).replace(" ", ""))
+def test_every_deterministic_twin_of_the_backward_dispatch(ops, inst, hd, T, form):
+    """The DET instantiation of every branch of wj_attn_bwd (B = 3, H = 2, random bf16 operands): dqkv equals the default launch's bit
+    for bit; three deterministic launches agree bit for bit in dqkv, dbias_ws and dbias; dbias = the fp32 column sums of its own dqkv
+    within the 1e-4 of test_attention_backward_bias_gradient_is_bit_identical."""
+    from tests.test_attention_census_gpu import bwd_instantiation
+    assert bwd_instantiation(dict(T=T, hd=hd, form=form)) == inst
+    B, H = 3, 2
+    D = H * hd
+    g = torch.Generator(device=dev()).manual_seed(29)
+    key_mask = seq_off = None
+    rows, lse_shape = B * T, (B, H, T)
+    if form == "ragged":
+        lens = torch.tensor([T, max(1, T // 2), max(1, T - 1)])
+        off = torch.zeros(B + 1, dtype=torch.int32)
+        off[1:] = torch.cumsum(lens, 0)
+        rows, seq_off, lse_shape = int(off[-1]), off.to(dev()), (int(off[-1]), H)
+    elif form == "mask":
+        m = torch.rand(B, T, generator=torch.Generator().manual_seed(T)) < 0.4
+        m[:, T // 2] = False
+        key_mask = m.to(torch.uint8).to(dev())
+    qkv = torch.randn(rows, 3 * D, generator=g, device=dev()).to(torch.bfloat16)
+    dout = torch.randn(rows, D, generator=g, device=dev()).to(torch.bfloat16)
+    out = torch.empty(rows, D, dtype=torch.bfloat16, device=dev())
+    lse = torch.empty(lse_shape, device=dev())
+    ops.attn_fwd(qkv, out, B=B, T=T, H=H, hd=hd, lse=lse, seq_off=seq_off, key_mask=key_mask)
+    dqkv = torch.empty_like(qkv)
+    dbias = torch.empty(3 * D, device=dev())
+    ws = torch.empty(B, 3 * D, device=dev())
+
+    def launch(det):
+        dqkv.fill_(float("nan"))
+        dbias.fill_(1.0)
+        ws.fill_(float("nan"))
+        ops.attn_bwd(qkv, out, dout, lse, dqkv, B=B, T=T, H=H, hd=hd, dbias=dbias, dbias_ws=ws, seq_off=seq_off, key_mask=key_mask,
+                     deterministic=det)
+        torch.cuda.synchronize()
+        return [bits(dqkv), bits(ws), bits(dbias)]
+    default = launch(False)
+    first = launch(True)
+    assert torch.equal(first[0], default[0]), f"dqkv of the deterministic form differs from the default form's in {int((first[0] != default[0]).sum())} elements"
+    for r in (1, 2):
+        for name, a, b in zip(("dqkv", "dbias_ws", "dbias"), launch(True), first):
+            assert torch.equal(a, b), f"deterministic launch {r} differs from launch 0 in {name}"
+    assert not torch.isnan(dqkv.float()).any()
+    assert _relerr(dbias, 1 + dqkv.float().sum(0)) < 1e-4
+
+
 # ------------------------------------------------------------------------------------------------------------ whole steps
 def _one_step(cfg, n, audio, mset, deterministic, ragged=True, sparse=True, seed=7, defer=True):
     """a freshly built model, one forward + backward + FusedAdamW.step; returns loss, gradients, parameters, Adam moments (as bits)"""
