@@ -38,7 +38,7 @@ def build(force: bool = False, verbose: bool = True, lab: bool = False) -> str:
     objdir = os.path.join(LIBDIR, "obj_lab" if lab else "obj")
     os.makedirs(objdir, exist_ok=True)
     inc = os.path.join(os.path.dirname(HERE), "include")
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_internal.h"), os.path.join(CSRC, "attention_pieces.h"), os.path.join(inc, "wavjepa_hip.h"), os.path.join(inc, "wavjepa_hip_lab.h")]
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_internal.h"), os.path.join(CSRC, "gemm_pieces.h"), os.path.join(CSRC, "attention_pieces.h"), os.path.join(inc, "wavjepa_hip.h"), os.path.join(inc, "wavjepa_hip_lab.h")]
     flags = FLAGS + (["-DWJ_LAB"] if lab else [])
     lib = LAB_LIB if lab else LIB
     jobs = []

@@ -27,14 +27,12 @@
 //     are staged through LDS in row chunks and written as whole rows: 16-B coalesced stores, row-contiguous
 //     256-B float atomics for the split-K wgrad.
 //   * Workgroup ids are remapped so that the N-tiles sharing an A panel run on one XCD (shared L2).
-#include <stdlib.h>
-#include "common.h"
-#include "../../include/wavjepa_hip.h"
+#include "gemm_pieces.h"
 #include "gemm_internal.h"
 
 namespace {
 
-constexpr int BM = 256, BK = 32, NT = 512;
+constexpr int BM = 256, BK = 32, NT = GEMM_NT;
 constexpr long PAIR_TILE_BYTES = 2L * 4 * 32 * 64 * 16;   // K-split pairs: scratch per output tile (two roles x four waves' accumulators)
 
 // BMT: tile rows.  256 everywhere except the 384 x 128 tile of the predictor's grouped weight gradients (every dimension of those
@@ -61,11 +59,6 @@ template <int BN, int BMT = 256> struct Cfg {
     static constexpr int EPI_BYTES = RC_BF16 * CP_BF16 > RC_F32 * CP_F32 ? RC_BF16 * CP_BF16 : RC_F32 * CP_F32;   // 135168 / 69632
     static constexpr int LDS_BYTES = RING_BYTES > EPI_BYTES ? RING_BYTES : EPI_BYTES;
 };
-
-__device__ __attribute__((aligned(256))) unsigned char g_zero_page[256];
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void gl_void;
 
 // Branch-free pointer select (a ?: on pointers becomes EXEC-masked duplicate LDS-DMA instructions).
 __device__ __forceinline__ const bf16_t* sel_ptr(bool ok, const bf16_t* p, const bf16_t* z) {
@@ -168,13 +161,15 @@ struct TilePtrs {
     }
 };
 
-// ---- LDS -> 4 MFMA fragments (tile rows rbase0 + 16x + i, k = 8g + 0..7; i = lane&15, g = lane>>4) ---------------
-template <bool TRANS, int ROWS>
-__device__ __forceinline__ void load_frags4(bf16x8* f, const char* tile, int rbase0, int lane) {
+// ---- LDS -> NF MFMA fragments (tile rows rbase0 + 16x + i, k = 8g + 0..7; i = lane&15, g = lane>>4) --------------
+// NF = 4, or 2: the tail of a wave's six m-fragments in the 384-row tile
+template <int NF, bool TRANS, int ROWS>
+__device__ __forceinline__ void load_frags(bf16x8* f, const char* tile, int rbase0, int lane) {
+    static_assert(NF == 4 || NF == 2, "fragments are read in one asm statement of 4 or 2");
     const int i = lane & 15, g = lane >> 4;
     if constexpr (!TRANS) {
 #pragma unroll
-        for (int x = 0; x < 4; ++x) {
+        for (int x = 0; x < NF; ++x) {
             const int row = rbase0 + x * 16 + i;
             f[x] = *reinterpret_cast<const bf16x8*>(tile + row * 64 + ((g ^ row_swz(row)) << 4));
         }
@@ -183,91 +178,72 @@ __device__ __forceinline__ void load_frags4(bf16x8* f, const char* tile, int rba
         const int k = 8 * g + q;
         const int fx = (q | ((g & 1) << 2)) << 5;   // f(k) == f(k + 4), as a byte XOR on the 32-B column
         const unsigned base = (unsigned)(size_t)(const __attribute__((address_space(3))) char*)tile + k * (ROWS * 2);
-        const unsigned a0 = base + ((((rbase0 + 0) + 4 * p) << 1) ^ fx);
-        const unsigned a1 = base + ((((rbase0 + 16) + 4 * p) << 1) ^ fx);
-        const unsigned a2 = base + ((((rbase0 + 32) + 4 * p) << 1) ^ fx);
-        const unsigned a3 = base + ((((rbase0 + 48) + 4 * p) << 1) ^ fx);
-        bf16x4 l0, h0, l1, h1, l2, h2, l3, h3;
-        asm volatile(
-            "ds_read_b64_tr_b16 %0, %8\n\t"
-            "ds_read_b64_tr_b16 %1, %8 offset:%12\n\t"
-            "ds_read_b64_tr_b16 %2, %9\n\t"
-            "ds_read_b64_tr_b16 %3, %9 offset:%12\n\t"
-            "ds_read_b64_tr_b16 %4, %10\n\t"
-            "ds_read_b64_tr_b16 %5, %10 offset:%12\n\t"
-            "ds_read_b64_tr_b16 %6, %11\n\t"
-            "ds_read_b64_tr_b16 %7, %11 offset:%12\n\t"
-            "s_waitcnt lgkmcnt(0)"
-            : "=&v"(l0), "=&v"(h0), "=&v"(l1), "=&v"(h1), "=&v"(l2), "=&v"(h2), "=&v"(l3), "=&v"(h3)
-            : "v"(a0), "v"(a1), "v"(a2), "v"(a3), "n"(4 * ROWS * 2)
-            : "memory");
-        f[0] = __builtin_shufflevector(l0, h0, 0, 1, 2, 3, 4, 5, 6, 7);
-        f[1] = __builtin_shufflevector(l1, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-        f[2] = __builtin_shufflevector(l2, h2, 0, 1, 2, 3, 4, 5, 6, 7);
-        f[3] = __builtin_shufflevector(l3, h3, 0, 1, 2, 3, 4, 5, 6, 7);
+        unsigned a[NF];
+        bf16x4 l[NF], h[NF];
+#pragma unroll
+        for (int x = 0; x < NF; ++x) a[x] = base + ((((rbase0 + 16 * x) + 4 * p) << 1) ^ fx);
+        // ONE statement with its own lgkmcnt(0): through the intrinsic hipcc inserts vmcnt(0) before every read, draining the ring
+        if constexpr (NF == 4)
+            asm volatile(
+                "ds_read_b64_tr_b16 %0, %8\n\t"
+                "ds_read_b64_tr_b16 %1, %8 offset:%12\n\t"
+                "ds_read_b64_tr_b16 %2, %9\n\t"
+                "ds_read_b64_tr_b16 %3, %9 offset:%12\n\t"
+                "ds_read_b64_tr_b16 %4, %10\n\t"
+                "ds_read_b64_tr_b16 %5, %10 offset:%12\n\t"
+                "ds_read_b64_tr_b16 %6, %11\n\t"
+                "ds_read_b64_tr_b16 %7, %11 offset:%12\n\t"
+                "s_waitcnt lgkmcnt(0)"
+                : "=&v"(l[0]), "=&v"(h[0]), "=&v"(l[1]), "=&v"(h[1]), "=&v"(l[2]), "=&v"(h[2]), "=&v"(l[3]), "=&v"(h[3])
+                : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "n"(4 * ROWS * 2)
+                : "memory");
+        else
+            asm volatile(
+                "ds_read_b64_tr_b16 %0, %4\n\t"
+                "ds_read_b64_tr_b16 %1, %4 offset:%6\n\t"
+                "ds_read_b64_tr_b16 %2, %5\n\t"
+                "ds_read_b64_tr_b16 %3, %5 offset:%6\n\t"
+                "s_waitcnt lgkmcnt(0)"
+                : "=&v"(l[0]), "=&v"(h[0]), "=&v"(l[1]), "=&v"(h[1])
+                : "v"(a[0]), "v"(a[1]), "n"(4 * ROWS * 2)
+                : "memory");
+#pragma unroll
+        for (int x = 0; x < NF; ++x) f[x] = __builtin_shufflevector(l[x], h[x], 0, 1, 2, 3, 4, 5, 6, 7);
     }
 }
 
-// two fragments (tile rows rbase0 + 16x + i, x < 2): the tail of a wave's six m-fragments in the 384-row tile
-template <bool TRANS, int ROWS>
-__device__ __forceinline__ void load_frags2(bf16x8* f, const char* tile, int rbase0, int lane) {
-    const int i = lane & 15, g = lane >> 4;
-    if constexpr (!TRANS) {
-#pragma unroll
-        for (int x = 0; x < 2; ++x) {
-            const int row = rbase0 + x * 16 + i;
-            f[x] = *reinterpret_cast<const bf16x8*>(tile + row * 64 + ((g ^ row_swz(row)) << 4));
-        }
-    } else {
-        const int q = i >> 2, p = i & 3;
-        const int k = 8 * g + q;
-        const int fx = (q | ((g & 1) << 2)) << 5;
-        const unsigned base = (unsigned)(size_t)(const __attribute__((address_space(3))) char*)tile + k * (ROWS * 2);
-        const unsigned a0 = base + ((((rbase0 + 0) + 4 * p) << 1) ^ fx);
-        const unsigned a1 = base + ((((rbase0 + 16) + 4 * p) << 1) ^ fx);
-        bf16x4 l0, h0, l1, h1;
-        asm volatile(
-            "ds_read_b64_tr_b16 %0, %4\n\t"
-            "ds_read_b64_tr_b16 %1, %4 offset:%6\n\t"
-            "ds_read_b64_tr_b16 %2, %5\n\t"
-            "ds_read_b64_tr_b16 %3, %5 offset:%6\n\t"
-            "s_waitcnt lgkmcnt(0)"
-            : "=&v"(l0), "=&v"(h0), "=&v"(l1), "=&v"(h1)
-            : "v"(a0), "v"(a1), "n"(4 * ROWS * 2)
-            : "memory");
-        f[0] = __builtin_shufflevector(l0, h0, 0, 1, 2, 3, 4, 5, 6, 7);
-        f[1] = __builtin_shufflevector(l1, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-    }
+// Counted wait of the ring schedules: tile t has landed once all but this wave's loads of the `younger` in-flight tiles (LPT LDS-DMA
+// instructions each, at most two of them) are done.
+template <int LPT>
+__device__ __forceinline__ void wait_younger(int younger) {
+    if (younger >= 2) wait_vmcnt<2 * LPT>();
+    else if (younger == 1) wait_vmcnt<LPT>();
+    else wait_vmcnt<0>();
 }
 
 // Internal epilogue (not part of the ABI): the deterministic form of WJ_EPI_ATOMIC_F32 (wj_gemm_args.deterministic).  K slice `ksl` STORES
 // its fp32 tile into slab ksl of a scratch laid out [split][M][ldc] (EpiArgs.C = slab 0); slab_reduce_kernel adds the slabs in slice order.
 constexpr int EPI_SLAB_F32 = 64;
 
-struct EpiArgs {
-    void* C;
-    void* C2;
-    const float* bias;
-    const void* aux;
-    float* colsum;
-    long ldc;
-    int seg_rows, seg_valid;
-    float alpha;
-    const int32_t* rowmap;   // gather forms: storage row of logical row m (GATHER 1) / of logical k (GATHER 2)
-    const uint32_t* sa;      // MX fp8 path: E8M0 block scales of A, [K / 128][lds_a] dwords (byte b = k block 4 kt + b)
-    const uint32_t* sb;      //              ... and of B, [K / 128][lds_b]
-    long lds_a, lds_b;       //              rows (dwords) per K tile in those arrays
-    unsigned char* q_out;    // GELU epilogues, optional: gelu(h) also as MX fp8 (bytes [M][ldc]) + block scales [N / 128][ld_q] dwords
-    uint32_t* q_scales;
-    long ld_q;
-    float* pair_ws;          // K-split pairs (eight-phase schedule, pair_split below): [tiles][2 roles][4 waves][32 regs][64 lanes] float4
-    unsigned* pair_flags;    //   [tiles][2]: role r's half of the partial sums is posted (reset to 0 by the partner that consumed it)
+struct EpiArgs {             // (the defaults: a plain store of C, nothing optional)
+    void* C = nullptr;
+    void* C2 = nullptr;
+    const float* bias = nullptr;
+    const void* aux = nullptr;
+    float* colsum = nullptr;
+    long ldc = 0;
+    int seg_rows = 1, seg_valid = 1;
+    float alpha = 1.f;
+    const int32_t* rowmap = nullptr;   // gather forms: storage row of logical row m (GATHER 1) / of logical k (GATHER 2)
+    const uint32_t* sa = nullptr;      // MX fp8 path: E8M0 block scales of A, [K / 128][lds_a] dwords (byte b = k block 4 kt + b)
+    const uint32_t* sb = nullptr;      //              ... and of B, [K / 128][lds_b]
+    long lds_a = 0, lds_b = 0;         //              rows (dwords) per K tile in those arrays
+    unsigned char* q_out = nullptr;    // GELU epilogues, optional: gelu(h) also as MX fp8 (bytes [M][ldc]) + block scales [N / 128][ld_q] dwords
+    uint32_t* q_scales = nullptr;
+    long ld_q = 0;
+    float* pair_ws = nullptr;          // K-split pairs (eight-phase schedule, pair_split below): [tiles][2 roles][4 waves][32 regs][64 lanes] float4
+    unsigned* pair_flags = nullptr;    //   [tiles][2]: role r's half of the partial sums is posted (reset to 0 by the partner that consumed it)
 };
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // ---- eight-phase main loop (256 x 256 x 64 tile, row-form operands, K % 128 == 0) ----------------------------------------
 // Follows the 256^2 8-phase structure of the CDNA4 guide (cdna_hip_programming.md section 5), re-derived for this kernel's
@@ -294,167 +270,6 @@ __device__ __forceinline__ void wait_vmcnt() {
 // phase stages exactly one piece:   P0: Y(t+1)   P1: B1(t+1)   P2: B0(t+2)   P3: X(t+2)      (flight: 6 / 4 / 6 / 5 phases)
 // Two counted waits per tile: phase 3 retires X(t+1), B0(t+1) (vmcnt(8): Y(t+1), B1(t+1), B0(t+2), X(t+2) stay in flight), phase 0
 // retires B1(t) and with it the older Y(t) (vmcnt(6)); each is followed by a barrier before the phase that reads the data.
-template <int PAR>
-__device__ __forceinline__ void ep_tile(f32x4 (&acc)[8][4], char* smem, const char* (&px)[2], const char* (&py)[2], const char* (&pb0)[2],
-                                         const char* (&pb1)[2], const unsigned (&dx)[2], const unsigned (&db)[2], unsigned a_lo, unsigned b_lo,
-                                         bool more1, bool more2) {
-    constexpr unsigned BUF = 65536u, BOFF = 32768u;
-    char* cur = smem + PAR * BUF;
-    char* oth = smem + (PAR ^ 1) * BUF;
-    const unsigned a_hi = a_lo ^ 64u, b_hi = b_lo ^ 64u;
-    bf16x8 af[8], b0f[4], b1f[4];
-    auto lds = [&](unsigned off) { return *reinterpret_cast<const bf16x8*>(cur + off); };
-    auto dma = [&](const char*& src, char* dst) {
-        __builtin_amdgcn_global_load_lds((gl_void*)src, (lds_void*)dst, 16, 0, 0);
-        src += 128;
-    };
-    // ---- phase 0: X, B0 of this tile; stage Y(t+1); wait for B1(t)
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int x = 0; x < 2; ++x) { b0f[2 * x] = lds(b_lo + x * 2048); b0f[2 * x + 1] = lds(b_hi + x * 2048); }
-#pragma unroll
-    for (int x = 0; x < 4; ++x) { af[2 * x] = lds(a_lo + x * 2048); af[2 * x + 1] = lds(a_hi + x * 2048); }
-    if (more1) {
-        dma(py[0], oth + dx[0] + 8192); dma(py[1], oth + dx[1] + 8192);
-        wait_vmcnt<6>();
-    } else {
-        wait_vmcnt<0>();
-    }
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b0f[2 * ni], af[2 * mi], acc[mi][ni], 0, 0, 0);
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b0f[2 * ni + 1], af[2 * mi + 1], acc[mi][ni], 0, 0, 0);
-        }
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    // ---- phase 1: B1 of this tile; stage B1(t+1)
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int x = 0; x < 2; ++x) { b1f[2 * x] = lds(b_lo + 4096 + x * 2048); b1f[2 * x + 1] = lds(b_hi + 4096 + x * 2048); }
-    if (more1) { dma(pb1[0], oth + BOFF + db[0] + 4096); dma(pb1[1], oth + BOFF + db[1] + 4096); }
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-            acc[mi][2 + ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b1f[2 * ni], af[2 * mi], acc[mi][2 + ni], 0, 0, 0);
-            acc[mi][2 + ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b1f[2 * ni + 1], af[2 * mi + 1], acc[mi][2 + ni], 0, 0, 0);
-        }
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    // ---- phase 2: Y of this tile; stage B0(t+2) into THIS parity (its B0 rows were read two phases ago)
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int x = 0; x < 4; ++x) { af[2 * x] = lds(a_lo + 8192 + x * 2048); af[2 * x + 1] = lds(a_hi + 8192 + x * 2048); }
-    if (more2) { dma(pb0[0], cur + BOFF + db[0]); dma(pb0[1], cur + BOFF + db[1]); }
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-            acc[4 + mi][2 + ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b1f[2 * ni], af[2 * mi], acc[4 + mi][2 + ni], 0, 0, 0);
-            acc[4 + mi][2 + ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b1f[2 * ni + 1], af[2 * mi + 1], acc[4 + mi][2 + ni], 0, 0, 0);
-        }
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    // ---- phase 3: no fragment reads; stage X(t+2) into THIS parity (read in phase 0); wait for X(t+1), B0(t+1)
-    __builtin_amdgcn_sched_barrier(0);
-    if (more2) {
-        dma(px[0], cur + dx[0]); dma(px[1], cur + dx[1]);
-        wait_vmcnt<8>();
-    } else if (more1) {
-        wait_vmcnt<4>();
-    } else {
-        wait_vmcnt<0>();
-    }
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-            acc[4 + mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b0f[2 * ni], af[2 * mi], acc[4 + mi][ni], 0, 0, 0);
-            acc[4 + mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b0f[2 * ni + 1], af[2 * mi + 1], acc[4 + mi][ni], 0, 0, 0);
-        }
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-}
-
-__device__ __forceinline__ void eight_phase_loop(f32x4 (&acc)[8][4], char* smem, const bf16_t* __restrict__ A,
-                                                  const bf16_t* __restrict__ B, long lda, long ldb, int m0, int n0, int M, int N, int K,
-                                                  int wave, int lane) {
-    constexpr unsigned BUF = 65536u, BOFF = 32768u;
-    const int nkt = K / 64;                       // even (K % 128 == 0)
-    // this wave's two instructions of a piece: 8 rows each.  X rows: wave rows 0-63 of wave row 0 (waves 0-3) / 1 (waves 4-7);
-    // B0 rows: 32 of each wave column, waves pair up on a column.  Y = X + 64 rows, B1 = B0 + 32 rows.
-    const char* px[2]; const char* py[2]; const char* pb0[2]; const char* pb1[2];
-    unsigned dx[2], db[2];                        // LDS byte offsets (inside the A / B region) of the X / B0 instructions
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int rx = (wave < 4 ? 16 * wave : 128 + 16 * (wave - 4)) + 8 * u;         // first row of the 8-row group
-        const int ib = 16 * wave + 8 * u, rb = (ib >> 5) * 64 + (ib & 31);
-        dx[u] = (unsigned)rx * 128u;
-        db[u] = (unsigned)rb * 128u;
-        auto src = [&](const bf16_t* base, long ld, int r0, int R, int row) {
-            const int c = (lane & 7) ^ ((row >> 1) & 7);                             // LDS chunk position lane % 8 holds source chunk c
-            int gr = r0 + row;
-            gr = gr < R ? gr : R - 1;                                                // past the edge: clamped, never stored
-            return reinterpret_cast<const char*>(base + (long)gr * ld + c * 8);
-        };
-        px[u] = src(A, lda, m0, M, rx + (lane >> 3));
-        py[u] = src(A, lda, m0, M, rx + 64 + (lane >> 3));
-        pb0[u] = src(B, ldb, n0, N, rb + (lane >> 3));
-        pb1[u] = src(B, ldb, n0, N, rb + 32 + (lane >> 3));
-    }
-    auto dma = [&](const char*& s_, char* dst) {
-        __builtin_amdgcn_global_load_lds((gl_void*)s_, (lds_void*)dst, 16, 0, 0);
-        s_ += 128;
-    };
-    // prologue: tile 0 (parity 0) in the order its phases need it, then what "phases 2 / 3 of tile -1" would have staged of tile 1
-#pragma unroll
-    for (int u = 0; u < 2; ++u) dma(px[u], smem + dx[u]);
-#pragma unroll
-    for (int u = 0; u < 2; ++u) dma(pb0[u], smem + BOFF + db[u]);
-#pragma unroll
-    for (int u = 0; u < 2; ++u) dma(py[u], smem + dx[u] + 8192);
-#pragma unroll
-    for (int u = 0; u < 2; ++u) dma(pb1[u], smem + BOFF + db[u] + 4096);
-    if (nkt > 1) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) dma(pb0[u], smem + BUF + BOFF + db[u]);
-#pragma unroll
-        for (int u = 0; u < 2; ++u) dma(px[u], smem + BUF + dx[u]);
-        wait_vmcnt<4>();
-    } else {
-        wait_vmcnt<0>();
-    }
-    __builtin_amdgcn_s_barrier();
-    const int i = lane & 15, g = lane >> 4, wm = wave >> 2, wn = wave & 3;
-    const unsigned sw = (unsigned)((g ^ ((i >> 1) & 7)) << 4);
-    const unsigned a_lo = (unsigned)((wm * 128 + i) * 128) + sw;
-    const unsigned b_lo = BOFF + (unsigned)((wn * 64 + i) * 128) + sw;
-    if (wm == 1) __builtin_amdgcn_s_barrier();    // waves 4-7 run one barrier behind
-    for (int t = 0; t < nkt; t += 2) {
-        ep_tile<0>(acc, smem, px, py, pb0, pb1, dx, db, a_lo, b_lo, t + 1 < nkt, t + 2 < nkt);
-        ep_tile<1>(acc, smem, px, py, pb0, pb1, dx, db, a_lo, b_lo, t + 2 < nkt, t + 3 < nkt);
-    }
-    if (wm == 0) __builtin_amdgcn_s_barrier();    // balance the stagger
-}
-
 // ---- MX fp8 form of the eight-phase loop (256 x 256 x 128 tile) --------------------------------------------------------------
 // Operands are OCP e4m3 bytes with one E8M0 scale per 32 consecutive k (block-scaled v_mfma_scale_f32_16x16x128_f8f6f4: twice the
 // bf16 MFMA rate per byte of operand).  A K tile is 128 deep = the SAME 128-B LDS rows, swizzle, staging and phase structure as
@@ -463,200 +278,240 @@ __device__ __forceinline__ void eight_phase_loop(f32x4 (&acc)[8][4], char* smem,
 // k = 64 + 16 g .. in registers 4-7, and the scale byte of k block g of row i).  One MFMA per 16 x 16 fragment and K tile.
 // Block scales: [K / 128][rows] dwords (byte b = block 4 kt + b), 1 KiB per operand and K tile, staged by LDS-DMA next to the
 // ring (every wave moves 128 B of each, so the counted waits stay uniform) one K tile ahead.
-typedef int v8i32 __attribute__((ext_vector_type(8)));
-typedef int v4i32 __attribute__((ext_vector_type(4)));
-
-// The builtin form of the scaled MFMA is allocated with a destination DISTINCT from its accumulator input (early-clobber), which
-// at 128 accumulator registers per lane spills ~150 of them to scratch (and every scratch access is a vmcnt(0) in the LDS-DMA
-// ring).  In hardware vdst == srcC is the ordinary accumulate form, so the instruction is written out with the two tied.
-// "s_nop 1": VALU-written scale registers feed the MFMA (hipcc pads nothing inside an asm statement).
-__device__ __forceinline__ void mx_mfma(f32x4& acc, const v8i32& a, const v8i32& b, int scale_a, int scale_b) {
-    asm volatile("s_nop 1\n\tv_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0]"
-                 : "+v"(acc) : "v"(a), "v"(b), "v"(scale_a), "v"(scale_b));
-}
-
+// Staging by usage phase as in the bf16 loop (X / Y / B0 / B1 pieces, one per phase), plus the next tile's block scales, issued
+// FIRST in phase 0 (their buffer was last read in phase 2 of the previous tile).  Stream order per tile:
+//   P0: scales(t+1), Y(t+1)   P1: B1(t+1)   P2: B0(t+2)   P3: X(t+2)
+// phase 0's wait retires B1(t) (vmcnt(8): B0(t+1), X(t+1), scales(t+1), Y(t+1) stay in flight), phase 3's retires X(t+1),
+// B0(t+1) and scales(t+1) (vmcnt(8): Y(t+1), B1(t+1), B0(t+2), X(t+2) stay in flight).
 constexpr unsigned F8_SCALE_OFF = 131072u;   // LDS: [parity][A 1 KiB | B 1 KiB] after the two 64-KiB operand parities
 
-template <int PAR>
-__device__ __forceinline__ void ep8_tile(f32x4 (&acc)[8][4], char* smem, const char* __restrict__ A, const char* __restrict__ B,
-                                         const char* __restrict__ SA, const char* __restrict__ SB, unsigned (&ox)[2], unsigned (&oy)[2],
-                                         unsigned (&ob0)[2], unsigned (&ob1)[2], const unsigned (&dx)[2], const unsigned (&db)[2],
-                                         unsigned& osa, unsigned& osb, unsigned sa_step, unsigned sb_step, unsigned a_lo, unsigned b_lo,
-                                         int wave, int lane, bool more1, bool more2) {
+// What the two forms of the loop differ in, as operand policies: the fragment chunk type and MFMA form (Bf16Mma / MxMma), how a lane
+// addresses its LDS-DMA source, the staging of the block scales, and phase 0's vmcnt threshold.
+struct EpBf16 : Bf16Mma {
+    static constexpr int K_TILE = 64;            // k per 128-B row
+    static constexpr int WAIT0 = 6;              // younger than B1(t) in phase 0: B0, X, Y of t+1
+    static constexpr bool SCALED = false;
+    struct Src {                                 // this wave's two instructions of a piece: per-lane 64-bit pointers
+        const char* p[2];
+        __device__ __forceinline__ void init(int u, const char* base, long off) { p[u] = base + off; }
+        __device__ __forceinline__ void dma(int u, char* dst) {
+            __builtin_amdgcn_global_load_lds((gl_void*)p[u], (lds_void*)dst, 16, 0, 0);
+            p[u] += 128;
+        }
+    };
+    struct Scales {
+        __device__ __forceinline__ void stage(char*) {}
+        template <int N> __device__ __forceinline__ void read(int*, const char*, int) {}
+    };
+    static __device__ __forceinline__ void drain() {}
+};
+struct EpMx : MxMma {
+    static constexpr int K_TILE = 128;
+    static constexpr int WAIT0 = 8;              // ... and the two scale instructions of t+1
+    static constexpr bool SCALED = true;
+    struct Src {                                 // uniform matrix base + 32-bit per-lane offset (one register per instruction instead of a 64-bit pointer)
+        const char* base;
+        unsigned off[2];
+        __device__ __forceinline__ void init(int u, const char* b, long o) { base = b; off[u] = (unsigned)o; }
+        __device__ __forceinline__ void dma(int u, char* dst) {
+            __builtin_amdgcn_global_load_lds((gl_void*)(base + off[u]), (lds_void*)dst, 16, 0, 0);
+            off[u] += 128;
+        }
+    };
+    struct Scales {
+        const char* SA;
+        const char* SB;
+        unsigned osa, osb, sa_step, sb_step;
+        int wave, lane;
+        // this wave's 128 B of the next tile's A / B block scales (rows 32 wave .. +31: 4 rows (16 B) per lane of lanes 0-7; rows past
+        // the edge read the padding)
+        __device__ __forceinline__ void stage(char* sc) {
+            if (lane < 8) {
+                __builtin_amdgcn_global_load_lds((gl_void*)(SA + osa), (lds_void*)(sc + wave * 128), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((gl_void*)(SB + osb), (lds_void*)(sc + 1024 + wave * 128), 16, 0, 0);
+            }
+            osa += sa_step; osb += sb_step;
+        }
+        // the scale byte of k block g of rows row0 + 16 x + i
+        template <int N> __device__ __forceinline__ void read(int* sc_out, const char* sc, int row0) {
+            const int i = lane & 15, g = lane >> 4;
+#pragma unroll
+            for (int x = 0; x < N; ++x) sc_out[x] = (int)(*reinterpret_cast<const uint32_t*>(sc + (row0 + x * 16 + i) * 4) >> (8 * g));
+        }
+    };
+    static __device__ __forceinline__ void drain() { asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); }   // asm MFMA results -> compiler-scheduled readers (the epilogue)
+};
+template <class P> struct EpPieces { typename P::Src x, y, b0, b1; };
+
+template <class P, int PAR>
+__device__ __forceinline__ void ep_tile(f32x4 (&acc)[8][4], char* smem, EpPieces<P>& pc, typename P::Scales& S, const unsigned (&dx)[2],
+                                         const unsigned (&db)[2], unsigned a_lo, unsigned b_lo, int wm, int wn, bool more1, bool more2) {
     constexpr unsigned BUF = 65536u, BOFF = 32768u;
     char* cur = smem + PAR * BUF;
     char* oth = smem + (PAR ^ 1) * BUF;
     const unsigned a_hi = a_lo ^ 64u, b_hi = b_lo ^ 64u;
-    const int i = lane & 15, g = lane >> 4, wm = wave >> 2, wn = wave & 3;
-    const char* sc = smem + F8_SCALE_OFF + PAR * 2048;          // this tile's scales
-    char* sc_o = smem + F8_SCALE_OFF + (PAR ^ 1) * 2048;        // next tile's
-    v8i32 af[4], b0f[2], b1f[2];             // one MX operand = chunk g (k 16 g ..) | chunk 4 + g (k 64 + 16 g ..) of a 128-B row
+    const char* sc = smem + F8_SCALE_OFF + PAR * 2048;          // this tile's scales (MX), [A | B]
+    typename P::Chunk af[8], b0f[4], b1f[4];
     int sa[4], sb0[2], sb1[2];
-    auto lds8 = [&](unsigned lo, unsigned hi) {
-        const v4i32 x = *reinterpret_cast<const v4i32*>(cur + lo), y = *reinterpret_cast<const v4i32*>(cur + hi);
-        return __builtin_shufflevector(x, y, 0, 1, 2, 3, 4, 5, 6, 7);
-    };
-    auto scale = [&](const char* base, int row) { return (int)(*reinterpret_cast<const uint32_t*>(base + row * 4) >> (8 * g)); };
-    // LDS-DMA source = uniform matrix base + 32-bit per-lane offset (one register per stream instead of a 64-bit pointer)
-    auto dma = [&](const char* base, unsigned& off, char* dst) {
-        __builtin_amdgcn_global_load_lds((gl_void*)(base + off), (lds_void*)dst, 16, 0, 0);
-        off += 128;
-    };
-    // Staging by usage phase as in the bf16 loop (X / Y / B0 / B1 pieces, one per phase), plus the next tile's block scales, issued
-    // FIRST in phase 0 (their buffer was last read in phase 2 of the previous tile).  Stream order per tile:
-    //   P0: scales(t+1), Y(t+1)   P1: B1(t+1)   P2: B0(t+2)   P3: X(t+2)
-    // phase 0's wait retires B1(t) (vmcnt(8): B0(t+1), X(t+1), scales(t+1), Y(t+1) stay in flight), phase 3's retires X(t+1),
-    // B0(t+1) and scales(t+1) (vmcnt(8): Y(t+1), B1(t+1), B0(t+2), X(t+2) stay in flight).
-    // ---- phase 0: A rows 0-63, B cols 0-31
+    const int* psa = P::SCALED ? sa : nullptr;
+    const int* psb0 = P::SCALED ? sb0 : nullptr;
+    const int* psb1 = P::SCALED ? sb1 : nullptr;
+    // ---- phase 0: X, B0 of this tile; stage Y(t+1); wait for B1(t)
     __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int x = 0; x < 2; ++x) { b0f[x] = lds8(b_lo + x * 2048, b_hi + x * 2048); sb0[x] = scale(sc + 1024, wn * 64 + x * 16 + i); }
-#pragma unroll
-    for (int x = 0; x < 4; ++x) { af[x] = lds8(a_lo + x * 2048, a_hi + x * 2048); sa[x] = scale(sc, wm * 128 + x * 16 + i); }
+    read_frags<2>(b0f, cur, b_lo, b_hi);
+    S.template read<2>(sb0, sc + 1024, wn * 64);
+    read_frags<4>(af, cur, a_lo, a_hi);
+    S.template read<4>(sa, sc, wm * 128);
     if (more1) {
-        if (lane < 8) {                       // this wave's 128 B of the next tile's A / B block scales (rows 32 wave .. +31)
-            __builtin_amdgcn_global_load_lds((gl_void*)(SA + osa), (lds_void*)(sc_o + wave * 128), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gl_void*)(SB + osb), (lds_void*)(sc_o + 1024 + wave * 128), 16, 0, 0);
-        }
-        osa += sa_step; osb += sb_step;
-        dma(A, oy[0], oth + dx[0] + 8192); dma(A, oy[1], oth + dx[1] + 8192);
-        wait_vmcnt<8>();
+        S.stage(smem + F8_SCALE_OFF + (PAR ^ 1) * 2048);
+        pc.y.dma(0, oth + dx[0] + 8192); pc.y.dma(1, oth + dx[1] + 8192);
+        wait_vmcnt<P::WAIT0>();
     } else {
         wait_vmcnt<0>();
     }
-    __builtin_amdgcn_s_barrier();
+    phase_mfma<P, 0, 0>(acc, b0f, af, nullptr, psb0, psa);
+    // ---- phase 1: B1 of this tile; stage B1(t+1)
     __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-            mx_mfma(acc[mi][ni], b0f[ni], af[mi], sb0[ni], sa[mi]);
-    __builtin_amdgcn_s_setprio(0);
+    read_frags<2>(b1f, cur, b_lo + 4096, b_hi + 4096);
+    S.template read<2>(sb1, sc + 1024, wn * 64 + 32);
+    if (more1) { pc.b1.dma(0, oth + BOFF + db[0] + 4096); pc.b1.dma(1, oth + BOFF + db[1] + 4096); }
+    phase_mfma<P, 0, 2>(acc, b1f, af, nullptr, psb1, psa);
+    // ---- phase 2: Y of this tile; stage B0(t+2) into THIS parity (its B0 rows were read two phases ago)
     __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    // ---- phase 1: B cols 32-63
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int x = 0; x < 2; ++x) { b1f[x] = lds8(b_lo + 4096 + x * 2048, b_hi + 4096 + x * 2048); sb1[x] = scale(sc + 1024, wn * 64 + 32 + x * 16 + i); }
-    if (more1) { dma(B, ob1[0], oth + BOFF + db[0] + 4096); dma(B, ob1[1], oth + BOFF + db[1] + 4096); }
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-            mx_mfma(acc[mi][2 + ni], b1f[ni], af[mi], sb1[ni], sa[mi]);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    // ---- phase 2: A rows 64-127
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int x = 0; x < 4; ++x) { af[x] = lds8(a_lo + 8192 + x * 2048, a_hi + 8192 + x * 2048); sa[x] = scale(sc, wm * 128 + 64 + x * 16 + i); }
-    if (more2) { dma(B, ob0[0], cur + BOFF + db[0]); dma(B, ob0[1], cur + BOFF + db[1]); }
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-            mx_mfma(acc[4 + mi][2 + ni], b1f[ni], af[mi], sb1[ni], sa[mi]);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    // ---- phase 3: no fragment reads
+    read_frags<4>(af, cur, a_lo + 8192, a_hi + 8192);
+    S.template read<4>(sa, sc, wm * 128 + 64);
+    if (more2) { pc.b0.dma(0, cur + BOFF + db[0]); pc.b0.dma(1, cur + BOFF + db[1]); }
+    phase_mfma<P, 4, 2>(acc, b1f, af, nullptr, psb1, psa);
+    // ---- phase 3: no fragment reads; stage X(t+2) into THIS parity (read in phase 0); wait for X(t+1), B0(t+1)
     __builtin_amdgcn_sched_barrier(0);
     if (more2) {
-        dma(A, ox[0], cur + dx[0]); dma(A, ox[1], cur + dx[1]);
+        pc.x.dma(0, cur + dx[0]); pc.x.dma(1, cur + dx[1]);
         wait_vmcnt<8>();
     } else if (more1) {
         wait_vmcnt<4>();
     } else {
         wait_vmcnt<0>();
     }
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-            mx_mfma(acc[4 + mi][ni], b0f[ni], af[mi], sb0[ni], sa[mi]);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
+    phase_mfma<P, 4, 0>(acc, b0f, af, nullptr, psb0, psa);
 }
 
-// A, B: e4m3 bytes, [M][K] / [N][K] (K contiguous, leading dimensions in BYTES, matrices < 4 GiB); K % 256 == 0
-__device__ __forceinline__ void eight_phase_loop_fp8(f32x4 (&acc)[8][4], char* smem, const char* __restrict__ A, const char* __restrict__ B,
-                                                     long lda, long ldb, int m0, int n0, int M, int N, int K, const EpiArgs& e, int wave,
-                                                     int lane) {
+// A, B: the operands at the first k of this workgroup's K range, rows lda_b / ldb_b BYTES apart (MX: matrices < 4 GiB); nkt K tiles of
+// P::K_TILE (even, or 1)
+template <class P>
+__device__ __forceinline__ void eight_phase_loop(f32x4 (&acc)[8][4], char* smem, const char* __restrict__ A, const char* __restrict__ B,
+                                                  long lda_b, long ldb_b, int m0, int n0, int M, int N, int nkt, typename P::Scales& S,
+                                                  int wave, int lane) {
     constexpr unsigned BUF = 65536u, BOFF = 32768u;
-    const int nkt = K / 128;
-    unsigned ox[2], oy[2], ob0[2], ob1[2], dx[2], db[2];
+    // this wave's two instructions of a piece: 8 rows each (piece_row_x / piece_row_b).  Y = X + 64 rows, B1 = B0 + 32 rows.
+    EpPieces<P> pc;
+    unsigned dx[2], db[2];                        // LDS byte offsets (inside the A / B region) of the X / B0 instructions
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-        const int rx = (wave < 4 ? 16 * wave : 128 + 16 * (wave - 4)) + 8 * u;
-        const int ib = 16 * wave + 8 * u, rb = (ib >> 5) * 64 + (ib & 31);
+        const int rx = piece_row_x(wave, u), rb = piece_row_b(wave, u);
         dx[u] = (unsigned)rx * 128u;
         db[u] = (unsigned)rb * 128u;
-        auto off = [&](long ld, int r0, int R, int row) {
-            const int c = (lane & 7) ^ ((row >> 1) & 7);
+        auto off = [&](long ld_b, int r0, int R, int row) {
             int gr = r0 + row;
-            gr = gr < R ? gr : R - 1;
-            return (unsigned)((long)gr * ld + c * 16);
+            gr = gr < R ? gr : R - 1;                                                // past the edge: clamped, never stored
+            return (long)gr * ld_b + swz128(lane & 7, row) * 16;
         };
-        ox[u] = off(lda, m0, M, rx + (lane >> 3));
-        oy[u] = off(lda, m0, M, rx + 64 + (lane >> 3));
-        ob0[u] = off(ldb, n0, N, rb + (lane >> 3));
-        ob1[u] = off(ldb, n0, N, rb + 32 + (lane >> 3));
+        pc.x.init(u, A, off(lda_b, m0, M, rx + (lane >> 3)));
+        pc.y.init(u, A, off(lda_b, m0, M, rx + 64 + (lane >> 3)));
+        pc.b0.init(u, B, off(ldb_b, n0, N, rb + (lane >> 3)));
+        pc.b1.init(u, B, off(ldb_b, n0, N, rb + 32 + (lane >> 3)));
     }
-    // block scales: this wave's 32 rows of the tile, 4 rows (16 B) per lane of lanes 0-7; rows past the edge read the padding
-    const char* SA = reinterpret_cast<const char*>(e.sa);
-    const char* SB = reinterpret_cast<const char*>(e.sb);
-    unsigned osa = (unsigned)(m0 + wave * 32 + (lane & 7) * 4) * 4u, osb = (unsigned)(n0 + wave * 32 + (lane & 7) * 4) * 4u;
-    const unsigned sa_step = (unsigned)(e.lds_a * 4), sb_step = (unsigned)(e.lds_b * 4);
-    auto dma = [&](const char* base, unsigned& off, char* dst) {
-        __builtin_amdgcn_global_load_lds((gl_void*)(base + off), (lds_void*)dst, 16, 0, 0);
-        off += 128;
-    };
-    if (lane < 8) {
-        __builtin_amdgcn_global_load_lds((gl_void*)(SA + osa), (lds_void*)(smem + F8_SCALE_OFF + wave * 128), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((gl_void*)(SB + osb), (lds_void*)(smem + F8_SCALE_OFF + 1024 + wave * 128), 16, 0, 0);
-    }
-    osa += sa_step; osb += sb_step;
+    // prologue: tile 0 (parity 0; its scales first) in the order its phases need it, then what "phases 2 / 3 of tile -1" would have
+    // staged of tile 1
+    S.stage(smem + F8_SCALE_OFF);
 #pragma unroll
-    for (int u = 0; u < 2; ++u) dma(A, ox[u], smem + dx[u]);
+    for (int u = 0; u < 2; ++u) pc.x.dma(u, smem + dx[u]);
 #pragma unroll
-    for (int u = 0; u < 2; ++u) dma(B, ob0[u], smem + BOFF + db[u]);
+    for (int u = 0; u < 2; ++u) pc.b0.dma(u, smem + BOFF + db[u]);
 #pragma unroll
-    for (int u = 0; u < 2; ++u) dma(A, oy[u], smem + dx[u] + 8192);
+    for (int u = 0; u < 2; ++u) pc.y.dma(u, smem + dx[u] + 8192);
 #pragma unroll
-    for (int u = 0; u < 2; ++u) dma(B, ob1[u], smem + BOFF + db[u] + 4096);
+    for (int u = 0; u < 2; ++u) pc.b1.dma(u, smem + BOFF + db[u] + 4096);
     if (nkt > 1) {
 #pragma unroll
-        for (int u = 0; u < 2; ++u) dma(B, ob0[u], smem + BUF + BOFF + db[u]);
+        for (int u = 0; u < 2; ++u) pc.b0.dma(u, smem + BUF + BOFF + db[u]);
 #pragma unroll
-        for (int u = 0; u < 2; ++u) dma(A, ox[u], smem + BUF + dx[u]);
+        for (int u = 0; u < 2; ++u) pc.x.dma(u, smem + BUF + dx[u]);
         wait_vmcnt<4>();
     } else {
         wait_vmcnt<0>();
     }
     __builtin_amdgcn_s_barrier();
-    const int i = lane & 15, g = lane >> 4, wm = wave >> 2, wn = wave & 3;
-    const unsigned sw = (unsigned)((g ^ ((i >> 1) & 7)) << 4);
-    const unsigned a_lo = (unsigned)((wm * 128 + i) * 128) + sw;
-    const unsigned b_lo = BOFF + (unsigned)((wn * 64 + i) * 128) + sw;
-    if (wm == 1) __builtin_amdgcn_s_barrier();
+    const int wm = wave >> 2, wn = wave & 3;
+    const unsigned a_lo = frag_off(wm * 128, lane), b_lo = BOFF + frag_off(wn * 64, lane);
+    if (wm == 1) __builtin_amdgcn_s_barrier();    // waves 4-7 run one barrier behind
     for (int t = 0; t < nkt; t += 2) {
-        ep8_tile<0>(acc, smem, A, B, SA, SB, ox, oy, ob0, ob1, dx, db, osa, osb, sa_step, sb_step, a_lo, b_lo, wave, lane, t + 1 < nkt, t + 2 < nkt);
-        ep8_tile<1>(acc, smem, A, B, SA, SB, ox, oy, ob0, ob1, dx, db, osa, osb, sa_step, sb_step, a_lo, b_lo, wave, lane, t + 2 < nkt, t + 3 < nkt);
+        ep_tile<P, 0>(acc, smem, pc, S, dx, db, a_lo, b_lo, wm, wn, t + 1 < nkt, t + 2 < nkt);
+        ep_tile<P, 1>(acc, smem, pc, S, dx, db, a_lo, b_lo, wm, wn, t + 2 < nkt, t + 3 < nkt);
     }
-    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // asm MFMA results -> compiler-scheduled readers (the epilogue)
-    if (wm == 0) __builtin_amdgcn_s_barrier();
+    P::drain();
+    if (wm == 0) __builtin_amdgcn_s_barrier();    // balance the stagger
+}
+
+// K-split pairs (gemm3_body): the two workgroups of an output tile exchange HALF of their fp32 partial sums through `pair_ws`.
+__device__ __forceinline__ void pair_exchange(f32x4 (&acc)[8][4], const EpiArgs& e, int tile, int role, int wm, int wave, int lane, int t) {
+    // post the accumulators of the waves whose rows the partner finishes, take the partner's for the rows kept here.
+    // Coherence between the two workgroups (different CUs, possibly different XCDs = different L2s) is carried by the
+    // ACCESSES, not by fences: agent-scope (sc1) stores write through the L2, agent-scope loads do not hit stale lines.
+    // (Release / acquire fences -- buffer_wbl2 / buffer_inv of the whole L2 from 234 workgroups -- cost ~90 us per launch.)
+    char* ws = reinterpret_cast<char*>(e.pair_ws) + (size_t)tile * PAIR_TILE_BYTES;
+    unsigned* flags = e.pair_flags + tile * 2;
+    const long slot = ((long)((wave & 3) * 32) * 64 + lane) * 16;
+    if (wm != role) {
+        char* dst = ws + (size_t)role * (PAIR_TILE_BYTES / 2) + slot;
+#pragma unroll
+        for (int a = 0; a < 8; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dst + (a * 4 + b) * 1024), "v"(acc[a][b]) : "memory");
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the partials have reached the coherence point ...
+    __syncthreads();
+    if (t == 0) {
+        __hip_atomic_store(flags + role, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // ... before the flag
+        while (__hip_atomic_load(flags + (role ^ 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) __builtin_amdgcn_s_sleep(2);
+        __hip_atomic_store(flags + (role ^ 1), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // consumed: ready for the next launch
+    }
+    __syncthreads();
+    if (wm == role) {
+        const char* src = ws + (size_t)(role ^ 1) * (PAIR_TILE_BYTES / 2) + slot;
+        // two batches of 16 loads, each one round trip (a batch per accumulator row made eight dependent round trips of
+        // ~2 us while all 234 workgroups exchange at once)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            f32x4 p[16];
+            asm volatile(
+                "global_load_dwordx4 %0, %16, off sc1\n\t"
+                "global_load_dwordx4 %1, %16, off offset:1024 sc1\n\t"
+                "global_load_dwordx4 %2, %16, off offset:2048 sc1\n\t"
+                "global_load_dwordx4 %3, %16, off offset:3072 sc1\n\t"
+                "global_load_dwordx4 %4, %17, off sc1\n\t"
+                "global_load_dwordx4 %5, %17, off offset:1024 sc1\n\t"
+                "global_load_dwordx4 %6, %17, off offset:2048 sc1\n\t"
+                "global_load_dwordx4 %7, %17, off offset:3072 sc1\n\t"
+                "global_load_dwordx4 %8, %18, off sc1\n\t"
+                "global_load_dwordx4 %9, %18, off offset:1024 sc1\n\t"
+                "global_load_dwordx4 %10, %18, off offset:2048 sc1\n\t"
+                "global_load_dwordx4 %11, %18, off offset:3072 sc1\n\t"
+                "global_load_dwordx4 %12, %19, off sc1\n\t"
+                "global_load_dwordx4 %13, %19, off offset:1024 sc1\n\t"
+                "global_load_dwordx4 %14, %19, off offset:2048 sc1\n\t"
+                "global_load_dwordx4 %15, %19, off offset:3072 sc1\n\t"
+                "s_waitcnt vmcnt(0)"
+                : "=&v"(p[0]), "=&v"(p[1]), "=&v"(p[2]), "=&v"(p[3]), "=&v"(p[4]), "=&v"(p[5]), "=&v"(p[6]), "=&v"(p[7]),
+                  "=&v"(p[8]), "=&v"(p[9]), "=&v"(p[10]), "=&v"(p[11]), "=&v"(p[12]), "=&v"(p[13]), "=&v"(p[14]), "=&v"(p[15])
+                : "v"(src + (h * 4 + 0) * 4096), "v"(src + (h * 4 + 1) * 4096), "v"(src + (h * 4 + 2) * 4096), "v"(src + (h * 4 + 3) * 4096)
+                : "memory");
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) acc[h * 4 + a][b] += p[a * 4 + b];
+        }
+    }
 }
 
 // GATHER 0: dense.  1: logical row m of A (row form) and of C lives at storage row rowmap[m] (conv dgrad over the active
@@ -701,11 +556,11 @@ __device__ __forceinline__ void gemm3_body(const bf16_t* __restrict__ A, const b
     int wg = 0, role = 0;
     if (pair) {
         const int nt = tiles_n * ((M + BM - 1) / BM);      // tiles of the problem
-        const int x = bid & 7, j = bid >> 3, tq = nt >> 3, tr = nt & 7;
-        const int len = tq + (x < tr ? 1 : 0), start = x < tr ? x * (tq + 1) : tr * (tq + 1) + (x - tr) * tq;
-        if (j >= 2 * len) return;                 // grid padding
-        role = j >= len ? 1 : 0;
-        wg = role * nt + start + (role ? j - len : j);
+        const int j = bid >> 3;
+        const XcdRun run = xcd_run(nt, bid & 7);
+        if (j >= 2 * run.len) return;             // grid padding
+        role = j >= run.len ? 1 : 0;
+        wg = role * nt + run.start + (role ? j - run.len : j);
     } else {
         wg = remapped ? bid : xcd_remap(bid, nwg);
     }
@@ -752,8 +607,15 @@ __device__ __forceinline__ void gemm3_body(const bf16_t* __restrict__ A, const b
         pa.init(A, lda, m0, M, kbeg, wave, lane, zero);
         pb.init(B, ldb, n0, N, kbeg, wave, lane, zero);
     }
-    auto stage_dense = [&](char* st, int k0) {
-        if (k0 + BK <= kend) {
+    // the K tile that starts at k0 -> ring stage st (GATHER 2: kidx holds that tile's rows)
+    auto stage_k = [&](char* st, int k0) {
+        if constexpr (GATHER == 2) {
+            stage_tile<AT, BM, true>(st, A, lda, m0, M, k0, kend, wave, lane, zero, kidx);
+            stage_tile<BT, BN, true>(st + A_BYTES, B, ldb, n0, N, k0, kend, wave, lane, zero, kidx);
+        } else if constexpr (GATHER == 1) {
+            stage_tile<AT, BM, true>(st, A, lda, m0, M, k0, kend, wave, lane, zero, arow);
+            stage_tile<BT, BN>(st + A_BYTES, B, ldb, n0, N, k0, kend, wave, lane, zero);
+        } else if (k0 + BK <= kend) {
             pa.issue_and_advance(st, wave);
             pb.issue_and_advance(st + A_BYTES, wave);
         } else {
@@ -761,87 +623,38 @@ __device__ __forceinline__ void gemm3_body(const bf16_t* __restrict__ A, const b
             stage_tile<BT, BN>(st + A_BYTES, B, ldb, n0, N, k0, kend, wave, lane, zero);
         }
     };
+    // this wave's fragments of the K tile in ring stage `cur`: 4 of B, MI of A
+    auto load_tile_frags = [&](bf16x8 (&af)[MI], bf16x8 (&bfr)[4], int cur) {
+        const char* sa = smem + cur * STAGE_BYTES;
+        load_frags<4, BT, BN>(bfr, sa + A_BYTES, wn * 64, lane);
+#pragma unroll
+        for (int h = 0; h < MI / 4; ++h) load_frags<4, AT, BM>(af + 4 * h, sa, wm * (MI * 16) + h * 64, lane);
+        if constexpr (MI % 4 == 2) load_frags<2, AT, BM>(af + MI - 2, sa, wm * (MI * 16) + (MI - 2) * 16, lane);
+    };
 
     if constexpr (SCHED == 3) {
-        eight_phase_loop_fp8(acc, smem, reinterpret_cast<const char*>(A), reinterpret_cast<const char*>(B), lda, ldb, m0, n0, M, N, K, e, wave, lane);
+        // A, B: e4m3 bytes, [M][K] / [N][K] (K contiguous, leading dimensions in BYTES); K % 256 == 0
+        EpMx::Scales S;
+        S.SA = reinterpret_cast<const char*>(e.sa);
+        S.SB = reinterpret_cast<const char*>(e.sb);
+        S.osa = (unsigned)(m0 + wave * 32 + (lane & 7) * 4) * 4u;
+        S.osb = (unsigned)(n0 + wave * 32 + (lane & 7) * 4) * 4u;
+        S.sa_step = (unsigned)(e.lds_a * 4); S.sb_step = (unsigned)(e.lds_b * 4);
+        S.wave = wave; S.lane = lane;
+        eight_phase_loop<EpMx>(acc, smem, reinterpret_cast<const char*>(A), reinterpret_cast<const char*>(B), lda, ldb, m0, n0, M, N, K / EpMx::K_TILE, S, wave, lane);
     } else if constexpr (SCHED == 2) {
-        eight_phase_loop(acc, smem, A + kbeg, B + kbeg, lda, ldb, m0, n0, M, N, kend - kbeg, wave, lane);
+        EpBf16::Scales S;
+        eight_phase_loop<EpBf16>(acc, smem, reinterpret_cast<const char*>(A + kbeg), reinterpret_cast<const char*>(B + kbeg), lda * 2, ldb * 2, m0, n0, M, N,
+                                 (kend - kbeg) / EpBf16::K_TILE, S, wave, lane);
         if constexpr (PAIR_OK) {
-            if (pair) {
-                // post the accumulators of the waves whose rows the partner finishes, take the partner's for the rows kept here.
-                // Coherence between the two workgroups (different CUs, possibly different XCDs = different L2s) is carried by the
-                // ACCESSES, not by fences: agent-scope (sc1) stores write through the L2, agent-scope loads do not hit stale lines.
-                // (Release / acquire fences -- buffer_wbl2 / buffer_inv of the whole L2 from 234 workgroups -- cost ~90 us per launch.)
-                char* ws = reinterpret_cast<char*>(e.pair_ws) + (size_t)tile * PAIR_TILE_BYTES;
-                unsigned* flags = e.pair_flags + tile * 2;
-                const long slot = ((long)((wave & 3) * 32) * 64 + lane) * 16;
-                if (wm != role) {
-                    char* dst = ws + (size_t)role * (PAIR_TILE_BYTES / 2) + slot;
-#pragma unroll
-                    for (int a = 0; a < 8; ++a)
-#pragma unroll
-                        for (int b = 0; b < 4; ++b)
-                            asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dst + (a * 4 + b) * 1024), "v"(acc[a][b]) : "memory");
-                }
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the partials have reached the coherence point ...
-                __syncthreads();
-                if (t == 0) {
-                    __hip_atomic_store(flags + role, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // ... before the flag
-                    while (__hip_atomic_load(flags + (role ^ 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) __builtin_amdgcn_s_sleep(2);
-                    __hip_atomic_store(flags + (role ^ 1), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // consumed: ready for the next launch
-                }
-                __syncthreads();
-                if (wm == role) {
-                    const char* src = ws + (size_t)(role ^ 1) * (PAIR_TILE_BYTES / 2) + slot;
-                    // two batches of 16 loads, each one round trip (a batch per accumulator row made eight dependent round trips of
-                    // ~2 us while all 234 workgroups exchange at once)
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        f32x4 p[16];
-                        asm volatile(
-                            "global_load_dwordx4 %0, %16, off sc1\n\t"
-                            "global_load_dwordx4 %1, %16, off offset:1024 sc1\n\t"
-                            "global_load_dwordx4 %2, %16, off offset:2048 sc1\n\t"
-                            "global_load_dwordx4 %3, %16, off offset:3072 sc1\n\t"
-                            "global_load_dwordx4 %4, %17, off sc1\n\t"
-                            "global_load_dwordx4 %5, %17, off offset:1024 sc1\n\t"
-                            "global_load_dwordx4 %6, %17, off offset:2048 sc1\n\t"
-                            "global_load_dwordx4 %7, %17, off offset:3072 sc1\n\t"
-                            "global_load_dwordx4 %8, %18, off sc1\n\t"
-                            "global_load_dwordx4 %9, %18, off offset:1024 sc1\n\t"
-                            "global_load_dwordx4 %10, %18, off offset:2048 sc1\n\t"
-                            "global_load_dwordx4 %11, %18, off offset:3072 sc1\n\t"
-                            "global_load_dwordx4 %12, %19, off sc1\n\t"
-                            "global_load_dwordx4 %13, %19, off offset:1024 sc1\n\t"
-                            "global_load_dwordx4 %14, %19, off offset:2048 sc1\n\t"
-                            "global_load_dwordx4 %15, %19, off offset:3072 sc1\n\t"
-                            "s_waitcnt vmcnt(0)"
-                            : "=&v"(p[0]), "=&v"(p[1]), "=&v"(p[2]), "=&v"(p[3]), "=&v"(p[4]), "=&v"(p[5]), "=&v"(p[6]), "=&v"(p[7]),
-                              "=&v"(p[8]), "=&v"(p[9]), "=&v"(p[10]), "=&v"(p[11]), "=&v"(p[12]), "=&v"(p[13]), "=&v"(p[14]), "=&v"(p[15])
-                            : "v"(src + (h * 4 + 0) * 4096), "v"(src + (h * 4 + 1) * 4096), "v"(src + (h * 4 + 2) * 4096), "v"(src + (h * 4 + 3) * 4096)
-                            : "memory");
-#pragma unroll
-                        for (int a = 0; a < 4; ++a)
-#pragma unroll
-                            for (int b = 0; b < 4; ++b) acc[h * 4 + a][b] += p[a * 4 + b];
-                    }
-                }
-            }
+            if (pair) pair_exchange(acc, e, tile, role, wm, wave, lane, t);
         }
     } else if (nkt > 0) {
 #pragma unroll
         for (int p = 0; p < S - 1; ++p) {
             if (p < nkt) {
-                if constexpr (GATHER == 2) {
-                    load_kidx(kbeg + p * BK);
-                    stage_tile<AT, BM, true>(smem + p * STAGE_BYTES, A, lda, m0, M, kbeg + p * BK, kend, wave, lane, zero, kidx);
-                    stage_tile<BT, BN, true>(smem + p * STAGE_BYTES + A_BYTES, B, ldb, n0, N, kbeg + p * BK, kend, wave, lane, zero, kidx);
-                } else if constexpr (GATHER == 1) {
-                    stage_tile<AT, BM, true>(smem + p * STAGE_BYTES, A, lda, m0, M, kbeg + p * BK, kend, wave, lane, zero, arow);
-                    stage_tile<BT, BN>(smem + p * STAGE_BYTES + A_BYTES, B, ldb, n0, N, kbeg + p * BK, kend, wave, lane, zero);
-                } else {
-                    stage_dense(smem + p * STAGE_BYTES, kbeg + p * BK);
-                }
+                if constexpr (GATHER == 2) load_kidx(kbeg + p * BK);
+                stage_k(smem + p * STAGE_BYTES, kbeg + p * BK);
             }
         }
         if constexpr (GATHER == 2) load_kidx(kbeg + (S - 1) * BK);   // indices of the tile staged in iteration 0
@@ -850,33 +663,16 @@ __device__ __forceinline__ void gemm3_body(const bf16_t* __restrict__ A, const b
             for (int kt = 0; kt < nkt; ++kt) {
                 // tile kt has landed once all but this wave's loads of the younger in-flight tiles are done; the barrier makes
                 // every wave's share visible and proves every wave is past its reads of the stage refilled below (tile kt-1).
-                const int younger = min(S - 2, nkt - 1 - kt);
-                if (younger >= 2) wait_vmcnt<2 * LPT>();
-                else if (younger == 1) wait_vmcnt<LPT>();
-                else wait_vmcnt<0>();
+                wait_younger<LPT>(min(S - 2, nkt - 1 - kt));
                 __builtin_amdgcn_s_barrier();
                 if (kt + S - 1 < nkt) {
                     const int nxt = cur == 0 ? S - 1 : cur - 1;   // (cur + S - 1) % S
-                    char* st = smem + nxt * STAGE_BYTES;
                     const int k0 = kbeg + (kt + S - 1) * BK;
-                    if constexpr (GATHER == 2) {
-                        stage_tile<AT, BM, true>(st, A, lda, m0, M, k0, kend, wave, lane, zero, kidx);
-                        stage_tile<BT, BN, true>(st + A_BYTES, B, ldb, n0, N, k0, kend, wave, lane, zero, kidx);
-                        load_kidx(k0 + BK);                       // next iteration's tile: the scalar load has a whole tile to land
-                    } else if constexpr (GATHER == 1) {
-                        stage_tile<AT, BM, true>(st, A, lda, m0, M, k0, kend, wave, lane, zero, arow);
-                        stage_tile<BT, BN>(st + A_BYTES, B, ldb, n0, N, k0, kend, wave, lane, zero);
-                    } else {
-                        stage_dense(st, k0);
-                    }
+                    stage_k(smem + nxt * STAGE_BYTES, k0);
+                    if constexpr (GATHER == 2) load_kidx(k0 + BK);   // next iteration's tile: the scalar load has a whole tile to land
                 }
-                const char* sa = smem + cur * STAGE_BYTES;
-                const char* sb = sa + A_BYTES;
                 bf16x8 af[MI], bfr[4];
-                load_frags4<BT, BN>(bfr, sb, wn * 64, lane);
-#pragma unroll
-                for (int h = 0; h < MI / 4; ++h) load_frags4<AT, BM>(af + 4 * h, sa, wm * (MI * 16) + h * 64, lane);
-                if constexpr (MI % 4 == 2) load_frags2<AT, BM>(af + MI - 2, sa, wm * (MI * 16) + (MI - 2) * 16, lane);
+                load_tile_frags(af, bfr, cur);
 #pragma unroll
                 for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
@@ -891,13 +687,8 @@ __device__ __forceinline__ void gemm3_body(const bf16_t* __restrict__ A, const b
             // (counted vmcnt) for tile kt+1 in the segment before group 0 starts reading it.
             // (Interleaving the LDS-DMA issue into the MFMA cluster instead was measured slower: ceiling 1133 -> 843 TFLOP/s.)
             const int grp = wave >> 2;
-            {   // tile 0 landed and visible
-                const int younger = min(S - 2, nkt - 1);
-                if (younger >= 2) wait_vmcnt<2 * LPT>();
-                else if (younger == 1) wait_vmcnt<LPT>();
-                else wait_vmcnt<0>();
-                __builtin_amdgcn_s_barrier();
-            }
+            wait_younger<LPT>(min(S - 2, nkt - 1));            // tile 0 landed ...
+            __builtin_amdgcn_s_barrier();                      // ... and visible
             if (grp == 1) __builtin_amdgcn_s_barrier();       // group 1 starts one segment later
             for (int kt = 0; kt < nkt; ++kt) {
                 // ---- LOAD segment
@@ -905,23 +696,13 @@ __device__ __forceinline__ void gemm3_body(const bf16_t* __restrict__ A, const b
 #ifndef WJ_ABLATE_GLDS
                 if (kt + S - 1 < nkt) {
                     const int nxt = cur == 0 ? S - 1 : cur - 1;   // stage of tile kt-1: both groups read it >= 1 barrier ago
-                    char* st = smem + nxt * STAGE_BYTES;
-                    stage_dense(st, kbeg + (kt + S - 1) * BK);
+                    stage_k(smem + nxt * STAGE_BYTES, kbeg + (kt + S - 1) * BK);
                 }
 #endif
-                const char* sa = smem + cur * STAGE_BYTES;
-                const char* sb = sa + A_BYTES;
                 bf16x8 af[MI], bfr[4];
-                load_frags4<BT, BN>(bfr, sb, wn * 64, lane);
-#pragma unroll
-                for (int h = 0; h < MI / 4; ++h) load_frags4<AT, BM>(af + 4 * h, sa, wm * (MI * 16) + h * 64, lane);
-                if constexpr (MI % 4 == 2) load_frags2<AT, BM>(af + MI - 2, sa, wm * (MI * 16) + (MI - 2) * 16, lane);
+                load_tile_frags(af, bfr, cur);
                 const int younger = min(S - 2, nkt - 2 - kt);   // tiles younger than kt+1 still allowed in flight
-                if (grp == 1 && kt + 1 < nkt) {
-                    if (younger >= 2) wait_vmcnt<2 * LPT>();
-                    else if (younger == 1) wait_vmcnt<LPT>();
-                    else wait_vmcnt<0>();
-                }
+                if (grp == 1 && kt + 1 < nkt) wait_younger<LPT>(younger);
                 __builtin_amdgcn_s_barrier();
                 // ---- COMPUTE segment
                 __builtin_amdgcn_sched_barrier(0);
@@ -932,11 +713,7 @@ __device__ __forceinline__ void gemm3_body(const bf16_t* __restrict__ A, const b
                     for (int ni = 0; ni < 4; ++ni)
                         acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[ni], af[mi], acc[mi][ni], 0, 0, 0);
                 __builtin_amdgcn_s_setprio(0);
-                if (grp == 0 && kt + 1 < nkt) {
-                    if (younger >= 2) wait_vmcnt<2 * LPT>();
-                    else if (younger == 1) wait_vmcnt<LPT>();
-                    else wait_vmcnt<0>();
-                }
+                if (grp == 0 && kt + 1 < nkt) wait_younger<LPT>(younger);
                 __builtin_amdgcn_sched_barrier(0);
                 __builtin_amdgcn_s_barrier();
                 cur = cur == S - 1 ? 0 : cur + 1;
@@ -1248,9 +1025,7 @@ __global__ __launch_bounds__(NT, (BN == 256 || BMT == 384) ? 1 : 2) void gemm3_g
     const GroupProblem& P = g.p[q];
     const int bid = gid - P.wg_begin;
     EpiArgs e;
-    e.C = P.C; e.C2 = nullptr; e.bias = nullptr; e.aux = nullptr; e.colsum = nullptr; e.ldc = P.ldc; e.seg_rows = 1; e.seg_valid = 1;
-    e.alpha = 1.f; e.rowmap = nullptr; e.sa = nullptr; e.sb = nullptr; e.lds_a = 0; e.lds_b = 0; e.q_out = nullptr; e.q_scales = nullptr; e.ld_q = 0;
-    e.pair_ws = nullptr; e.pair_flags = nullptr;
+    e.C = P.C; e.ldc = P.ldc;
     gemm3_body<true, true, EPI, BN, SCHED, 0, BMT>(P.A, P.B, P.lda, P.ldb, P.M, P.N, P.K, P.tiles_n, P.split, P.kps, e, bid, P.nwg, true);
 }
 
@@ -1337,22 +1112,14 @@ int launch(const wj_gemm_args* a, hipStream_t s) {
     e.seg_rows = a->seg_rows > 0 ? a->seg_rows : 1; e.seg_valid = a->seg_rows > 0 ? a->seg_valid : 1;
     e.alpha = a->alpha;
     e.rowmap = a->rowmap;
-    e.sa = nullptr; e.sb = nullptr; e.lds_a = 0; e.lds_b = 0; e.q_out = nullptr; e.q_scales = nullptr; e.ld_q = 0;
-    e.pair_ws = nullptr; e.pair_flags = nullptr;
     if (pair) {
         e.pair_flags = (unsigned*)a->workspace;
         e.pair_ws = (float*)((char*)a->workspace + 4096L * ((tiles_m * tiles_n * 8 + 4095) / 4096));
     }
-    auto kern = gemm3_kernel<AT, BT, EPI, BN, SCHED, GATHER>;
-    constexpr int lds = Cfg<BN>::LDS_BYTES;
-    static int attr = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (attr != hipSuccess) return WJ_ERR_LAUNCH;
     // pairs: every XCD gets both roles of its run of tiles (ceil(tiles / 8) of each; spare workgroups leave at once)
     const int nwg = pair ? 16 * ((tiles_m * tiles_n + 7) / 8) : tiles_m * tiles_n * split;
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(NT), lds, s, (const bf16_t*)a->A, (const bf16_t*)a->B, (long)a->lda,
-                       (long)a->ldb, a->M, a->N, a->K, tiles_n, split, kps, e);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return launch_with_lds<gemm3_kernel<AT, BT, EPI, BN, SCHED, GATHER>>(dim3(nwg), Cfg<BN>::LDS_BYTES, s, (const bf16_t*)a->A, (const bf16_t*)a->B,
+                                                                         (long)a->lda, (long)a->ldb, a->M, a->N, a->K, tiles_n, split, kps, e);
 }
 
 // Deterministic form of the split-K weight gradient (col-form A and B; GATHER 2: the sparse conv wgrad over its row list): the K slices
@@ -1364,17 +1131,10 @@ int launch_slab(const wj_gemm_args* a, hipStream_t s) {
     int split, kps;
     split_plan(a->K, a->split_k, split, kps);
     EpiArgs e;
-    e.C = a->workspace; e.C2 = nullptr; e.bias = nullptr; e.aux = nullptr; e.ldc = a->ldc; e.colsum = nullptr; e.seg_rows = 1; e.seg_valid = 1;
-    e.alpha = 1.f; e.rowmap = a->rowmap;
-    e.sa = nullptr; e.sb = nullptr; e.lds_a = 0; e.lds_b = 0; e.q_out = nullptr; e.q_scales = nullptr; e.ld_q = 0;
-    e.pair_ws = nullptr; e.pair_flags = nullptr;
-    auto kern = gemm3_kernel<true, true, EPI_SLAB_F32, BN, 0, GATHER>;
-    constexpr int lds = Cfg<BN>::LDS_BYTES;
-    static int attr = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (attr != hipSuccess) return WJ_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n * split), dim3(NT), lds, s, (const bf16_t*)a->A, (const bf16_t*)a->B, (long)a->lda,
-                       (long)a->ldb, a->M, a->N, a->K, tiles_n, split, kps, e);
-    WJ_CHECK_LAUNCH();
+    e.C = a->workspace; e.ldc = a->ldc; e.rowmap = a->rowmap;
+    const int rc = launch_with_lds<gemm3_kernel<true, true, EPI_SLAB_F32, BN, 0, GATHER>>(dim3(tiles_m * tiles_n * split), Cfg<BN>::LDS_BYTES, s, (const bf16_t*)a->A,
+                                                                                         (const bf16_t*)a->B, (long)a->lda, (long)a->ldb, a->M, a->N, a->K, tiles_n, split, kps, e);
+    if (rc != WJ_OK) return rc;
     SlabTable g;
     g.n = 1;
     g.p[0] = SlabItem{(const float*)a->workspace, (float*)a->C, (long)a->ldc, (long)a->M * a->ldc, 0, a->N / 4, split, a->alpha};
@@ -1487,20 +1247,13 @@ template <int EPI>
 int launch_fp8(const wj_gemm_fp8_args* a, hipStream_t s) {
     const int tiles_m = (a->M + BM - 1) / BM, tiles_n = (a->N + 255) / 256;
     EpiArgs e;
-    e.C = a->C; e.C2 = a->epilogue == WJ_EPI_BIAS_GELU ? nullptr : a->C2; e.bias = a->bias; e.aux = nullptr; e.ldc = a->ldc; e.colsum = nullptr;
-    e.seg_rows = 1; e.seg_valid = 1; e.alpha = 1.f; e.rowmap = nullptr;
+    e.C = a->C; e.C2 = a->epilogue == WJ_EPI_BIAS_GELU ? nullptr : a->C2; e.bias = a->bias; e.ldc = a->ldc;
     e.sa = (const uint32_t*)a->scale_a; e.sb = (const uint32_t*)a->scale_b; e.lds_a = a->ld_scale_a; e.lds_b = a->ld_scale_b;
     e.q_out = (unsigned char*)a->q_out; e.q_scales = (uint32_t*)a->q_scales; e.ld_q = a->ld_q_scale;
-    e.pair_ws = nullptr; e.pair_flags = nullptr;
-    auto kern = gemm3_kernel<false, false, EPI, 256, 3, 0>;
     constexpr int lds = Cfg<256>::LDS_BYTES;     // 135168 >= ring (128 KiB) + two parities of block scales (4 KiB)
-    static_assert(lds >= 131072 + 4096, "LDS budget of the MX fp8 loop");
-    static int attr = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (attr != hipSuccess) return WJ_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(NT), lds, s, (const bf16_t*)a->A, (const bf16_t*)a->B, (long)a->lda, (long)a->ldb,
-                       a->M, a->N, a->K, tiles_n, 1, a->K, e);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    static_assert(lds >= (int)F8_SCALE_OFF + 4096, "LDS budget of the MX fp8 loop");
+    return launch_with_lds<gemm3_kernel<false, false, EPI, 256, 3, 0>>(dim3(tiles_m * tiles_n), lds, s, (const bf16_t*)a->A, (const bf16_t*)a->B, (long)a->lda,
+                                                                       (long)a->ldb, a->M, a->N, a->K, tiles_n, 1, a->K, e);
 }
 
 extern "C" int wj_gemm_mxfp8(const wj_gemm_fp8_args* a, void* stream) {
@@ -1567,6 +1320,7 @@ template <int BN, int BMT = 256, int SCHED = 0>
 int launch_grouped(const wj_wgrad_group_args* a, hipStream_t s) {
     GroupTable g;
     const int begin = plan_group<BN, BMT>(a, g);
+    constexpr int lds = Cfg<BN, BMT>::LDS_BYTES;
     if (a->deterministic && group_slab_need(g) > 0) {
         // store-and-sum form: problem x's slices go to slabs [split_x][M_x][ldc_x], back to back in the workspace; one reduction launch
         SlabTable r;
@@ -1580,64 +1334,63 @@ int launch_grouped(const wj_wgrad_group_args* a, hipStream_t s) {
             P.C = ws;
             ws += (long)P.split * P.M * P.ldc;
         }
-        auto kern = gemm3_grouped_wgrad_kernel<BN, BMT, SCHED, EPI_SLAB_F32>;
-        constexpr int lds = Cfg<BN, BMT>::LDS_BYTES;
-        static int attr = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (attr != hipSuccess) return WJ_ERR_LAUNCH;
-        hipLaunchKernelGGL(kern, dim3(begin), dim3(NT), lds, s, g);
-        WJ_CHECK_LAUNCH();
-        return launch_slab_reduce(r, s);
+        const int rc = launch_with_lds<gemm3_grouped_wgrad_kernel<BN, BMT, SCHED, EPI_SLAB_F32>>(dim3(begin), lds, s, g);
+        return rc != WJ_OK ? rc : launch_slab_reduce(r, s);
     }
-    auto kern = gemm3_grouped_wgrad_kernel<BN, BMT, SCHED>;
-    constexpr int lds = Cfg<BN, BMT>::LDS_BYTES;
-    static int attr = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (attr != hipSuccess) return WJ_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(begin), dim3(NT), lds, s, g);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return launch_with_lds<gemm3_grouped_wgrad_kernel<BN, BMT, SCHED>>(dim3(begin), lds, s, g);
 }
 
-// slab bytes of the deterministic form of this group (0: not deterministic, malformed, or no problem is split) --
-// wj_workspace_bytes("wj_wgrad_grouped", args).  Mirrors the tile choice of wj_wgrad_grouped below.
-int64_t wj_wgrad_group_ws_bytes(const wj_wgrad_group_args* a) {
-    if (!a || !a->deterministic || a->n < 1 || a->n > GROUP_MAX) return 0;
+// The tile form of a grouped launch, from the shapes of the group (all positive): 256 x 256 where every N fills it; 384 x 128 where every
+// problem is a multiple of 384 rows x 128 columns (the predictor: d = 384 -- no half-empty row tiles; WJ_WGRAD_384=0: the 256 x 128 tile,
+// round 4; =2: the ping-pong schedule on the 384 x 128 tile); else 256 x 128.  ONE place for the launch and the workspace query.
+enum GroupTile { GT_256x256, GT_256x128, GT_384x128, GT_384x128_PINGPONG };
+static GroupTile group_tile(const wj_wgrad_group_args* a) {
+    static const int m384_mode = wj_lab_env_int("WJ_WGRAD_384", 1);
     bool wide = true, m384 = true;
     for (int x = 0; x < a->n; ++x) {
-        if (a->M[x] <= 0 || a->N[x] <= 0 || a->K[x] <= 0) return 0;
         wide = wide && a->N[x] % 256 == 0;
         m384 = m384 && a->M[x] % 384 == 0 && a->N[x] % 128 == 0;
     }
+    if (wide) return GT_256x256;
+    if (m384 && m384_mode == 1) return GT_384x128;
+    if (m384 && WJ_LAB_BUILD && m384_mode == 2) return GT_384x128_PINGPONG;
+    return GT_256x128;
+}
+
+// slab bytes of the deterministic form of this group (0: not deterministic, malformed, or no problem is split) --
+// wj_workspace_bytes("wj_wgrad_grouped", args)
+int64_t wj_wgrad_group_ws_bytes(const wj_wgrad_group_args* a) {
+    if (!a || !a->deterministic || a->n < 1 || a->n > GROUP_MAX) return 0;
+    for (int x = 0; x < a->n; ++x)
+        if (a->M[x] <= 0 || a->N[x] <= 0 || a->K[x] <= 0) return 0;
     GroupTable g;
-    if (wide) plan_group<256, 256>(a, g);
-    else if (m384 && wj_lab_env_int("WJ_WGRAD_384", 1) != 0) plan_group<128, 384>(a, g);
-    else plan_group<128, 256>(a, g);
+    switch (group_tile(a)) {
+        case GT_256x256: plan_group<256, 256>(a, g); break;
+        case GT_256x128: plan_group<128, 256>(a, g); break;
+        default: plan_group<128, 384>(a, g); break;
+    }
     return group_slab_need(g);
 }
 
 extern "C" int wj_wgrad_grouped(const wj_wgrad_group_args* a, void* stream) {
     WJ_CLEAR_STALE_ERROR();
     if (!a || a->n < 1 || a->n > GROUP_MAX) return WJ_ERR_ARG;
-    bool wide = true, m384 = true;
     for (int x = 0; x < a->n; ++x) {
         if (!a->A[x] || !a->B[x] || !a->C[x] || a->M[x] <= 0 || a->N[x] <= 0 || a->K[x] <= 0) return WJ_ERR_ARG;
         if ((a->M[x] & 7) || (a->N[x] & 7) || (a->lda[x] & 7) || (a->ldb[x] & 7) || (a->ldc[x] & 3)) return WJ_ERR_ARG;
         if (((uintptr_t)a->A[x] | (uintptr_t)a->B[x] | (uintptr_t)a->C[x]) & 15) return WJ_ERR_ARG;
-        wide = wide && a->N[x] % 256 == 0;
-        m384 = m384 && a->M[x] % 384 == 0 && a->N[x] % 128 == 0;
     }
-    // every problem a multiple of 384 rows x 128 columns (the predictor: d = 384): the 384 x 128 tile has no half-empty row tiles
-    // (WJ_WGRAD_384=0: the 256 x 128 tile, round 4; =2: the ping-pong schedule on the 384 x 128 tile)
-    static int m384_mode = -1;
-    if (m384_mode < 0) m384_mode = wj_lab_env_int("WJ_WGRAD_384", 1);
     if (a->deterministic) {
         // the need follows from the plan the launch below makes (same tile variant, same split factors)
         const long need = wj_wgrad_group_ws_bytes(a);
         if (need > 0 && (!a->workspace || a->workspace_bytes < need || ((uintptr_t)a->workspace & 15))) return WJ_ERR_ARG;
     }
-    if (wide) return launch_grouped<256>(a, (hipStream_t)stream);
-    if (m384 && m384_mode == 1) return launch_grouped<128, 384, 0>(a, (hipStream_t)stream);
-    if (m384 && m384_mode == 2) return launch_grouped<128, 384, 1>(a, (hipStream_t)stream);
-    return launch_grouped<128>(a, (hipStream_t)stream);
+    switch (group_tile(a)) {
+        case GT_256x256: return launch_grouped<256>(a, (hipStream_t)stream);
+        case GT_384x128: return launch_grouped<128, 384, 0>(a, (hipStream_t)stream);
+        case GT_384x128_PINGPONG: return launch_grouped<128, 384, 1>(a, (hipStream_t)stream);
+        default: return launch_grouped<128>(a, (hipStream_t)stream);
+    }
 }
 
 // scratch bytes wj_gemm_bf16 can use for this problem (0: none) -- wj_workspace_bytes("wj_gemm_bf16", args)

@@ -29,54 +29,24 @@
 //   * the last panel is SHIFTED inwards (M - 128) like the persistent kernel's edge tiles: same operands, same k order, same bits.
 // The accumulation order per output element is that of variants 0-3 (k ascending, 32 per MFMA, bias added last in fp32): bit-identical
 // to them; variant 4 starts from the bias and differs in the last place on <= 0.05 % of the elements.
-#include <atomic>
-#include "common.h"
-#include "../../include/wavjepa_hip.h"
+#include "gemm_pieces.h"
 #include "gemm_internal.h"
 
 namespace {
 
-constexpr int NT = 512;
 constexpr int PN = 384;                           // output width this build serves
 constexpr int THIRDS = PN / 128;
 constexpr unsigned SLOT = 16384u;                 // one K tile of A (128 rows) or one step of W (128 rows), 128 B per row
 constexpr unsigned A_RING = 0u, B_RING = 4u * SLOT;
 constexpr unsigned BIAS_OFF = 8u * SLOT;          // PN floats
 constexpr unsigned STRIP_OFF = BIAS_OFF + 2048u;  // [8 waves][16 rows x STRIP_ROW]: the epilogue's transpose, per wave, no barriers
-constexpr unsigned STRIP_ROW = 144u;
 constexpr int LDS_TOTAL = (int)(STRIP_OFF + 8u * 16u * STRIP_ROW);
-constexpr int EPI_STORES = 4 * THIRDS;            // global stores one wave's epilogue issues per item
+constexpr int EPI_STORES = 4 * THIRDS * strip_stores(true);   // global stores one wave's epilogue issues per item: 4 half-width blocks per third
 
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-
-struct QArgs {
-    const char* A;
-    const char* B;
-    char* C;
-    const float* bias;
-    long ldc_b;
-    unsigned lda_b, ldb_b;
-    int M, K, nitems, wpx;
+struct QArgs : RowArgs {
+    int nitems, wpx;
     int diag;                 // lab build (WJ_PANEL_DIAG): 1 = no W pieces, 2 = no A pieces, 4 = no MFMAs, 8 = no fragment reads, 16 = no stores (timing only: wrong results); 32 = K rotation per workgroup (correct results, other summation order)
 };
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// One LDS-DMA instruction: 64 lanes x 16 B from sbase + voff (per lane) to LDS bytes [lds_dst + 16 lane).  M0 is written here only.
-__device__ __forceinline__ void dma(unsigned voff, const char* sbase, unsigned lds_dst) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_dst) : "memory", "m0");
-}
-
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
-    bf16x2 p;
-    p[0] = f2bf(a);
-    p[1] = f2bf(b);
-    return __builtin_bit_cast(unsigned, p);
-}
 
 // The running state of the two prefetch streams (wave-uniform).
 struct Cursor {
@@ -140,34 +110,16 @@ __device__ __forceinline__ void step(f32x4 (&acc)[4][2 * THIRDS], bf16x8 (&af)[2
     __builtin_amdgcn_sched_barrier(0);
     // ---- fragments of step j + 1 into the other register set: W (slot_b now names step j + 1's slot) ...
     if (!(WJ_LAB_BUILD && (a.diag & 8))) {
-        const char* bs = smem + B_RING + slot_b * SLOT;
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-            bf[PB ^ 1][ni][0] = *reinterpret_cast<const bf16x8*>(bs + b_rd + ni * 2048);
-            bf[PB ^ 1][ni][1] = *reinterpret_cast<const bf16x8*>(bs + (b_rd ^ 64u) + ni * 2048);
-        }
+        read_frags<2>(&bf[PB ^ 1][0][0], smem + B_RING + slot_b * SLOT, b_rd, b_rd ^ 64u);
     }
     // ... and, in the last step of a K tile, the A fragments of the next K tile (slot_a, advanced in the K tile's first step, names the NEXT K tile's slot)
     if (SUB == THIRDS - 1 && !(WJ_LAB_BUILD && (a.diag & 8))) {
-        const char* as = smem + A_RING + slot_a * SLOT;
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi) {
-            af[PA ^ 1][mi][0] = *reinterpret_cast<const bf16x8*>(as + a_rd + mi * 2048);
-            af[PA ^ 1][mi][1] = *reinterpret_cast<const bf16x8*>(as + (a_rd ^ 64u) + mi * 2048);
-        }
+        read_frags<4>(&af[PA ^ 1][0][0], smem + A_RING + slot_a * SLOT, a_rd, a_rd ^ 64u);
     }
     __builtin_amdgcn_sched_barrier(0);
     // ---- multiply step j from the registers the previous step filled
     if (WJ_LAB_BUILD && (a.diag & 4)) return;
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-            acc[mi][SUB * 2 + ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[PB][ni][0], af[PA][mi][0], acc[mi][SUB * 2 + ni], 0, 0, 0);
-            acc[mi][SUB * 2 + ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[PB][ni][1], af[PA][mi][1], acc[mi][SUB * 2 + ni], 0, 0, 0);
-        }
-    __builtin_amdgcn_s_setprio(0);
+    mfma_cluster<Bf16Mma, 0, SUB * 2>(acc, &bf[PB][0][0], &af[PA][0][0]);
     __builtin_amdgcn_sched_barrier(0);
 }
 
@@ -175,12 +127,10 @@ __device__ __forceinline__ void step(f32x4 (&acc)[4][2 * THIRDS], bf16x8 (&af)[2
 // acc[mi][t * 2 + ni][r] = C[m0 + wm * 64 + mi * 16 + i][t * 128 + wn * 32 + ni * 16 + 4 g + r]   (i = lane & 15, g = lane >> 4)
 __device__ __forceinline__ void epilogue(f32x4 (&acc)[4][2 * THIRDS], char* smem, const QArgs& a, int m0, int wave, int lane) {
     const int wm = wave >> 2, wn = wave & 3;
-    const int i = lane & 15, g = lane >> 4;
-    char* strip = smem + STRIP_OFF + wave * (16 * STRIP_ROW);
-    char* wr = strip + i * STRIP_ROW + g * 8;                                   // + ni * 32
-    const int srow = lane >> 2, schunk = lane & 3;
-    const char* rd = strip + srow * STRIP_ROW + schunk * 16;
-    char* c0 = a.C + (long)(m0 + wm * 64 + srow) * a.ldc_b + (long)(wn * 32) * 2 + schunk * 16;
+    const int g = lane >> 4;
+    StripLane sl;
+    sl.init(smem + STRIP_OFF + wave * (16 * STRIP_ROW), lane, true);
+    char* c0 = a.C + (long)(m0 + wm * 64 + sl.srow) * a.ldc_b + (long)(wn * 32) * 2 + sl.schunk * 16;
     const float* bias = reinterpret_cast<const float*>(smem + BIAS_OFF) + wn * 32 + 4 * g;
 #pragma unroll
     for (int t = 0; t < THIRDS; ++t) {
@@ -189,22 +139,20 @@ __device__ __forceinline__ void epilogue(f32x4 (&acc)[4][2 * THIRDS], char* smem
         for (int ni = 0; ni < 2; ++ni) bv[ni] = *reinterpret_cast<const f32x4*>(bias + t * 128 + ni * 16);
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi) {
+            u32x2 o[2];
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni) {
                 const f32x4 v = acc[mi][t * 2 + ni] + bv[ni];
-                *reinterpret_cast<u32x2*>(wr + ni * 32) = u32x2{pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3])};
+                o[ni] = u32x2{pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3])};
             }
-            __builtin_amdgcn_wave_barrier();
-            const u32x4 o = *reinterpret_cast<const u32x4*>(rd);
-            __builtin_amdgcn_wave_barrier();
             // (lab build, diag 16: the stores go to ONE line per lane group -- same count, no write traffic)
             char* dst = (WJ_LAB_BUILD && (a.diag & 16)) ? a.C + (lane & 7) * 16 : c0 + (long)(mi * 16) * a.ldc_b + (long)(t * 128) * 2;
-            __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(dst));
+            strip_store(o, sl, dst, 0);
         }
     }
 }
 
-__global__ __launch_bounds__(NT, 1) void gemm_panel_kernel(QArgs a) {
+__global__ __launch_bounds__(GEMM_NT, 1) void gemm_panel_kernel(QArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -215,9 +163,8 @@ __global__ __launch_bounds__(NT, 1) void gemm_panel_kernel(QArgs a) {
 
     // ---- this workgroup's items: the panels [cstart, cstart + clen) of its XCD label, every wpx-th from q0
     const int xl = blockIdx.x & 7, q0 = blockIdx.x >> 3;
-    const int qn = a.nitems >> 3, qr = a.nitems & 7;
-    const int clen = qn + (xl < qr ? 1 : 0);
-    const int cstart = xl < qr ? xl * (qn + 1) : qr * (qn + 1) + (xl - qr) * qn;
+    const XcdRun run = xcd_run(a.nitems, xl);
+    const int clen = run.len, cstart = run.start;
     if (q0 >= clen) return;
     const int n_my = (clen - q0 + a.wpx - 1) / a.wpx;
 
@@ -225,21 +172,17 @@ __global__ __launch_bounds__(NT, 1) void gemm_panel_kernel(QArgs a) {
     if (t < PN) reinterpret_cast<float*>(smem + BIAS_OFF)[t] = a.bias ? a.bias[t] : 0.f;
 
     // ---- piece geometry: a slot is 16 instructions of 8 rows x 128 B; staging wave w (= wave & 3) issues rows 32 w + 8 u + lane / 8
-    // (u = 0..3); lane % 8 is the LDS chunk position, holding source chunk (lane % 8) ^ ((row >> 1) & 7) (the swizzle the fragment reads undo)
+    // (u = 0..3), swizzled as piece_voff has it
     unsigned dpiece[4], voff[4];
     const unsigned ld_b = a_wave ? a.lda_b : a.ldb_b;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const int r0 = 32 * (wave & 3) + 8 * u;
         dpiece[u] = lds0 + (unsigned)r0 * 128u;
-        const int row = r0 + (lane >> 3);
-        voff[u] = (unsigned)row * ld_b + (unsigned)(((lane & 7) ^ ((row >> 1) & 7)) * 16);
+        voff[u] = piece_voff(r0, lane, ld_b);
     }
-    // fragment read offsets inside a slot: lane (i, g) reads row (block + i), chunk g (k 0-31) and g ^ 4 (k 32-63)
-    const int i = lane & 15, g = lane >> 4;
-    const unsigned sw = (unsigned)((g ^ ((i >> 1) & 7)) << 4);
-    const unsigned a_rd = (unsigned)((wm * 64 + i) * 128) + sw;
-    const unsigned b_rd = (unsigned)((wn * 32 + i) * 128) + sw;
+    // fragment read offsets inside a slot
+    const unsigned a_rd = frag_off(wm * 64, lane), b_rd = frag_off(wn * 32, lane);
 
     // K rotation (lab build, WJ_PANEL_DIAG bit 32): workgroup w walks the K tiles of every item from tile rot(w) round to rot(w) - 1, so
     // that at any instant the chip's workgroups read DIFFERENT 128-byte columns of their A rows (all of them start together and move at
@@ -273,16 +216,8 @@ __global__ __launch_bounds__(NT, 1) void gemm_panel_kernel(QArgs a) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                 // the bias words
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni) {
-        bf[0][ni][0] = *reinterpret_cast<const bf16x8*>(smem + B_RING + b_rd + ni * 2048);
-        bf[0][ni][1] = *reinterpret_cast<const bf16x8*>(smem + B_RING + (b_rd ^ 64u) + ni * 2048);
-    }
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi) {
-        af[0][mi][0] = *reinterpret_cast<const bf16x8*>(smem + A_RING + a_rd + mi * 2048);
-        af[0][mi][1] = *reinterpret_cast<const bf16x8*>(smem + A_RING + (a_rd ^ 64u) + mi * 2048);
-    }
+    read_frags<2>(&bf[0][0][0], smem + B_RING, b_rd, b_rd ^ 64u);
+    read_frags<4>(&af[0][0][0], smem + A_RING, a_rd, a_rd ^ 64u);
     // slot_b: the slot the next W refill goes to = the slot of the step being multiplied; slot_a likewise for K tiles
     unsigned slot_b = 0, slot_a = 0;
     int lag_w = 0, lag_a = 0;
@@ -316,33 +251,19 @@ __global__ __launch_bounds__(NT, 1) void gemm_panel_kernel(QArgs a) {
 }  // namespace
 
 bool wj_gemm_panel_eligible(const wj_gemm_args* a) {
-    if (a->a_trans || a->b_trans || a->rowmap || a->split_k > 1 || a->colsum || a->aux) return false;
+    if (!row_form_common_ok(a, 128, 128) || a->colsum || a->aux) return false;
     if (a->epilogue != WJ_EPI_BF16) return false;
     if (a->N != PN || a->M < 128) return false;
     if (a->K < 256 || (a->K % 128)) return false;                   // K tiles come in pairs (register double-buffering), at least four
-    if ((a->lda & 7) || (a->ldb & 7) || (a->ldc & 7)) return false;
-    if (((uintptr_t)a->A | (uintptr_t)a->B | (uintptr_t)a->C | (uintptr_t)a->bias) & 15) return false;
-    if (a->lda * 2 * 128 >= (1l << 31) || a->ldb * 2 * 128 >= (1l << 31)) return false;   // 32-bit per-lane offsets inside a slot
     return true;
 }
 
 int wj_gemm_panel_launch(const wj_gemm_args* a, hipStream_t s) {
     if (!wj_gemm_panel_eligible(a)) return WJ_ERR_UNSUPPORTED;
     QArgs p;
-    p.A = (const char*)a->A; p.B = (const char*)a->B; p.C = (char*)a->C; p.bias = (const float*)a->bias;
-    p.ldc_b = a->ldc * 2; p.lda_b = (unsigned)(a->lda * 2); p.ldb_b = (unsigned)(a->ldb * 2);
-    p.M = a->M; p.K = a->K;
+    p.set(a);
     p.nitems = (a->M + 127) / 128;
     p.wpx = a->persist_cus > 0 ? (a->persist_cus > 32 ? 32 : a->persist_cus) : 32;
     p.diag = wj_lab_env_int("WJ_PANEL_DIAG", 0);              // (read per launch in the lab build: a timing tool sweeps it)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) return WJ_ERR_UNSUPPORTED;
-    static std::atomic<bool> lds_ok[32];
-    if (!lds_ok[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute((const void*)gemm_panel_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL) != hipSuccess) return WJ_ERR_LAUNCH;
-        lds_ok[dev].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(gemm_panel_kernel, dim3(8 * p.wpx), dim3(NT), LDS_TOTAL, s, p);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return launch_with_lds<gemm_panel_kernel>(dim3(8 * p.wpx), LDS_TOTAL, s, p);
 }
