@@ -120,6 +120,22 @@ def test_conv_layernorm_channel_extractor(monkeypatch, stacks):
     assert d_hip < Y.ACT_FACTOR * d_orc + Y.ACT_EPS
 
 
+@pytest.mark.parametrize("channels", [None, "own", "shared"])
+@pytest.mark.parametrize("mode", ["default", "layer_norm"])
+def test_engine_front_end_and_stand_alone_extractor_give_the_same_tokens(mode, channels):
+    """3 clips of 16000 samples, mono (99 tokens) or two channels through own / shared stacks (198 tokens): after an inference pass the
+    engine front-end's token slice and the stand-alone m.extract_audio(audio) are the same bits -- both callers run one walker."""
+    kw = dict(seconds=1.0, tokens=99) if channels is None else dict(seconds=1.0, tokens=198, in_channels=2, channel_stacks=channels)
+    m, _ = build(SMALL, **kw) if mode == "default" else build_ln(SMALL, True, **kw)
+    audio = torch.from_numpy(synth.synth_audio(3, 1 if channels is None else 2, 16000, seed=31)).to(torch.bfloat16).to(dev())
+    m.get_audio_representation(audio, None)
+    got = m._engine.front.tokens()
+    want = m.extract_audio(audio)
+    assert m._engine.conv_ln == (mode == "layer_norm") and len(m._engine.stacks) == (2 if channels == "own" else 1)
+    assert got.shape == want.shape == (3, 99 if channels is None else 198, 64) and got.dtype == want.dtype == torch.bfloat16
+    assert float(want.float().abs().max()) > 0 and torch.equal(got, want)
+
+
 def test_conv_layernorm_inference_representation(monkeypatch):
     """get_audio_representation on 3 clips, with a key-padding mask on one of them and with None, against J.audio_representation."""
     patch_oracle(monkeypatch)

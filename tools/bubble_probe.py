@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Is the main stream waiting for the HOST between the front-end and the student's first kernel?  Two events recorded on the main stream
-around engine._conv_rows (host-side NumPy list building + one upload): with the host running ahead of the GPU their distance is the copy's
+around the conv front-end's active_rows (host-side NumPy list building + one upload): with the host running ahead of the GPU their distance is the copy's
 ~0.1 ms; with the host just in time it is the host's own time in that function.  Unprofiled, steady state."""
 import os
 import sys
@@ -23,7 +23,7 @@ src = SyntheticAudioSource(masker, batch_size=32, samples_per_audio=8, n_tokens=
 runner = StepRunner(model, gradient_clip_val=5.0)
 eng = model._ensure_engine()
 evs, host = [], []
-orig = eng._conv_rows
+orig = eng.front.active_rows
 
 
 def wrapped(plan):
@@ -37,13 +37,13 @@ def wrapped(plan):
     return r
 
 
-eng._conv_rows = wrapped
+eng.front.active_rows = wrapped
 for i in range(30):
     runner.step(src.next_batch(), i)
 torch.cuda.synchronize()
-# _conv_rows is called twice per step (forward: builds and uploads; backward: cached) -- report the forward calls (the longer host times)
+# active_rows is called twice per step (forward: builds and uploads; backward: cached) -- report the forward calls (the longer host times)
 gaps = [a.elapsed_time(b) for a, b in evs]
 pairs = sorted(zip(host, gaps), reverse=True)[:12]
-print("host ms in _conv_rows / GPU-side gap on the main stream around it (12 longest host times of 30 steps):")
+print("host ms in active_rows / GPU-side gap on the main stream around it (12 longest host times of 30 steps):")
 for h, g in pairs:
     print(f"  host {h:6.2f} ms   stream gap {g:6.2f} ms")

@@ -15,7 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from wavjepa_amd import ops  # noqa: E402
-from wavjepa_amd.engine import conv_geometry  # noqa: E402
+from wavjepa_amd.conv_frontend import conv_geometry  # noqa: E402
 
 SPEC = [(512, 10, 5)] + [(512, 3, 2)] * 4 + [(512, 2, 2)]
 

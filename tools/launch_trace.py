@@ -4,10 +4,11 @@ built model): every library launch with the scalar fields of its argument struct
 value's first appearance in the case (addresses differ from process to process, the order in which buffers are first touched does not);
 the members of the array-carrying entries (wj_wgrad_grouped, wj_colsum_f32_group, ...) the same way; every event record / wait.  Each
 line names the stream it went to (main / side / upload / other).  A case ends with `== <case>: <events> events, sha256 <hash>`; the
-WJ_DETERMINISTIC=1 cases add the sha256 of the loss bytes and of flat.g32 after the backward.
+WJ_DETERMINISTIC=1 cases add the sha256 of the loss bytes and of flat.g32 after the backward, the stand-alone extractor forwards that
+of their tokens.
 
 Two trees issue the same step exactly when these hashes agree: run this file unchanged in both (it uses only what `ops._run` and the
-array-carrying wrappers end in -- `_abi.call` -- and the `build` / `build_pre` / `masks` / `clips` helpers of the GPU tests) and diff the
+array-carrying wrappers end in -- `_abi.call` -- and the `build` / `build_pre` / `build_ln` / `masks` / `clips` helpers of the GPU tests) and diff the
 outputs.  `--summary` prints the `==` lines only; a substring argument selects cases."""
 import ctypes
 import hashlib
@@ -22,7 +23,8 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 sys.path[:0] = [ROOT, GOLDEN]
 import synth  # noqa: E402
 from tests import test_denoiser_gpu as TD  # noqa: E402
-from tests.test_jepa_gpu import BASE, SMALL, build, dev  # noqa: E402
+from tests.test_conv_layernorm_gpu import build_ln  # noqa: E402
+from tests.test_jepa_gpu import BASE, SMALL, PinnedRng, build, dev  # noqa: E402
 from tests.test_prenorm_gpu import build_pre, clips, masks  # noqa: E402
 from wavjepa_amd import _abi, engine as E  # noqa: E402
 
@@ -92,10 +94,28 @@ class Trace:
 
 
 def sha(t) -> str:
-    return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
+    t = t.detach().contiguous()
+    return hashlib.sha256((t.view(torch.int16) if t.dtype == torch.bfloat16 else t).cpu().numpy().tobytes()).hexdigest()
 
 
-def jepa_step(layout, cfg=SMALL, ragged=True, env=None, infer=False, fp8=False):
+def two_channel_batch():
+    """3 two-channel clips of 16000 samples (198 tokens) with channel-based masks: test_conv_layernorm_channel_extractor's."""
+    from wavjepa_amd.masking import TimeInverseBlockMasker
+    with PinnedRng(4100):
+        ctx, tgt, vis = TimeInverseBlockMasker(4, 0.65, 10, 0.25, 10, 0.1, channel_based_masking=True, channel_major=True)(
+            batch_size=3, n_times=198, in_channels=2)
+    return torch.from_numpy(synth.synth_audio(3, 2, 16000, seed=31)).to(torch.bfloat16).to(dev()), ctx, tgt, vis
+
+
+def build_case(layout, cfg, conv_bias=None, channels=None, **kw):
+    """conv_bias None: mode "default", else mode "layer_norm" with / without conv bias; channels "own" / "shared": two-channel extractor."""
+    if channels is not None:
+        kw.update(seconds=1.0, tokens=198, in_channels=2, channel_stacks=channels)
+    builder = build if layout == "post" else (lambda c, **k: build_pre(c, layout, **k))
+    return builder(cfg, **kw) if conv_bias is None else build_ln(cfg, conv_bias, builder=builder, **kw)
+
+
+def jepa_step(layout, cfg=SMALL, ragged=True, env=None, infer=False, fp8=False, conv_bias=None, channels=None):
     """One case: a fresh model (built, engine and side stream included, before the trace starts), then one training step or inference."""
     def run():
         kw = {}
@@ -108,10 +128,12 @@ def jepa_step(layout, cfg=SMALL, ragged=True, env=None, infer=False, fp8=False):
             audio = torch.from_numpy(synth.synth_audio(3, 1, 32159, seed=9)).to(dev())
             pad = torch.zeros(3, 200, dtype=torch.bool)
             pad[1, 150:] = True
+        elif channels is not None:
+            audio, ctx, tgt, vis = two_channel_batch()
         else:
             ctx, tgt, vis = masks(GOLDEN, 4)
             audio = clips(4)
-        m, _ = build(cfg, **kw) if layout == "post" else build_pre(cfg, layout, **kw)
+        m, _ = build_case(layout, cfg, conv_bias, channels, **kw)
         eng = m._ensure_engine()
         eng.ragged, eng.fp8 = ragged, fp8
         extra = []
@@ -142,6 +164,17 @@ def denoiser_step():
     return run, {}
 
 
+def standalone_forward(conv_bias=None, channels=None):
+    """The extractor's own forward, m.extract_audio(audio), outside the engine; adds the sha256 of the tokens."""
+    def run():
+        audio = clips(3) if channels is None else two_channel_batch()[0]
+        m, _ = build_case("post", SMALL, conv_bias, channels)
+        with Trace(m._ensure_engine()) as tr:
+            tok = m.extract_audio(audio)
+        return tr.lines, ["tokens sha256 " + sha(tok)]
+    return run, {}
+
+
 CASES = {}
 for lay in ("post", "both"):
     CASES[f"{lay} ragged"] = jepa_step(lay)
@@ -154,6 +187,23 @@ for lay in ("post", "both"):
     for top_k in (1, 8):
         CASES[f"{lay} top_k={top_k}"] = jepa_step(lay, cfg=dict(SMALL, top_k=top_k))
     CASES[f"{lay} inference"] = jepa_step(lay, infer=True)
+# the conv front-end: mode "layer_norm", the conv switches, the two-channel extractor, the stand-alone forward
+for bias in (True, False):
+    CASES[f"layer_norm ragged bias={bias}"] = jepa_step("post", conv_bias=bias)
+    CASES[f"layer_norm dense bias={bias}"] = jepa_step("post", ragged=False, conv_bias=bias)
+for switch in ("WJ_DETERMINISTIC=1", "WJ_SIDE_STREAM=0"):
+    CASES[f"layer_norm {switch}"] = jepa_step("post", env=dict([switch.split("=")]), conv_bias=True)
+for switch in ("WJ_SPARSE_CONV=0", "WJ_CONV_WGRAD_SIDE=0"):
+    CASES[f"post {switch}"] = jepa_step("post", env=dict([switch.split("=")]))
+    CASES[f"layer_norm {switch}"] = jepa_step("post", env=dict([switch.split("=")]), conv_bias=True)
+for switch in ("WJ_FUSE_CONV_GELU_BWD=0", "WJ_FUSE_ADD_POS=0"):
+    CASES[f"post {switch}"] = jepa_step("post", env=dict([switch.split("=")]))
+for mode, bias in (("default", None), ("layer_norm", True)):
+    for stacks in ("own", "shared"):
+        CASES[f"{mode} two-channel {stacks}"] = jepa_step("post", conv_bias=bias, channels=stacks)
+        CASES[f"{mode} stand-alone two-channel {stacks}"] = standalone_forward(bias, stacks)
+    CASES[f"{mode} stand-alone mono"] = standalone_forward(bias)
+CASES["layer_norm two-channel own WJ_DETERMINISTIC=1"] = jepa_step("post", env={"WJ_DETERMINISTIC": "1"}, conv_bias=True, channels="own")
 CASES["post fp8"] = jepa_step("post", cfg=BASE, fp8=True)
 CASES["denoiser"] = denoiser_step()
 

@@ -6,9 +6,8 @@ reference wavjepa/jepa.py:365-419 (forward), :230-270 (teacher targets), :335-36
 backward of those ops.  Activations are token-major bf16/fp32 buffers sized once per batch size; the residual
 stream is fp32 and every GEMM operand is bf16, exactly the dtype flow bf16 autocast produces on the reference.
 
-Conv front-end layout: channels-last [clip][row][C] with per-clip row counts P_l chosen so that
-P_{l-1} = stride_l * P_l; a strided conv is then ONE GEMM with lda = stride*C and K = k*C over all clips
-(rows >= L_l of a clip are padding, kept at zero).
+The conv front-end (audio -> the last conv layer's output, and its backward) is conv_frontend.ConvFrontend; the engine adds
+feature_norms, the mapper and the positions behind it (_frontend) and their backward in front of it (_frontend_bwd).
 """
 from __future__ import annotations
 
@@ -19,18 +18,8 @@ import numpy as np
 import torch
 
 from . import ops
+from .conv_frontend import ConvFrontend, ConvLayerParams, _empty, conv_active_rows, conv_geometry  # noqa: F401  (re-exported)
 from .params import FlatParams
-
-
-def _empty(*shape, dtype, device):
-    """Arena buffers are uninitialised by design (every kernel writes what a later kernel reads).  WJ_ARENA_FILL=nan poisons
-    them instead, so that a read of never-written memory shows up as NaN in the results (tools/debug_order.py)."""
-    import os
-    if os.environ.get("WJ_ARENA_FILL", "") == "nan":
-        if not dtype.is_floating_point:          # fp8 operand bytes: 0x7f is the e4m3 NaN encoding
-            return torch.full(shape, 0x7f, dtype=dtype, device=device)
-        return torch.full(shape, float("nan"), dtype=dtype, device=device)
-    return torch.empty(*shape, dtype=dtype, device=device)
 
 
 @dataclass
@@ -221,64 +210,6 @@ def make_mask_plan(ctx_mask, target_indices, vis_mask, device) -> MaskPlan:
                     ragged_ok=ragged_ok, ctx_np=ctx_np)
 
 
-def conv_geometry(n_samples: int, spec) -> Tuple[List[int], List[int]]:
-    """Valid output lengths L_l and padded per-clip row counts P_l with P_{l-1} = stride_l * P_l and enough zero
-    padding rows for the dgrad taps (P_l - L_l >= ceil(k_l / s_l) - 1, at least 1)."""
-    L, cur = [], n_samples
-    for _, k, s in spec:
-        cur = (cur - k) // s + 1
-        L.append(cur)
-    n = len(spec)
-    need = [max(1, -(-spec[l][1] // spec[l][2]) - 1) for l in range(n)]
-    p_last = L[-1] + need[-1]
-    while True:
-        P = [0] * n
-        P[-1] = p_last
-        for l in range(n - 2, -1, -1):
-            P[l] = P[l + 1] * spec[l + 1][2]
-        if all(P[l] >= L[l] + need[l] for l in range(n)):
-            return L, P
-        p_last += 1
-
-
-def conv_active_rows(keep: np.ndarray, P: Sequence[int], spec) -> Dict[int, Tuple[np.ndarray, np.ndarray]]:
-    """Rows of every conv layer's output that can carry a gradient when only `keep` [N, T] (bool) rows of the LAST layer's
-    output do (the student sees the context tokens only, so ~80 % of the conv backward would multiply zeros).
-
-    Returns {l: (act, ext)} of int32 GLOBAL row indices (clip * P[l] + row), ascending:
-      act[l]: rows of layer l's output gradient that are written this step (consumed by GELU', wgrad, and cleared after);
-      ext[l]: act[l] grown by the dgrad halo (ceil(k/s) - 1 rows after every run): the logical rows of the dgrad GEMM, whose
-              outputs s*g + rho, rho < s, are exactly act[l-1].
-    Layer 0 (no GEMM dgrad below it): (act, per-clip offsets int32 [N+1] into act)."""
-    N, T = keep.shape
-    edge = np.diff(np.concatenate([np.zeros((N, 1), np.int8), keep.astype(np.int8), np.zeros((N, 1), np.int8)], axis=1), axis=1)
-    clip, start = np.nonzero(edge == 1)
-    _, end = np.nonzero(edge == -1)          # same (clip, position) order: the i-th end closes the i-th start
-
-    def expand(clip, start, end, rows_per_clip):
-        n = end - start
-        if n.size == 0:
-            return np.zeros(0, np.int32)
-        first = np.cumsum(n) - n
-        return (np.repeat(clip.astype(np.int64) * rows_per_clip + start - first, n) + np.arange(int(n.sum()))).astype(np.int32)
-
-    out: Dict[int, Tuple[np.ndarray, Optional[np.ndarray]]] = {}
-    for l in range(len(spec) - 1, 0, -1):
-        _, k, s = spec[l]
-        act = expand(clip, start, end, P[l])
-        grown = end + (-(-k // s) - 1)
-        if start.size:                       # merge runs that now touch or overlap inside a clip
-            new = np.ones(start.size, bool)
-            new[1:] = (clip[1:] != clip[:-1]) | (start[1:] > grown[:-1])
-            head = np.flatnonzero(new)
-            clip, start, grown = clip[head], start[head], np.maximum.reduceat(grown, head)
-        out[l] = (act, expand(clip, start, grown, P[l]))
-        start, end = start * s, grown * s
-    per_clip = np.bincount(clip, weights=end - start, minlength=N).astype(np.int64)
-    out[0] = (expand(clip, start, end, P[0]), np.concatenate([[0], np.cumsum(per_clip)]).astype(np.int32))
-    return out
-
-
 class _Layer:
     """Raw device pointers of one transformer layer (weights bf16, biases / LN params fp32, gradients fp32)."""
     __slots__ = ("wqkv", "bqkv", "wo", "bo", "w1", "b1", "w2", "b2", "g1", "be1", "g2", "be2",
@@ -321,10 +252,7 @@ class JepaEngine:
         # fp32 tables on this device are used in place (load_state_dict / the data-parallel broadcast write through); a converted copy
         # (other dtype or device) is refreshed from its source in prepare_weights
         self._pos_src = (pos_enc, pos_dec)
-        self.L, self.P = conv_geometry(cfg.n_samples, cfg.conv_spec)
         self.S = max(1, int(cfg.streams))            # channel streams through mono conv stacks
-        self.Tc = self.L[-1]                         # conv frames per stream
-        self.T = self.S * self.Tc                    # tokens per clip: channel-major "B (C S)" flatten
         self.stacks = list(cfg.conv_prefixes)        # distinct conv stacks; stream c uses stacks[min(c, len - 1)]
         assert len(self.stacks) in (1, self.S)
         self.C = cfg.conv_spec[-1][0]
@@ -337,6 +265,12 @@ class JepaEngine:
             raise NotImplementedError("conv_bias=True needs mode='layer_norm': the GroupNorm front-end's kernels carry no conv bias")
         if self.conv_ln and self.C not in (64, 128, 256, 512):
             raise NotImplementedError(f"mode='layer_norm' runs conv widths 64 / 128 / 256 / 512, not {self.C}")
+        # audio -> post[-1] and back: geometry, conv buffers, weight layouts, forward and backward walkers (conv_frontend.py)
+        self.front = ConvFrontend(cfg.conv_spec, cfg.in_channels, cfg.n_samples, self.S, self._conv_params(), self.conv_ln, self.dev,
+                                  upload=pack_upload)
+        self.L, self.P = self.front.L, self.front.P
+        self.Tc = self.L[-1]                         # conv frames per stream
+        self.T = self.S * self.Tc                    # tokens per clip: channel-major "B (C S)" flatten
         assert cfg.d_enc % cfg.h_enc == 0 and cfg.d_dec % cfg.h_dec == 0
         # clips of more than 416 tokens run the block-streamed attention kernels (ops.attn_entries), which take 32- and 64-wide heads
         if self.T > ops.ATTN_STREAM_T_MAX:
@@ -359,7 +293,6 @@ class JepaEngine:
         self.ragged_step = False
         # conv backward over the active rows only (needs a ragged step and k >= stride in every GEMM conv layer)
         self.sparse_conv = _os.environ.get("WJ_SPARSE_CONV", "1") != "0" and all(k >= st for _, k, st in cfg.conv_spec[1:])
-        self._conv_grads_dirty = False
         # deterministic mode (WJ_DETERMINISTIC=1, or engine.deterministic = True before a step): every float sum of the backward whose
         # order follows arrival order by default -- the split-K weight gradients, the column-sum folds, the attention backward's LDS
         # sums -- takes its store-and-sum form (include/wavjepa_hip.h: the `deterministic` fields).  Loss, gradients, parameters and Adam
@@ -393,7 +326,6 @@ class JepaEngine:
         # measures the kernels the timed step runs.
         self.pair_split = _os.environ.get("WJ_PAIR_SPLIT", "0") == "1"
         self.pair_ws = None
-        self._conv_w_fresh = False
         self.defer_folds = _os.environ.get("WJ_DEFER_FOLDS", "1") != "0"
         self.fuse_add_pos = _os.environ.get("WJ_FUSE_ADD_POS", "1") != "0"     # 0: mapper GEMM + wj_add_pos as two launches
         self.mapper_wgrad_side = _os.environ.get("WJ_MAPPER_WGRAD_SIDE", "1") != "0"
@@ -410,8 +342,6 @@ class JepaEngine:
         self._folds = []
         self._bind_params()
         self._bind_wt()
-        self._conv_w: Dict[str, torch.Tensor] = {}
-        self._alloc_conv_weights()
 
     def _pick_side_stream(self) -> torch.cuda.Stream:
         """A second stream that really runs beside the current one.  HIP deals streams onto a few hardware queues round-robin;
@@ -466,6 +396,18 @@ class JepaEngine:
         self.dec_layers = [_layer_ptrs(f, f"decoder.layers.{i}.", False) for i in range(c.l_dec)]
         self.tea_layers = [_layer_ptrs(f, f"teacher_encoder.layers.{i}.", True) for i in range(c.l_enc)]
 
+    def _conv_params(self) -> List[List[ConvLayerParams]]:
+        """[stack][layer] parameter and gradient pointers of the conv stacks (layer 0: bf16 weight; layers 1..: the fp32 master)."""
+        f, c = self.flat, self.cfg
+        norm = "2.1." if self.conv_ln else "2."          # Sequential(-, LayerNorm, -) behind every conv / GroupNorm behind conv 0
+
+        def layer(pre: str, l: int) -> ConvLayerParams:
+            w, b = f"{pre}{l}.0.weight", f"{pre}{l}.0.bias" if c.conv_bias else None
+            g, be = (f"{pre}{l}.{norm}weight", f"{pre}{l}.{norm}bias") if self.conv_ln or l == 0 else (None, None)
+            ptr, gptr = (lambda n: None if n is None else f.ptr32(n)), (lambda n: None if n is None else f.gptr(n))
+            return ConvLayerParams(f.ptr16(w) if l == 0 else f.ptr32(w), ptr(b), ptr(g), ptr(be), gptr(w), gptr(b), gptr(g), gptr(be))
+        return [[layer(pre, l) for l in range(len(c.conv_spec))] for pre in self.stacks]
+
     def _bind_wt(self) -> None:
         """W^T shadows: one more bf16 buffer with the parameter layout, every 2-D transformer weight stored transposed at its own offset."""
         f = self.flat
@@ -509,26 +451,6 @@ class JepaEngine:
             return ()
         return tuple(k for k, n_out, k_in in (("wqkv", D, 3 * D), ("wo", D, D), ("w1", D, 4 * D), ("w2", 4 * D, D))
                      if self._row_form_pays(M, n_out) or (pairs and self._pair_pays(M, n_out, k_in)))
-
-    def _alloc_conv_weights(self) -> None:
-        C = self.C
-        for si in range(len(self.stacks)):
-            for l, (_, k, s) in enumerate(self.cfg.conv_spec):
-                if l == 0:
-                    continue
-                self._conv_w[f"{si}:wp{l}"] = _empty(C, k * C, dtype=torch.bfloat16, device=self.dev)
-                for rho in range(s):
-                    U = len(range(rho, k, s))
-                    if U > 0:
-                        self._conv_w[f"{si}:wd{l}_{rho}"] = _empty(U * C, C, dtype=torch.bfloat16, device=self.dev)
-                self._conv_w[f"{si}:dwp{l}"] = torch.zeros(C, k * C, dtype=torch.float32, device=self.dev)
-
-    def _stack_groups(self):
-        """[(stack index, first conv clip, clips)] for the conv GEMMs of a batch of self.N clips: one group over all S*N mono
-        clips when the streams share their weights, one group of N clips per stream otherwise (clips are channel-major)."""
-        if len(self.stacks) == 1:
-            return [(0, 0, self.N * self.S)]
-        return [(c, c * self.N, self.N) for c in range(self.S)]
 
     def _check_fp8(self) -> None:
         if self.fp8 and (self.cfg.norm_first_enc or self.cfg.norm_first_dec):
@@ -578,33 +500,9 @@ class JepaEngine:
         if self.fp8:
             self._fp8_weights()
         self._wt_fresh = None                       # the shadows follow p16; refreshed by the first backward that needs them
-        self._conv_w_fresh = False                  # GEMM layouts of conv layers 1..: rebuilt by the front-end, behind its conv0 launches
-
-    def _conv_weight_layouts(self) -> None:
-        """GEMM layouts of conv layers 1.. from the fp32 masters (20 launches of ~5 us).  Issued by the front-end AFTER the conv0 kernels
-        are queued: at the start of a step the GPU is idle, and the host needs ~15 us per launch -- behind conv0 (1.1 ms) they cost nothing,
-        in front of it they were 0.3 ms of idle GPU per step (rocprofv3 trace, tools/trace_gaps.py)."""
-        if self._conv_w_fresh:
-            return
-        f, C = self.flat, self.C
-        for si, pre in enumerate(self.stacks):
-            for l, (_, k, s) in enumerate(self.cfg.conv_spec):
-                if l == 0:
-                    continue
-                src = f.ptr32(f"{pre}{l}.0.weight")
-                ops.conv_weight_layout(src, self._conv_w[f"{si}:wp{l}"], C_out=C, C_in=C, k=k, mode=0)
-                for rho in range(s):
-                    U = len(range(rho, k, s))
-                    if U > 0:
-                        ops.conv_weight_layout(src, self._conv_w[f"{si}:wd{l}_{rho}"], C_out=C, C_in=C, k=k, mode=1, stride=s, rho=rho, U=U)
-        self._conv_w_fresh = True
+        self.front.w_fresh = False                  # GEMM layouts of conv layers 1..: rebuilt by the front-end, behind its conv0 launches
 
     # ------------------------------------------------------------------------------------------------ arena
-    def _rows(self, nrows: int, width: int, dtype, lead: int = 2, tail: int = 8) -> Tuple[torch.Tensor, int]:
-        """A zero-initialised [lead + nrows + tail][width] buffer; returns (tensor, pointer to row 0)."""
-        t = torch.zeros((lead + nrows + tail) * width, dtype=dtype, device=self.dev)
-        return t, t.data_ptr() + lead * width * t.element_size()
-
     def _alloc_stack(self, M: int, D: int, H: int, B: int, layers: int) -> List[_Acts]:
         bf, f32, dev = torch.bfloat16, torch.float32, self.dev
         out = []
@@ -662,40 +560,11 @@ class JepaEngine:
         self.N, self.G, self.M, self.Mp = N, G, M, Mp
         self._train_alloc = train
         Me, Md = self.cap_enc, self.cap_dec                   # rows of the student / predictor buffers (<= M / Mp)
-        nl = len(c.conv_spec)
-        Nc = N * self.S                               # mono conv clips (channel-major: clip index c*N + n)
-        # conv activations (post-GELU, and pre-GELU for layers >= 1) + their gradients
-        self.post, self.post_ptr, self.pre, self.pre_ptr = [], [], [None], [0]
-        self.dpost, self.dpost_ptr, self.dpre, self.dpre_ptr = [], [], [None], [0]
-        for l in range(nl):
-            t, p = self._rows(Nc * self.P[l], C, bf)
-            self.post.append(t); self.post_ptr.append(p)
-            if l > 0:
-                t, p = self._rows(Nc * self.P[l], C, bf)
-                self.pre.append(t); self.pre_ptr.append(p)
-            if train:
-                t, p = self._rows(Nc * self.P[l], C, bf)
-                self.dpost.append(t); self.dpost_ptr.append(p)
-                if l > 0:
-                    t, p = self._rows(Nc * self.P[l], C, bf)
-                    self.dpre.append(t); self.dpre_ptr.append(p)
+        self.front.alloc(N, train)                    # conv activations, statistics and their gradients
         if self.pair_split and self.pair_ws is None:
             # zero-filled ONCE; the library keeps its flags at zero between launches.  Sized for the largest problem that splits.
             self.pair_ws = torch.zeros(ops.workspace_bytes("wj_gemm_bf16", M=256 * (self.PAIR_TILES[1] // 2), N=512, K=2048, lda=2048, ldb=2048,
                                                            ldc=512, epilogue=ops.EPI_BF16), dtype=torch.uint8, device=dev)
-        taps = c.in_channels * c.conv_spec[0][1]
-        conv0_dims = dict(N=N, C_in=c.in_channels, C=C, k=c.conv_spec[0][1], L_out=self.L[0])      # per stream: N clips a call
-        if self.conv_ln:
-            # per-row LayerNorm statistics of every conv layer; layer 0's backward scratch (dense form: the largest)
-            self.cl_mean = [_empty(Nc * self.P[l], dtype=f32, device=dev) for l in range(nl)]
-            self.cl_rstd = [_empty(Nc * self.P[l], dtype=f32, device=dev) for l in range(nl)]
-            self.cl_ws_b = _empty(ops.workspace_bytes("wj_conv0_ln_gelu_bwd", max_rows=0, **conv0_dims) // 4, dtype=f32, device=dev) if train else None
-        else:
-            self.gn_stats = _empty(2, Nc, C, dtype=f32, device=dev)
-            self.gn_ws = _empty(ops.workspace_bytes("wj_conv0_gn_gelu_fwd", **conv0_dims) // 4, dtype=f32, device=dev)
-            self.gn_ws_b = _empty(ops.workspace_bytes("wj_conv0_gn_gelu_bwd", max_rows=0, **conv0_dims) // 4, dtype=f32, device=dev) if train else None
-            self.gn_yx = _empty(Nc, C, taps, dtype=f32, device=dev) if train else None     # forward sums the backward needs
-            self.gn_x1 = _empty(Nc, taps, dtype=f32, device=dev) if train else None
         self.fn_b = _empty(M, C, dtype=bf, device=dev)
         self.fn_mean = _empty(M, dtype=f32, device=dev)
         self.fn_rstd = _empty(M, dtype=f32, device=dev)
@@ -1301,13 +1170,10 @@ class JepaEngine:
     # ------------------------------------------------------------------------------------------------ front-end
     def _frontend(self, audio: torch.Tensor) -> None:
         """audio bf16 [N, C_in, L] -> lf (fp32) / lf_b (bf16) [N*T, d_enc]   (reference jepa.py:391-396)"""
-        c, f, N, C, S = self.cfg, self.flat, self.N, self.C, self.S
-        if self.conv_ln:
-            self._conv_stack_ln(audio)
-        else:
-            self._conv_stack_gn(audio)
+        c, f, C, S = self.cfg, self.flat, self.C, self.S
+        self.front.forward(audio)
         M, T = self.M, self.T
-        ops.layernorm_fwd(self.post_ptr[-1], f.ptr32("feature_norms.weight"), f.ptr32("feature_norms.bias"), M=M, D=C,
+        ops.layernorm_fwd(self.front.post_ptr[-1], f.ptr32("feature_norms.weight"), f.ptr32("feature_norms.bias"), M=M, D=C,
                           eps=c.norm_eps, y_bf16=self.fn_b, mean=self.fn_mean, rstd=self.fn_rstd, x_is_bf16=True,
                           in_seg=self.P[-1], in_valid=self.Tc, in_chan=S if S > 1 else 0)
         if self.has_mapper and self.fuse_add_pos and c.d_enc % 256 == 0 and C % 128 == 0:
@@ -1322,58 +1188,6 @@ class JepaEngine:
         else:
             src = self.fn_b
         ops.add_pos(src, self.pos_enc, M=M, T=T, D=c.d_enc, y_f32=self.lf, y_bf16=self.lf_b)
-
-    def _conv_stack_ln(self, audio: torch.Tensor) -> None:
-        """mode="layer_norm": the fused layer-0 kernel, then per layer the conv GEMM (bf16 pre-activations, + bias) and one
-        LayerNorm + GELU pass over its rows -> post[l] (bf16, clip padding rows 0); per-row mean / rstd kept for the backward."""
-        c, f, N, C, S = self.cfg, self.flat, self.N, self.C, self.S
-        _, k0, s0 = c.conv_spec[0]
-        audio_p = audio.data_ptr()
-        bias = (lambda pre, l: f.ptr32(f"{pre}{l}.0.bias")) if c.conv_bias else (lambda pre, l: None)
-        for ch in range(S):
-            pre = self.stacks[min(ch, len(self.stacks) - 1)]
-            r0 = ch * N * self.P[0]
-            ops.conv0_ln_fwd(audio_p + ch * c.n_samples * 2 if S > 1 else audio, f.ptr16(f"{pre}0.0.weight"), bias(pre, 0),
-                             f.ptr32(f"{pre}0.2.1.weight"), f.ptr32(f"{pre}0.2.1.bias"), self.post_ptr[0] + r0 * C * 2, self.cl_mean[0][r0:],
-                             self.cl_rstd[0][r0:], N=N, C_in=c.in_channels, L=c.n_samples, C=C, k=k0, stride=s0, L_out=self.L[0], P=self.P[0],
-                             audio_clip_stride=S * c.in_channels * c.n_samples if S > 1 else 0)
-        self._conv_weight_layouts()
-        for l in range(1, len(c.conv_spec)):
-            _, k, s = c.conv_spec[l]
-            for si, c0, nclips in self._stack_groups():
-                pre, r0, rows = self.stacks[si], c0 * self.P[l], nclips * self.P[l]
-                ops.gemm(self.post_ptr[l - 1] + c0 * self.P[l - 1] * C * 2, self._conv_w[f"{si}:wp{l}"], self.pre_ptr[l] + r0 * C * 2,
-                         M=rows, N=C, K=k * C, lda=s * C, ldb=k * C, ldc=C, bias=bias(pre, l), epilogue=ops.EPI_BF16)
-                ops.conv_ln_gelu_fwd(self.pre_ptr[l] + r0 * C * 2, f.ptr32(f"{pre}{l}.2.1.weight"), f.ptr32(f"{pre}{l}.2.1.bias"),
-                                     self.post_ptr[l] + r0 * C * 2, M=rows, C=C, mean=self.cl_mean[l][r0:], rstd=self.cl_rstd[l][r0:],
-                                     seg_rows=self.P[l], seg_valid=self.L[l])
-
-    def _conv_stack_gn(self, audio: torch.Tensor) -> None:
-        """mode="default": conv0 + GroupNorm + GELU, then one implicit GEMM with the fused GELU epilogue per layer."""
-        c, f, N, C, S = self.cfg, self.flat, self.N, self.C, self.S
-        _, k0, s0 = c.conv_spec[0]
-        taps = c.in_channels * k0
-        grad = torch.is_grad_enabled() and self.gn_yx is not None      # (an inference arena keeps no backward sums)
-        audio_p = audio.data_ptr()
-        for ch in range(S):                               # every stream: N mono clips (ConvFeatureExtractor: one stream, C_in channels)
-            pre = self.stacks[min(ch, len(self.stacks) - 1)]
-            c0 = ch * N                                   # first conv clip of this stream
-            ops.conv0_fwd(audio_p + ch * c.n_samples * 2 if S > 1 else audio, f.ptr16(f"{pre}0.0.weight"), f.ptr32(f"{pre}0.2.weight"),
-                          f.ptr32(f"{pre}0.2.bias"), self.post_ptr[0] + c0 * self.P[0] * C * 2, self.gn_stats[0, c0:], self.gn_stats[1, c0:],
-                          self.gn_ws, N=N, C_in=c.in_channels, L=c.n_samples, C=C, k=k0, stride=s0, L_out=self.L[0], P=self.P[0],
-                          yx=self.gn_yx[c0:] if grad else None, x1=self.gn_x1[c0:] if grad else None,
-                          audio_clip_stride=S * c.in_channels * c.n_samples if S > 1 else 0)
-        self._conv_weight_layouts()
-
-        def conv_layer(l: int, si: int, c0: int, nclips: int) -> None:
-            _, k, s = c.conv_spec[l]
-            ops.gemm(self.post_ptr[l - 1] + c0 * self.P[l - 1] * C * 2, self._conv_w[f"{si}:wp{l}"], self.pre_ptr[l] + c0 * self.P[l] * C * 2,
-                     C2=self.post_ptr[l] + c0 * self.P[l] * C * 2, M=nclips * self.P[l], N=C, K=k * C, lda=s * C, ldb=k * C, ldc=C,
-                     epilogue=ops.EPI_CONV_GELU, seg_rows=self.P[l], seg_valid=self.L[l])
-
-        for l in range(1, len(c.conv_spec)):
-            for si, c0, nclips in self._stack_groups():
-                conv_layer(l, si, c0, nclips)
 
     # ------------------------------------------------------------------------------------------------ forward
     def forward(self, audio: torch.Tensor, plan: MaskPlan) -> None:
@@ -1412,7 +1226,7 @@ class JepaEngine:
             # host-side list building + upload, hidden behind the forward kernels already queued.  (Building the lists later, behind
             # the student / predictor launches, measured the same outside the profiler -- 48.89 against 48.79 ms over three runs each --
             # and opened a 2-ms gap under rocprofv3, whose per-launch overhead makes the host the slower side.)
-            self._conv_rows(plan)
+            self.front.active_rows(plan)
         n_ctx = plan.n_ctx
         final = dict(mean=self.enc_fm, rstd=self.enc_fr)
         if rag:
@@ -1618,7 +1432,7 @@ class JepaEngine:
         """dy = d(local_features) fp32 [M, d_enc] (packed context rows on a ragged step) -> gradients of the mapper, feature_norms
         and the conv stack.  (JEPA: zero on non-context rows; the teacher branch is detached, jepa.py:408.)"""
         c, f = self.cfg, self.flat
-        N, M, C, De = self.N, self.M, self.C, c.d_enc
+        M, C, De = self.M, self.C, c.d_enc
         if rag:
             ops.unmask_rows_f32(dy, plan.inv, self.d_lf_b, M=M, D=De, src_is_f32=True, dst_is_bf16=True)
             if not self.has_mapper:
@@ -1634,194 +1448,12 @@ class JepaEngine:
             d_fn = self.d_fn
         else:
             d_fn = dy
-        nl = len(c.conv_spec)
         S, Tc = self.S, self.Tc
-        self._ln_bwd_direct(d_fn, self.post_ptr[-1], f.ptr32("feature_norms.weight"), self.fn_mean, self.fn_rstd, M=M, D=C,
-                            ds_bf16=self.dpost_ptr[-1], dgamma=f.gptr("feature_norms.weight"), dbeta=f.gptr("feature_norms.bias"),
+        self._ln_bwd_direct(d_fn, self.front.post_ptr[-1], f.ptr32("feature_norms.weight"), self.fn_mean, self.fn_rstd, M=M, D=C,
+                            ds_bf16=self.front.dpost_ptr[-1], dgamma=f.gptr("feature_norms.weight"), dbeta=f.gptr("feature_norms.bias"),
                             x_is_bf16=True, in_seg=self.P[-1], in_valid=Tc, out_seg=self.P[-1], out_valid=Tc, chan=S if S > 1 else 0)
-        sparse = rag and self.sparse_conv
-        if sparse:
-            act_rows = self._conv_rows(plan)
-            if self._conv_grads_dirty:       # a dense step left gradients everywhere: restore the all-zero state once
-                for t in self.dpost + self.dpre[1:]:
-                    t.zero_()
-                self._conv_grads_dirty = False
-        else:
-            self._conv_grads_dirty = True
-        groups = self._stack_groups()        # (stack, first conv clip, clips): one group, or one per channel stream
-        side_wgrad = sparse and self.use_side and self.conv_wgrad_side
-        ln = self.conv_ln
-        # mode="layer_norm": the LayerNorm sits between GELU' and the convolution, so GELU' cannot ride in the dgrad epilogue: plain dgrads
-        # into d(post[l - 1]) and one wj_conv_ln_gelu_bwd per layer where the default mode runs wj_gelu_bwd_bf16
-        fuse_gelu = self.fuse_conv_gelu_bwd and not ln
-        late_clear = []
-        for l in range(nl - 1, 0, -1):
-            _, k, s = c.conv_spec[l]
-            empty_phase = any(len(range(rho, k, s)) == 0 for rho in range(s))
-            if empty_phase:
-                self.dpost[l - 1].zero_()
-            for gi, (si, c0, nclips) in enumerate(groups):
-                rows = nclips * self.P[l]
-                r0, r0p = c0 * self.P[l] * C * 2, c0 * self.P[l - 1] * C * 2      # byte offsets of the group's first row (layers l, l-1)
-                dwp = self._conv_w[f"{si}:dwp{l}"]
-                if not side_wgrad:
-                    dwp.zero_()
-                if sparse:
-                    # Only act[l] rows of this layer's output gradient are non-zero.  Every gradient buffer is all-zero outside
-                    # the rows written this step (they are cleared again below), so the dgrad taps may read neighbours freely.
-                    # The lists hold rows of the WHOLE buffer; a group takes its contiguous slice of them.
-                    act, n_act, ext, n_ext = act_rows[l][gi]
-                    if ln:
-                        self._conv_ln_bwd(l, si, 0, self.N * S * self.P[l], rows=act, n_rows=n_act, clear_dpost=l < nl - 1)
-                    elif not (fuse_gelu and l < nl - 1):
-                        # (layers below the top one: d(pre) was written by the dgrad of the layer above, GELU' fused in its epilogue)
-                        ops.gelu_bwd_bf16(self.dpost_ptr[l], self.pre_ptr[l], self.dpre_ptr[l], 0, rows=act, n_rows=n_act, row_elems=C,
-                                          clear_dpost=l < nl - 1)
-                    if n_act > 0 and side_wgrad:
-                        # The layer's weight gradient (+ its scratch clear and the layout fold) on the SIDE stream: at this point of the
-                        # backward that stream is idle (every transformer weight gradient is out), and the main chain goes on with this
-                        # layer's dgrads, GELU' and the layer-0 pass -- d(pre[l]) is read by both and cleared only behind the join below.
-                        def conv_wgrad(l=l, k=k, s=s, dwp=dwp, act=act, n_act=n_act, si=si):
-                            dwp.zero_()
-                            ops.gemm(self.dpre_ptr[l], self.post_ptr[l - 1], dwp, M=C, N=k * C, K=n_act, lda=C, ldb=s * C, ldc=k * C, a_trans=1,
-                                     b_trans=1, epilogue=ops.EPI_ATOMIC_F32, split_k=ops.pick_split_k(C, k * C, n_act), rowmap=act, **self._det_kw())
-                            ops.conv_weight_layout(dwp, f.gptr(f"{self.stacks[si]}{l}.0.weight"), C_out=C, C_in=C, k=k, mode=2)
-                        self._on_side(conv_wgrad)
-                    elif n_act > 0:
-                        ops.gemm(self.dpre_ptr[l], self.post_ptr[l - 1], dwp, M=C, N=k * C, K=n_act, lda=C, ldb=s * C, ldc=k * C, a_trans=1,
-                                 b_trans=1, epilogue=ops.EPI_ATOMIC_F32, split_k=ops.pick_split_k(C, k * C, n_act), rowmap=act, **self._det_kw())
-                else:
-                    if ln:
-                        self._conv_ln_bwd(l, si, c0 * self.P[l], rows)
-                    else:
-                        ops.gelu_bwd_bf16(self.dpost_ptr[l] + r0, self.pre_ptr[l] + r0, self.dpre_ptr[l] + r0, rows * C)
-                    ops.gemm(self.dpre_ptr[l] + r0, self.post_ptr[l - 1] + r0p, dwp, M=C, N=k * C, K=rows, lda=C, ldb=s * C, ldc=k * C,
-                             a_trans=1, b_trans=1, epilogue=ops.EPI_ATOMIC_F32, split_k=ops.pick_split_k(C, k * C, rows), **self._det_kw())
-                if not side_wgrad:
-                    ops.conv_weight_layout(dwp, f.gptr(f"{self.stacks[si]}{l}.0.weight"), C_out=C, C_in=C, k=k, mode=2)
-                for rho in range(s):
-                    U = len(range(rho, k, s))
-                    if U == 0:
-                        continue
-                    if sparse:
-                        if n_ext > 0 and fuse_gelu and l - 1 >= 1:
-                            # the rows this GEMM writes (s g + rho, g in ext) are exactly act[l - 1]: d(pre[l - 1]) = bf16(d(post)) * gelu'(pre)
-                            # straight from its epilogue -- the bits a bf16 d(post) tensor + wj_gelu_bwd_bf16 over act[l - 1] would give
-                            ops.gemm(self.dpre_ptr[l] - (U - 1) * C * 2, self._conv_w[f"{si}:wd{l}_{rho}"], self.dpre_ptr[l - 1] + rho * C * 2,
-                                     M=n_ext, N=C, K=U * C, lda=C, ldb=C, ldc=s * C, b_trans=1, rowmap=ext,
-                                     epilogue=ops.EPI_MUL_GELU_GRAD_Z, aux=self.pre_ptr[l - 1] + rho * C * 2)
-                        elif n_ext > 0:
-                            ops.gemm(self.dpre_ptr[l] - (U - 1) * C * 2, self._conv_w[f"{si}:wd{l}_{rho}"], self.dpost_ptr[l - 1] + rho * C * 2,
-                                     M=n_ext, N=C, K=U * C, lda=C, ldb=C, ldc=s * C, b_trans=1, rowmap=ext)
-                    else:
-                        ops.gemm(self.dpre_ptr[l] + r0 - (U - 1) * C * 2, self._conv_w[f"{si}:wd{l}_{rho}"],
-                                 self.dpost_ptr[l - 1] + r0p + rho * C * 2, M=rows, N=C, K=U * C, lda=C, ldb=C, ldc=s * C, b_trans=1)
-                if sparse and side_wgrad:
-                    late_clear.append((self.dpre_ptr[l], act, n_act))
-                elif sparse:
-                    ops.zero_rows(self.dpre_ptr[l], act, n_rows=n_act, row_bytes=C * 2)
-        _, k0, s0 = c.conv_spec[0]
-        audio_p = self.audio.data_ptr()
-        for ch in range(S):                  # layer 0: one call per stream (N mono clips each; ConvFeatureExtractor: one stream)
-            pre = self.stacks[min(ch, len(self.stacks) - 1)]
-            c0 = ch * N
-            lists = {}
-            if sparse:
-                rows0, n0, off0, max0 = act_rows[0][ch]
-                lists = dict(rows=rows0, row_off=off0, max_rows=max0)
-            if ln:
-                r0 = c0 * self.P[0]
-                bias = c.conv_bias
-                ops.conv0_ln_bwd(audio_p + ch * c.n_samples * 2 if S > 1 else self.audio, f.ptr16(f"{pre}0.0.weight"),
-                                 f.ptr32(f"{pre}0.0.bias") if bias else None, f.ptr32(f"{pre}0.2.1.weight"), f.ptr32(f"{pre}0.2.1.bias"),
-                                 self.cl_mean[0][r0:], self.cl_rstd[0][r0:], self.dpost_ptr[0] + r0 * C * 2, f.gptr(f"{pre}0.0.weight"),
-                                 f.gptr(f"{pre}0.0.bias") if bias else None, f.gptr(f"{pre}0.2.1.weight"), f.gptr(f"{pre}0.2.1.bias"),
-                                 self.cl_ws_b, N=N, C_in=c.in_channels, L=c.n_samples, C=C, k=k0, stride=s0, L_out=self.L[0], P=self.P[0],
-                                 audio_clip_stride=S * c.in_channels * c.n_samples if S > 1 else 0, **lists)
-                if sparse:
-                    ops.zero_rows(self.dpost_ptr[0] + r0 * C * 2, rows0, n_rows=n0, row_bytes=C * 2)
-                continue
-            ops.conv0_bwd(audio_p + ch * c.n_samples * 2 if S > 1 else self.audio, f.ptr16(f"{pre}0.0.weight"), f.ptr32(f"{pre}0.2.weight"),
-                          f.ptr32(f"{pre}0.2.bias"), self.gn_stats[0, c0:], self.gn_stats[1, c0:], self.dpost_ptr[0] + c0 * self.P[0] * C * 2,
-                          f.gptr(f"{pre}0.0.weight"), f.gptr(f"{pre}0.2.weight"), f.gptr(f"{pre}0.2.bias"), self.gn_ws_b,
-                          yx=self.gn_yx[c0:], x1=self.gn_x1[c0:], N=N, C_in=c.in_channels, L=c.n_samples, C=C, k=k0, stride=s0,
-                          L_out=self.L[0], P=self.P[0], audio_clip_stride=S * c.in_channels * c.n_samples if S > 1 else 0, **lists)
-            if sparse:
-                ops.zero_rows(self.dpost_ptr[0] + c0 * self.P[0] * C * 2, rows0, n_rows=n0, row_bytes=C * 2)
-        if late_clear:
-            self._join_side()                # the side stream's conv weight gradients have read d(pre[l]): clear the rows now
-            for ptr, act, n_act in late_clear:
-                ops.zero_rows(ptr, act, n_rows=n_act, row_bytes=C * 2)
-
-    def _conv_ln_bwd(self, l: int, si: int, row0: int, M: int, rows=None, n_rows: int = 0, clear_dpost: bool = False) -> None:
-        """wj_conv_ln_gelu_bwd of conv layer l >= 1 over the M rows from row `row0` of the layer's buffers (listed form: `rows` index
-        those M rows); its dgamma | dbeta | dbias partial rows take the fold forms of _ln_bwd."""
-        f, C, pre = self.flat, self.C, self.stacks[si]
-        off = row0 * C * 2
-        dg, db = f.gptr(f"{pre}{l}.2.1.weight"), f.gptr(f"{pre}{l}.2.1.bias")
-        dbias = f.gptr(f"{pre}{l}.0.bias") if self.cfg.conv_bias else None
-        args = (self.dpost_ptr[l] + off, self.pre_ptr[l] + off, self.cl_mean[l][row0:], self.cl_rstd[l][row0:], f.ptr32(f"{pre}{l}.2.1.weight"),
-                f.ptr32(f"{pre}{l}.2.1.bias"), self.dpre_ptr[l] + off)
-        kw = dict(M=M, C=C, seg_rows=self.P[l], seg_valid=self.L[l], rows=rows, n_rows=n_rows, clear_dpost=clear_dpost)
-        form, ws = self._fold_form(3 * C, True)
-        if form == "slot":
-            ops.conv_ln_gelu_bwd(*args, ws, **kw)
-            self._fold(form, ws, 3 * C, ops.conv_ln_bwd_partial_rows(n_rows if rows is not None else M, C), dg, db, dbias, C)
-        else:                                # the entry folds its partial rows itself (in order when deterministic)
-            ops.conv_ln_gelu_bwd(*args, self.red_ws, dgamma=dg, dbeta=db, dbias=dbias, deterministic=self.deterministic, **kw)
-
-    def _conv_rows(self, plan: MaskPlan):
-        """Device copies of conv_active_rows for this plan (cached on the plan: mask sets are reused by the data source).
-        {l >= 1: [per stack group (act, n_act, ext, n_ext)]} with rows of the WHOLE layer buffer (a group's rows are a contiguous
-        slice of the ascending list: conv clips are channel-major), {0: [per stream (rows, n, row_off, max_rows)]} with rows
-        relative to the stream's first clip (one conv0 call per stream)."""
-        cached = getattr(plan, "_conv_rows", None)
-        if cached is not None and cached[0] == (self.N, self.S, len(self.stacks), tuple(self.P)):
-            return cached[1]
-        N, S = self.N, self.S
-        keep = (plan.ctx_u8.cpu().numpy() == 0) if plan.ctx_np is None else ~plan.ctx_np
-        if S > 1:                            # tokens (n, c, t) -> conv clip c*N + n
-            keep = np.ascontiguousarray(keep.reshape(N, S, self.Tc).transpose(1, 0, 2)).reshape(S * N, self.Tc)
-        lists = conv_active_rows(keep, self.P, self.cfg.conv_spec)
-        pad = np.zeros(256, np.int32)        # the k-gather GEMM prefetches indices up to 256 entries past the end
-        # every list of the step in ONE host -> device copy
-        act0, off0 = lists[0]
-        host, keys = [], []
-        for l, (act, ext) in lists.items():
-            if l == 0:
-                continue
-            host += [np.concatenate([act, pad]).astype(np.int32), np.concatenate([ext, pad]).astype(np.int32)]
-            keys += [("act", l), ("ext", l)]
-        per0_host = []
-        for ch in range(S):
-            lo, hi = int(off0[ch * N]), int(off0[(ch + 1) * N])
-            rows = (act0[lo:hi] - ch * N * self.P[0]).astype(np.int32)
-            off = (off0[ch * N:(ch + 1) * N + 1] - lo).astype(np.int32)
-            per0_host.append((rows, off))
-            host += [np.concatenate([rows, pad]).astype(np.int32), np.concatenate([off, pad]).astype(np.int32)]
-            keys += [("rows0", ch), ("off0", ch)]
-        dev = dict(zip(keys, pack_upload(host, self.dev)))
-
-        groups = self._stack_groups()
-        out = {}
-        for l, (act, ext) in lists.items():
-            if l == 0:
-                continue
-            d_act, d_ext = dev[("act", l)], dev[("ext", l)]
-            per = []
-            for _, c0, nclips in groups:
-                lo, hi = c0 * self.P[l], (c0 + nclips) * self.P[l]
-                a0, a1 = np.searchsorted(act, [lo, hi])
-                e0, e1 = np.searchsorted(ext, [lo, hi])
-                per.append((d_act.data_ptr() + 4 * int(a0), int(a1 - a0), d_ext.data_ptr() + 4 * int(e0), int(e1 - e0)))
-            out[l] = per
-            out[("keep", l)] = (d_act, d_ext)        # owners of the pointers above
-        per0 = []
-        for ch, (rows, off) in enumerate(per0_host):
-            per0.append((dev[("rows0", ch)], int(rows.size), dev[("off0", ch)], int(np.diff(off).max()) if off.size > 1 else 0))
-        out[0] = per0
-        plan._conv_rows = ((self.N, self.S, len(self.stacks), tuple(self.P)), out)
-        return out
+        # conv backward over the active rows only on a ragged step (sparse_conv), over every row otherwise
+        self.front.backward(self, self.audio, plan if rag and self.sparse_conv else None)
 
     # ------------------------------------------------------------------------------------------------ EMA / inference
     def ema_step(self, r: float) -> None:
