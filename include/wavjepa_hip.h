@@ -182,7 +182,8 @@ int wj_wgrad_grouped(const wj_wgrad_group_args*, void* stream);
  *   group_stats (optional, f32 [ceil(M / group_rows)][WJ_GROUP_STATS_SPLIT][2], overwritten): partial (sum y, sum y^2) of the
  *   f32 output over every group of group_rows consecutive rows, one pair per quarter of the group; the consumer
  *   (wj_instnorm_mean; teacher targets, jepa.py:244-252) adds the quarters in order.  Plain stores, no float atomics:
- *   forward activations are bit-reproducible from run to run.
+ *   forward activations are bit-reproducible from run to run.  A lane sums a row's elements on their own and adds the row to its
+ *   running pair: each sum stays within 8 u (sum of magnitudes) of the exact one on constant groups too (tests/norm_reference.py).
  * -----------------------------------------------------------------------------------------------------------*/
 #define WJ_GROUP_STATS_SPLIT 4
 typedef struct {

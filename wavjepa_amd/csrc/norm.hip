@@ -97,6 +97,14 @@ __device__ __forceinline__ RowRange fwd_rows(const Lanes<V, LPR>& L, int M, bool
     const int rpp = (group_rows + GS_SPLIT - 1) / GS_SPLIT;
     return {grp * group_rows + part * rpp + L.wave * RPW + L.sr, min(M, grp * group_rows + min(group_rows, (part + 1) * rpp)), 4u * RPW};
 }
+// A lane's running group sums take a row's share (its <= 16 elements, summed on their own) in ONE addition each.  Added element by
+// element instead, a lane's sums are one chain over all its rows -- 600 elements at 200 x 768 -- and on a sample whose elements are all
+// equal every addition of that chain rounds the same way: the sums came out 19 u (sum |s|) off, 2.4 x the 8 u that
+// tests/norm_reference.py allows a sum (4.6 x at D = 1024); by rows they stay within 0.4 x.
+__device__ __forceinline__ void add_row_to_group(float& gs1, float& gs2, float r1, float r2) {
+    gs1 += r1;
+    gs2 += r2;
+}
 // kernel-uniform call: fold lanes, then waves, then one pair of stores per workgroup into [group][GS_SPLIT][2]
 __device__ __forceinline__ void store_group_stats(float* group_stats, float gs1, float gs2) {
     __shared__ float gred[4][2];
@@ -161,12 +169,13 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(wj_ln_fwd_args a) {
         }
         float mean, rstd;
         row_stats(L, s, sum, a.eps, a.mean, a.rstd, m, mean, rstd);
+        float r1 = 0.f, r2 = 0.f;      // the row's share of the group sums (add_row_to_group)
         LN_FOR_CHUNKS(L, j, col) {
             const f32x4 y = normalise4(s[j], mean, rstd, gam[j], bet[j]);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                gs1 += y[e];
-                gs2 = fmaf(y[e], y[e], gs2);
+                r1 += y[e];
+                r2 = fmaf(y[e], y[e], r2);
             }
             const bf16x4 o = round4(y);
             store4(a.y_f32, m, a.y_bf16, m, D, col, y, o);
@@ -200,6 +209,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(wj_ln_fwd_args a) {
                     ((uint32_t*)a.y_fp8_scales)[(long)(col / 128) * a.ld_fp8_scale + m] = s0 | (s1 << 8) | (s2 << 16) | (s3 << 24);
             }
         }
+        add_row_to_group(gs1, gs2, r1, r2);
     }
     if (a.group_stats) store_group_stats(a.group_stats, gs1, gs2);
 }
@@ -254,7 +264,7 @@ __global__ __launch_bounds__(256) void ln_pre_fwd_kernel(wj_ln_pre_fwd_args a) {
     // launches get slower (tools/ln_bench.py, 10045 x 768: 25.4 us against 24.2; all five shapes in profiles/norm_shared_pieces.txt)
     for (int m = rows.begin; m < rows.end; m += (int)rows.step) {
         f32x4 s[V];
-        float sum = 0.f;
+        float sum = 0.f, r2 = 0.f;
         L.zero(s);
         LN_FOR_CHUNKS(L, j, col) {
             s[j] = load4_sum(a.x, m, false, a.r, m, D, col);
@@ -262,10 +272,10 @@ __global__ __launch_bounds__(256) void ln_pre_fwd_kernel(wj_ln_pre_fwd_args a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 sum += s[j][e];
-                gs1 += s[j][e];
-                gs2 = fmaf(s[j][e], s[j][e], gs2);
+                r2 = fmaf(s[j][e], s[j][e], r2);
             }
         }
+        add_row_to_group(gs1, gs2, sum, r2);
         if (!norm) continue;
         float mean, rstd;
         row_stats(L, s, sum, a.eps, a.mean, a.rstd, m, mean, rstd);
