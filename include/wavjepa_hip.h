@@ -708,12 +708,43 @@ typedef struct {
 } wj_mse_args;
 int wj_masked_mse(const wj_mse_args*, void* stream);
 
+/* Masked loss family: wj_masked_mse's launch sequence (count, rows, one-workgroup final: no atomics, two launches give the same bits)
+ * with the per-element loss chosen by `kind`.  d = fl32(bf16 pred - f32 target):
+ *   WJ_LOSS_MSE        e = d^2                                              e' = 2 d     (bit-equal to wj_masked_mse)
+ *   WJ_LOSS_L1         e = |d|                                              e' = sign(d), sign(0) = 0
+ *   WJ_LOSS_SMOOTH_L1  e = |d| < beta ? 0.5 d (d ib) : |d| - 0.5 beta       e' = |d| < beta ? d ib : sign(d),   ib = fl32(1 / beta)
+ *   WJ_LOSS_HUBER      e = |d| <= beta ? 0.5 d^2 : beta (|d| - 0.5 beta)    e' = |d| <= beta ? d : beta sign(d) (beta is delta)
+ *   loss[0] = sum_{tgt} mean_d e / (count + 1e-8);  loss[1] = count;
+ *   dpreds (optional, bf16) = tgt ? e' * gscale * gscale_ptr[0] / (D (count + 1e-8)) : 0.
+ * The fields up to gscale are wj_mse_args' own, in its order and meaning (dense and ragged forms, workspace f32 [2 + B*G*T]).
+ * beta: ignored by MSE and L1; <= 0 or not finite with SMOOTH_L1 / HUBER is WJ_ERR_ARG; a kind outside 0..3 is WJ_ERR_UNSUPPORTED. */
+#define WJ_LOSS_MSE 0
+#define WJ_LOSS_L1 1
+#define WJ_LOSS_SMOOTH_L1 2
+#define WJ_LOSS_HUBER 3
+typedef struct {
+    const void* preds;
+    const float* targets;
+    const uint8_t* tgt;
+    const int32_t* rows;
+    float* loss;
+    void* dpreds;
+    float* workspace;
+    const float* gscale_ptr;
+    int32_t B, G, T, D;
+    int32_t n_rows;
+    float gscale;
+    int32_t kind;            /* WJ_LOSS_* */
+    float beta;              /* smooth-L1's beta / Huber's delta */
+} wj_loss_args;
+int wj_masked_loss(const wj_loss_args*, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Workspace sizes.  The library never allocates: entry points that need scratch take a `workspace` pointer, and this
  * query tells the caller how many BYTES the call described by the SAME argument struct needs (pointers in it are
  * ignored).  `fn` is the entry point's name: "wj_gemm_bf16" / "wj_wgrad_grouped" / "wj_colsum_bf16" (the K-split pair scratch, or with
  * `deterministic` the slabs / partial rows of the store-and-sum forms), "wj_layernorm_bwd", "wj_attn_bwd" (its dbias_ws), "wj_conv0_gn_gelu_fwd",
- * "wj_conv0_gn_gelu_bwd", "wj_conv_ln_gelu_bwd" (its partial rows), "wj_conv0_ln_gelu_bwd", "wj_masked_mse", "wj_grad_sumsq", "wj_audio_prepare", "wj_noise_prepare".  Returns 0 for entry points without scratch, -1 for an unknown
+ * "wj_conv0_gn_gelu_bwd", "wj_conv_ln_gelu_bwd" (its partial rows), "wj_conv0_ln_gelu_bwd", "wj_masked_mse", "wj_masked_loss", "wj_grad_sumsq", "wj_audio_prepare", "wj_noise_prepare".  Returns 0 for entry points without scratch, -1 for an unknown
  * name or NULL arguments.
  * -----------------------------------------------------------------------------------------------------------*/
 int64_t wj_workspace_bytes(const char* fn, const void* args);

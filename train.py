@@ -70,6 +70,13 @@ class ComponentFactory:
         # trainer.norm_first: pre-norm layers in every stack; trainer.norm_first_decoder: the predictor's own setting (default: the same)
         norm_first = bool(cfg.trainer.get("norm_first", False))
         norm_first_dec = bool(cfg.trainer.get("norm_first_decoder", norm_first))
+        # trainer.loss: the per-element objective on target rows; trainer.loss_beta: smooth-L1's beta / Huber's delta
+        loss, beta = str(cfg.trainer.get("loss", "mse")), float(cfg.trainer.get("loss_beta", 1.0))
+        losses = {"mse": lambda: None, "l1": lambda: torch.nn.L1Loss(reduction="none"),
+                  "smooth_l1": lambda: torch.nn.SmoothL1Loss(reduction="none", beta=beta),
+                  "huber": lambda: torch.nn.HuberLoss(reduction="none", delta=beta)}
+        if loss not in losses:
+            raise ValueError(f"Unknown trainer.loss: {loss}. Available losses: {list(losses)}")
         try:
             return cls(feature_extractor=extractor, transformer_encoder_cfg=TransformerEncoderCFG.create(),
                        transformer_encoder_layers_cfg=TransformerLayerCFG.create(norm_first=norm_first),
@@ -79,7 +86,7 @@ class ComponentFactory:
                        resample_sr=cfg.data.sr, process_audio_seconds=cfg.data.process_seconds,
                        nr_samples_per_audio=cfg.data.samples_per_audio, compile_modules=cfg.trainer.compile_modules,
                        average_top_k_layers=cfg.trainer.average_top_k_layers, size=cfg.trainer.get("size", "base"),
-                       warmup_steps=cfg.trainer.get("warmup_steps", 100000))
+                       warmup_steps=cfg.trainer.get("warmup_steps", 100000), loss_fn=losses[loss]())
         except Exception as e:
             raise RuntimeError(f"Failed to create network instance: {str(e)}")
 

@@ -384,12 +384,41 @@ __global__ __launch_bounds__(1024) void mse_count_kernel(const uint8_t* __restri
     if (threadIdx.x == 0) ws[1] = c;
 }
 
-__global__ __launch_bounds__(256) void mse_rows_kernel(wj_mse_args a) {
+// One rows kernel for the whole loss family (include/wavjepa_hip.h: wj_loss_args), instantiated per kind.  d = fl32(bf16 pred - f32
+// target); e(d) goes into the row sum, e'(d) * gk into dpreds.  gk carries MSE's factor 2 (its e' = 2 d), 1 for the other kinds;
+// smooth-L1 multiplies by ib = fl32(1 / beta), formed once per thread.  sign(d) is exact: fl32(p - y) has the sign of p - y.
+template <int KIND>
+__device__ __forceinline__ void loss_elem(float d, float beta, float ib, float& e, float& g) {
+    if constexpr (KIND == WJ_LOSS_MSE) {
+        e = d * d;
+        g = d;
+    } else {
+        const float ad = fabsf(d);
+        const float sg = d > 0.f ? 1.0f : (d < 0.f ? -1.0f : 0.f);
+        if constexpr (KIND == WJ_LOSS_L1) {
+            e = ad;
+            g = sg;
+        } else if constexpr (KIND == WJ_LOSS_SMOOTH_L1) {
+            const float q = d * ib;
+            const bool quad = ad < beta;
+            e = quad ? (0.5f * d) * q : ad - 0.5f * beta;
+            g = quad ? q : sg;
+        } else {                                   // WJ_LOSS_HUBER, beta is delta
+            const bool quad = ad <= beta;
+            e = quad ? (0.5f * d) * d : beta * (ad - 0.5f * beta);
+            g = quad ? d : beta * sg;
+        }
+    }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void loss_rows_kernel(wj_loss_args a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int D = a.D;
     const long R = a.rows ? (long)a.n_rows : (long)a.B * a.G * a.T;
     const float count = a.workspace[1];
-    const float gk = 2.0f / ((float)D * (count + 1e-8f)) * a.gscale * (a.gscale_ptr ? a.gscale_ptr[0] : 1.0f);
+    const float gk = (KIND == WJ_LOSS_MSE ? 2.0f : 1.0f) / ((float)D * (count + 1e-8f)) * a.gscale * (a.gscale_ptr ? a.gscale_ptr[0] : 1.0f);
+    const float beta = a.beta, ib = KIND == WJ_LOSS_SMOOTH_L1 ? 1.0f / a.beta : 0.f;
     for (long r = blockIdx.x * 4L + wave; r < R; r += gridDim.x * 4L) {
         const long dense = a.rows ? (long)a.rows[r] : r;     // (b*G+g)*T + t; preds / dpreds are indexed by r
         const int t = (int)(dense % a.T);
@@ -407,8 +436,10 @@ __global__ __launch_bounds__(256) void mse_rows_kernel(wj_mse_args a) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float d = bf2f(p[e]) - y[e];
-                    err += d * d;
-                    dp[e] = f2bf(d * gk);
+                    float le, lg;
+                    loss_elem<KIND>(d, beta, ib, le, lg);
+                    err += le;
+                    dp[e] = f2bf(lg * gk);
                 }
             }
             if (a.dpreds) *reinterpret_cast<bf16x4*>((bf16_t*)a.dpreds + r * D + c) = dp;
@@ -598,7 +629,7 @@ extern "C" int wj_struct_size(const char* name) {
     WJ_SZ(wj_gemm_args) WJ_SZ(wj_ln_fwd_args) WJ_SZ(wj_ln_bwd_args) WJ_SZ(wj_ln_pre_fwd_args) WJ_SZ(wj_ln_pre_bwd_args) WJ_SZ(wj_colsum_args) WJ_SZ(wj_attn_fwd_args)
     WJ_SZ(wj_attn_bwd_args) WJ_SZ(wj_conv0_fwd_args) WJ_SZ(wj_conv0_bwd_args) WJ_SZ(wj_gelu_bwd_args) WJ_SZ(wj_conv_w_args)
     WJ_SZ(wj_add_pos_args) WJ_SZ(wj_gather_args) WJ_SZ(wj_scatter_fill_args) WJ_SZ(wj_scatter_fill_bwd_args)
-    WJ_SZ(wj_unmask_rows_args) WJ_SZ(wj_instnorm_args) WJ_SZ(wj_mse_args) WJ_SZ(wj_ema_args) WJ_SZ(wj_sumsq_args)
+    WJ_SZ(wj_unmask_rows_args) WJ_SZ(wj_instnorm_args) WJ_SZ(wj_mse_args) WJ_SZ(wj_loss_args) WJ_SZ(wj_ema_args) WJ_SZ(wj_sumsq_args)
     WJ_SZ(wj_adamw_args) WJ_SZ(wj_cast_args) WJ_SZ(wj_crop_args) WJ_SZ(wj_zero_rows_args) WJ_SZ(wj_instnorm_mean_args) WJ_SZ(wj_spin_args)
     WJ_SZ(wj_gemm_fp8_args) WJ_SZ(wj_quantize_fp8_args) WJ_SZ(wj_wgrad_group_args) WJ_SZ(wj_rir_conv_args) WJ_SZ(wj_snr_mix_args) WJ_SZ(wj_resample_args) WJ_SZ(wj_mse_groups_args) WJ_SZ(wj_transpose_args) WJ_SZ(wj_colsum_group_args) WJ_SZ(wj_rccl_init_args) WJ_SZ(wj_rccl_launch_args) WJ_SZ(wj_rccl_wait_args) WJ_SZ(wj_audio_prepare_args) WJ_SZ(wj_noise_prepare_args)
     WJ_SZ(wj_conv_ln_fwd_args) WJ_SZ(wj_conv_ln_bwd_args) WJ_SZ(wj_conv0_ln_fwd_args) WJ_SZ(wj_conv0_ln_bwd_args)
@@ -640,6 +671,10 @@ extern "C" int64_t wj_workspace_bytes(const char* fn, const void* args) {
     if (!strcmp(fn, "wj_conv0_gn_gelu_bwd")) return wj_conv0_bwd_ws_bytes((const wj_conv0_bwd_args*)args);
     if (!strcmp(fn, "wj_masked_mse")) {
         const wj_mse_args* a = (const wj_mse_args*)args;
+        return (2 + (int64_t)a->B * a->G * a->T) * 4;
+    }
+    if (!strcmp(fn, "wj_masked_loss")) {
+        const wj_loss_args* a = (const wj_loss_args*)args;
         return (2 + (int64_t)a->B * a->G * a->T) * 4;
     }
     if (!strcmp(fn, "wj_grad_sumsq")) return 1024 * 4;
@@ -841,18 +876,42 @@ extern "C" int wj_instnorm_mean(const wj_instnorm_mean_args* a, void* stream) {
     return WJ_OK;
 }
 
-extern "C" int wj_masked_mse(const wj_mse_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
-    if (!a || !a->preds || !a->targets || !a->tgt || !a->loss || !a->workspace) return WJ_ERR_ARG;
+// count -> rows<kind> -> final: one launch sequence for wj_masked_mse (kind MSE) and wj_masked_loss; validation precedes every launch
+static int masked_loss_launch(const wj_loss_args* a, void* stream) {
+    if (!a->preds || !a->targets || !a->tgt || !a->loss || !a->workspace) return WJ_ERR_ARG;
     if (a->B <= 0 || a->G <= 0 || a->T <= 0 || a->D <= 0 || (a->D & 3)) return WJ_ERR_ARG;
     const long Rd = (long)a->B * a->G * a->T;          // dense positions (the target count runs over all of them)
     if (a->rows && a->n_rows < 0) return WJ_ERR_ARG;
+    if (a->kind < WJ_LOSS_MSE || a->kind > WJ_LOSS_HUBER) return WJ_ERR_UNSUPPORTED;
+    if ((a->kind == WJ_LOSS_SMOOTH_L1 || a->kind == WJ_LOSS_HUBER) && !(a->beta > 0.f && a->beta <= 3.402823466e38f)) return WJ_ERR_ARG;   // NaN, inf, <= 0
     const long R = a->rows ? (long)a->n_rows : Rd;    // rows actually held by preds / dpreds
     hipLaunchKernelGGL(mse_count_kernel, dim3(1), dim3(1024), 0, STREAM, a->tgt, a->workspace, Rd);
-    if (R > 0) hipLaunchKernelGGL(mse_rows_kernel, dim3(grid_for(R, 4)), dim3(256), 0, STREAM, *a);
+    if (R > 0) {
+        const dim3 grid(grid_for(R, 4));
+        switch (a->kind) {
+            case WJ_LOSS_MSE: hipLaunchKernelGGL(loss_rows_kernel<WJ_LOSS_MSE>, grid, dim3(256), 0, STREAM, *a); break;
+            case WJ_LOSS_L1: hipLaunchKernelGGL(loss_rows_kernel<WJ_LOSS_L1>, grid, dim3(256), 0, STREAM, *a); break;
+            case WJ_LOSS_SMOOTH_L1: hipLaunchKernelGGL(loss_rows_kernel<WJ_LOSS_SMOOTH_L1>, grid, dim3(256), 0, STREAM, *a); break;
+            default: hipLaunchKernelGGL(loss_rows_kernel<WJ_LOSS_HUBER>, grid, dim3(256), 0, STREAM, *a); break;
+        }
+    }
     hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(1024), 0, STREAM, a->workspace, a->loss, R);
     WJ_CHECK_LAUNCH();
     return WJ_OK;
+}
+
+extern "C" int wj_masked_mse(const wj_mse_args* a, void* stream) {
+    WJ_CLEAR_STALE_ERROR();
+    if (!a) return WJ_ERR_ARG;
+    const wj_loss_args l = {a->preds, a->targets, a->tgt, a->rows, a->loss, a->dpreds, a->workspace, a->gscale_ptr,
+                            a->B, a->G, a->T, a->D, a->n_rows, a->gscale, WJ_LOSS_MSE, 0.f};
+    return masked_loss_launch(&l, stream);
+}
+
+extern "C" int wj_masked_loss(const wj_loss_args* a, void* stream) {
+    WJ_CLEAR_STALE_ERROR();
+    if (!a) return WJ_ERR_ARG;
+    return masked_loss_launch(a, stream);
 }
 
 extern "C" int wj_ema_update(const wj_ema_args* a, void* stream) {

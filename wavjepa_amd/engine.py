@@ -42,6 +42,8 @@ class EngineConfig:
     norm_first_dec: bool = False   # ... in the predictor
     conv_mode: str = "default"     # "default": GroupNorm on conv layer 0 only; "layer_norm": LayerNorm over channels behind EVERY conv layer
     conv_bias: bool = False        # conv layers carry a bias (mode "layer_norm" only)
+    loss_kind: str = "mse"         # per-element loss of the masked objective: "mse" | "l1" | "smooth_l1" | "huber" (ops.masked_loss)
+    loss_beta: float = 1.0         # smooth-L1's beta / Huber's delta
 
 
 @dataclass
@@ -261,6 +263,8 @@ class JepaEngine:
             raise ValueError(f"conv_mode must be 'default' or 'layer_norm', not {cfg.conv_mode!r}")
         # mode="layer_norm": Conv1d(+bias) -> LayerNorm over channels -> GELU in every conv layer (csrc/conv_ln.hip)
         self.conv_ln = cfg.conv_mode == "layer_norm"
+        if cfg.loss_kind not in ops.LOSS_KINDS:
+            raise ValueError(f"loss_kind {cfg.loss_kind!r}: one of {sorted(ops.LOSS_KINDS)}")
         if cfg.conv_bias and not self.conv_ln:
             raise NotImplementedError("conv_bias=True needs mode='layer_norm': the GroupNorm front-end's kernels carry no conv bias")
         if self.conv_ln and self.C not in (64, 128, 256, 512):
@@ -1268,8 +1272,12 @@ class JepaEngine:
             rows = dict(rows=plan.tgt_dense, n_rows=plan.n_tgt)          # preds hold the target rows only
         else:
             rows = dict(rows=plan.dec_rows, n_rows=plan.n_dec) if self.ragged_step else {}
-        ops.masked_mse(self.preds, self.targets, plan.tgt_u8, self.loss, self.mse_ws, B=self.N, G=self.G, T=self.T, D=c.d_enc,
-                       dpreds=dpreds, gscale_ptr=gscale_ptr, **rows)
+        if c.loss_kind == "mse":
+            ops.masked_mse(self.preds, self.targets, plan.tgt_u8, self.loss, self.mse_ws, B=self.N, G=self.G, T=self.T, D=c.d_enc,
+                           dpreds=dpreds, gscale_ptr=gscale_ptr, **rows)
+        else:
+            ops.masked_loss(self.preds, self.targets, plan.tgt_u8, self.loss, self.mse_ws, B=self.N, G=self.G, T=self.T, D=c.d_enc,
+                            kind=c.loss_kind, beta=c.loss_beta, dpreds=dpreds, gscale_ptr=gscale_ptr, **rows)
 
     def dense_preds(self) -> torch.Tensor:
         """Predictions as the reference shapes them, bf16 [N*G, T, d_enc].  On a ragged step only the visible rows were

@@ -11,7 +11,7 @@ from __future__ import annotations
 import copy
 import math
 import os
-from typing import Any, Dict, Optional
+from typing import Any, Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -256,6 +256,30 @@ HAS_LIGHTNING = _pl is not None
 _ModuleBase = _pl.LightningModule if HAS_LIGHTNING else nn.Module
 
 
+def loss_kind_of(loss_fn: Optional[nn.Module]) -> Tuple[str, float]:
+    """(kind, beta) of the masked objective the reference would compute with `loss_fn` (jepa.py:351: loss_fn(pred, target) per element,
+    so reduction must be 'none').  None / MSELoss -> mse; L1Loss -> l1; SmoothL1Loss(beta) -> smooth_l1 (beta = 0 is L1, as torch defines
+    it); HuberLoss(delta) -> huber.  Anything else is refused here instead of being trained as MSE."""
+    if loss_fn is None:
+        return "mse", 1.0
+    table = ((nn.MSELoss, "mse", None), (nn.SmoothL1Loss, "smooth_l1", "beta"), (nn.HuberLoss, "huber", "delta"), (nn.L1Loss, "l1", None))
+    for cls, kind, attr in table:
+        if type(loss_fn) is cls:
+            break
+    else:
+        raise NotImplementedError(f"loss_fn {type(loss_fn).__name__}: the loss kernel computes nn.MSELoss, nn.L1Loss, nn.SmoothL1Loss "
+                                  "and nn.HuberLoss")
+    if getattr(loss_fn, "reduction", "none") != "none":
+        raise ValueError(f"loss_fn must be built with reduction='none' (got {loss_fn.reduction!r}): the masked mean over target rows "
+                         "is taken by the loss kernel")
+    beta = 1.0 if attr is None else float(getattr(loss_fn, attr))
+    if kind == "smooth_l1" and beta == 0.0:
+        return "l1", 1.0
+    if attr is not None and not (beta > 0.0 and beta < float("inf")):
+        raise ValueError(f"loss_fn {type(loss_fn).__name__}: {attr} must be positive and finite (got {beta})")
+    return kind, beta
+
+
 class JEPA(_ModuleBase):
     """Joint-Embedding Predictive Architecture for waveforms (student encoder + predictor vs EMA teacher)."""
 
@@ -290,6 +314,12 @@ class JEPA(_ModuleBase):
         self.extract_audio = feature_extractor
         self.feature_norms = nn.LayerNorm(self.extract_audio.embedding_dim)
         self.loss_fn = loss_fn
+        # the module is not called: its kind runs inside the loss kernel (ops.masked_loss).  Recorded only when it is not MSE, so that
+        # checkpoints of MSE models keep the hyper-parameter set they always had
+        self.loss_kind, self.loss_beta = loss_kind_of(loss_fn)
+        if self.loss_kind != "mse":
+            self.hparams["loss"] = self.loss_kind
+            self.hparams["loss_beta"] = self.loss_beta
 
         enc_l, enc_c = dict(transformer_encoder_layers_cfg), dict(transformer_encoder_cfg)
         dec_l, dec_c = dict(transformer_decoder_layers_cfg), dict(transformer_decoder_cfg)
@@ -428,7 +458,8 @@ class JEPA(_ModuleBase):
                            d_dec=self.decoder_embedding_dim, h_dec=self.n_decoder_heads, l_dec=self.decoder.num_layers,
                            top_k=int(self.hparams.average_top_k_layers), ln_eps=self.encoder.layer_norm_eps,
                            norm_first_enc=self.encoder.norm_first, norm_first_dec=self.decoder.norm_first,
-                           conv_mode=getattr(ext, "mode", "default"), conv_bias=bool(getattr(ext, "conv_bias", False)))
+                           conv_mode=getattr(ext, "mode", "default"), conv_bias=bool(getattr(ext, "conv_bias", False)),
+                           loss_kind=self.loss_kind, loss_beta=self.loss_beta)
         self._engine = JepaEngine(cfg, self._flat, self.pos_encoding_encoder.data, self.pos_encoding_decoder.data)
         self._anchor = torch.zeros(1, device=self.device, requires_grad=True)
         self._student_bf16_fresh = False

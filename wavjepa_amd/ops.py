@@ -111,7 +111,7 @@ def require_gpu() -> None:
 def workspace_bytes(fn: str, **dims) -> int:
     """Scratch bytes entry point `fn` needs for the given dimensions (fields of its argument struct), from the library."""
     struct_name = {"wj_gemm_bf16": "wj_gemm_args", "wj_colsum_bf16": "wj_colsum_args", "wj_mask_scatter_fill_pos_bwd": "wj_scatter_fill_bwd_args", "wj_layernorm_bwd": "wj_ln_bwd_args", "wj_layernorm_pre_bwd": "wj_ln_pre_bwd_args", "wj_attn_bwd": "wj_attn_bwd_args", "wj_attn_stream_bwd": "wj_attn_bwd_args", "wj_conv0_gn_gelu_fwd": "wj_conv0_fwd_args",
-                   "wj_conv0_gn_gelu_bwd": "wj_conv0_bwd_args", "wj_masked_mse": "wj_mse_args", "wj_grad_sumsq": "wj_sumsq_args",
+                   "wj_conv0_gn_gelu_bwd": "wj_conv0_bwd_args", "wj_masked_mse": "wj_mse_args", "wj_masked_loss": "wj_loss_args", "wj_grad_sumsq": "wj_sumsq_args",
                    "wj_rir_convolve": "wj_rir_conv_args", "wj_snr_mix": "wj_snr_mix_args", "wj_mse_groups": "wj_mse_groups_args",
                    "wj_audio_prepare": "wj_audio_prepare_args", "wj_noise_prepare": "wj_noise_prepare_args",
                    "wj_conv_ln_gelu_bwd": "wj_conv_ln_bwd_args", "wj_conv0_ln_gelu_bwd": "wj_conv0_ln_bwd_args"}[fn]
@@ -555,6 +555,22 @@ def masked_mse(preds: Ptr, targets: Ptr, tgt: Ptr, loss: Ptr, workspace: Ptr, *,
                stream: Optional[int] = None) -> None:
     _run("wj_masked_mse", "wj_mse_args", stream, preds=_p(preds), targets=_p(targets), tgt=_p(tgt), rows=_p(rows), loss=_p(loss),
          dpreds=_p(dpreds), workspace=_p(workspace), gscale_ptr=_p(gscale_ptr), B=B, G=G, T=T, D=D, n_rows=n_rows, gscale=gscale)
+
+
+LOSS_KINDS = {"mse": _abi.DEFINES["WJ_LOSS_MSE"], "l1": _abi.DEFINES["WJ_LOSS_L1"], "smooth_l1": _abi.DEFINES["WJ_LOSS_SMOOTH_L1"],
+              "huber": _abi.DEFINES["WJ_LOSS_HUBER"]}
+
+
+def masked_loss(preds: Ptr, targets: Ptr, tgt: Ptr, loss: Ptr, workspace: Ptr, *, B: int, G: int, T: int, D: int, kind: str,
+                beta: float = 1.0, dpreds: Ptr = None, gscale: float = 1.0, gscale_ptr: Ptr = None, rows: Ptr = None, n_rows: int = 0,
+                stream: Optional[int] = None) -> None:
+    """masked_mse with the per-element loss of `kind` ("mse" | "l1" | "smooth_l1" | "huber"); beta is smooth-L1's beta / Huber's delta
+    (see include/wavjepa_hip.h: wj_loss_args)."""
+    if kind not in LOSS_KINDS:
+        raise ValueError(f"masked_loss: unknown kind {kind!r} (one of {sorted(LOSS_KINDS)})")
+    _run("wj_masked_loss", "wj_loss_args", stream, preds=_p(preds), targets=_p(targets), tgt=_p(tgt), rows=_p(rows), loss=_p(loss),
+         dpreds=_p(dpreds), workspace=_p(workspace), gscale_ptr=_p(gscale_ptr), B=B, G=G, T=T, D=D, n_rows=n_rows, gscale=gscale,
+         kind=LOSS_KINDS[kind], beta=beta)
 
 
 # ---------------------------------------------------------------------------------------------------------- optimiser side
