@@ -402,8 +402,18 @@ int wj_attn_stream_bwd(const wj_attn_bwd_args*, void* stream);
  * Conv layer 0 (C_in x k x stride, no bias) + GroupNorm(C, C) + erf-GELU, channels-last output.
  * Replaces cnn[0] = Conv1d -> Dropout(0) -> GroupNorm(dim, dim) -> GELU (audio_feature_extractor.py:90-96).
  *   audio: bf16 [N][C_in][L];  w: bf16 [C][C_in][k];  gamma/beta: f32 [C];
- *   act: bf16 [N][P][C] (rows >= L_out of every clip are written as 0);  mean/rstd: f32 [N][C] (of the bf16-rounded
- *   conv output over time, biased variance, eps 1e-5).  C % 16 == 0 (the statistics pass runs on the matrix cores); C_in*k in {10, 20}.
+ *   act: bf16 [N][P][C] (rows >= L_out of every clip are written as 0);  mean/rstd: f32 [N][C] (over time, biased variance,
+ *   mean = s1 / L_out and var = max(s2 / L_out - mean^2, 0) from fp32 sums s1, s2).  C % 16 == 0; C_in*k in {10, 20}.
+ *   Which conv output the statistics (and yx / x1) are the statistics of depends on the form the launch takes:
+ *     Gram form (the default): s1, s2, yx, x1 come from the clip's patch Gram matrix in double precision, i.e. they are the sums
+ *       of the UNROUNDED conv output sum_q w_q x_{t,q}, rounded to f32 once;
+ *     fallback form: the sums of the bf16-ROUNDED conv output (the tensor act is computed from), accumulated in fp32 on the
+ *       matrix cores.  Taken when the partial Grams do not fit the scratch the fallback sizes for its own records:
+ *       2 G (chunks + 1) > chunks (2 C + C taps + taps) with taps = C_in*k, G = taps + taps^2 and chunks the number of
+ *       statistics chunks of the launch -- that is always at C = 16 (20 taps: C <= 32), and at C <= 32 (20 taps: C <= 64) when the
+ *       clip is one chunk.
+ *   The two differ by the averaged bf16 rounding noise of L_out values (PARITY.md, "Conv layer 0"); act normalises the bf16-rounded
+ *   conv output with whichever statistics the launch formed.
  * -----------------------------------------------------------------------------------------------------------*/
 typedef struct {
     const void* audio;
@@ -414,7 +424,7 @@ typedef struct {
     float* mean;
     float* rstd;
     float* workspace; /* f32 scratch, wj_workspace_bytes("wj_conv0_gn_gelu_fwd") bytes: [N][C][2] folded (sum, sum of squares),
-                         then one partial record per (clip, 1024-step chunk), stored and folded in chunk order (no atomics) */
+                         then one partial record per (clip, statistics chunk), stored and folded in chunk order (no atomics) */
     float* yx;        /* optional f32 [N][C][C_in*k]: sum_t y_t x_{t,q}  (kept for the backward; NULL on inference)  */
     float* x1;        /* optional f32 [N][C_in*k]:    sum_t x_{t,q}      (both or neither)                            */
     int64_t audio_clip_stride; /* elements between consecutive clips of `audio`; 0 = C_in*L (packed).  One channel c of an
