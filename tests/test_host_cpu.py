@@ -299,6 +299,98 @@ def test_workspace_query():
     assert ops.workspace_bytes("wj_mask_scatter_fill_pos_bwd", B=256, T=200, D=384, G=4) == ops.scatter_fill_bwd_partial_rows(256, 200) * 384 * 4
 
 
+def _header_entries():
+    """{stream entry: argument struct} of both headers, read off the prototype lines themselves (not through the binding's parser)."""
+    import re
+    from wavjepa_amd import _abi
+    found = []
+    for path in (_abi.HEADER, _abi.LAB_HEADER):
+        found.append(dict(re.findall(r"^int (wj_\w+)\(const (wj_\w+)\*, void\* stream\);", open(path).read(), flags=re.M)))
+    assert len(found[0]) == 48 and len(found[1]) == 1
+    return {**found[0], **found[1]}
+
+
+def test_workspace_query_never_faults_and_knows_every_entry():
+    """wj_workspace_bytes takes caller input, so no argument set may kill the process: a zeroed struct of every stream entry of both
+    headers is answered in-process with a value >= -1 (an entry the library's table lacks would fail here too: its answer would be the
+    -1 of an unknown name where 0 or more is due), and the entries that refuse zero dimensions answer their smallest valid ones."""
+    from wavjepa_amd import _abi
+    lab = _abi.load_lab()
+    structs = {**_abi.STRUCTS, **_abi.LAB_STRUCTS}
+    smallest = {"wj_conv_ln_gelu_bwd": dict(M=1, C=64),
+                "wj_conv0_ln_gelu_bwd": dict(N=3, C_in=1, C=64, k=10, L_out=162),
+                "wj_rir_convolve": dict(B=2, C=1, T=1, L=1, fft_size=1024),
+                "wj_snr_mix": dict(B=1, C=1, T=1),
+                "wj_mse_groups": dict(G=2, n=1),
+                "wj_audio_prepare": dict(table=1, n_clips=2, B=2, max_len=100, orig=2, nw=1, width=136, taps=274, out_len=1000),
+                "wj_noise_prepare": dict(B=2, n_clips=2, max_len=8000, out_len=5000, fade_len=640),
+                "wj_conv0_gn_gelu_fwd": dict(N=1, C_in=1, C=16, k=10, L_out=1)}
+    refused = set()
+    for fn, struct in _header_entries().items():
+        zero = int(lab.wj_workspace_bytes(fn.encode(), ctypes.byref(structs[struct]())))
+        print(f"{fn}: zeroed {struct} -> {zero}")
+        assert zero >= -1, fn
+        if zero == -1:
+            refused.add(fn)
+            need = int(lab.wj_workspace_bytes(fn.encode(), ctypes.byref(structs[struct](**smallest[fn]))))
+            print(f"{fn}: {smallest[fn]} -> {need}")
+            assert need >= 0, (fn, need)
+    assert refused == set(smallest)
+    assert lab.wj_workspace_bytes(b"wj_no_such_entry", ctypes.byref(structs["wj_gemm_args"]())) == -1
+    rel = _abi.load()                                              # the release library: the same answers, minus the laboratory entry
+    for fn, struct in _header_entries().items():
+        a = structs[struct]()
+        want = -1 if fn in _abi.LAB_FUNCTIONS else int(lab.wj_workspace_bytes(fn.encode(), ctypes.byref(a)))
+        assert int(rel.wj_workspace_bytes(fn.encode(), ctypes.byref(a))) == want, fn
+
+
+def test_derived_prototypes_equal_the_former_hand_table():
+    """The binding derives argtypes / restype from the headers' prototypes; these twelve were once written by hand."""
+    from wavjepa_amd import _abi
+    i, p, s = ctypes.c_int, ctypes.c_void_p, ctypes.c_char_p
+    by_hand = {"wj_abi_version": [], "wj_device_count": [], "wj_struct_size": [s], "wj_debug_persist_stamps": [p, i],
+               "wj_gemm_release_stream": [p], "wj_ln_bwd_partial_rows": [i, i], "wj_ln_pre_bwd_partial_rows": [i, i],
+               "wj_conv_ln_bwd_partial_rows": [i, i], "wj_scatter_fill_bwd_partial_rows": [i, i], "wj_rccl_unique_id": [p],
+               "wj_rccl_bucket_allreduce_init": [p], "wj_rccl_bucket_allreduce_finalize": []}
+    lab = _abi.load_lab()
+    for fn, argtypes in by_hand.items():
+        f = getattr(lab, fn)
+        assert list(f.argtypes) == argtypes and f.restype is ctypes.c_int, fn
+    assert lab.wj_workspace_bytes.restype is ctypes.c_int64 and list(lab.wj_workspace_bytes.argtypes) == [s, p]
+    assert set(_abi.FUNCTIONS + _abi.LAB_FUNCTIONS) == set(by_hand) | {"wj_workspace_bytes"} | set(_abi.ENTRY_ARGS)
+    for fn in _abi.ENTRY_ARGS:                                       # every stream entry: (const ARGS*, void* stream) -> int
+        f = getattr(lab, fn)
+        assert list(f.argtypes) == [p, p] and f.restype is ctypes.c_int, fn
+
+
+def test_entry_args_pairs_every_entry_with_its_struct_and_ops_sets_only_its_fields():
+    import ast
+    import inspect
+    from wavjepa_amd import _abi, ops
+    assert _abi.ENTRY_ARGS == _header_entries()
+    structs = {**_abi.STRUCTS, **_abi.LAB_STRUCTS}
+    tree = ast.parse(inspect.getsource(ops))
+    calls = [c for c in ast.walk(tree) if isinstance(c, ast.Call) and isinstance(c.func, ast.Name)]
+    seen = set()
+    for fdef in [n for n in tree.body if isinstance(n, ast.FunctionDef)]:
+        for c in [c for c in ast.walk(fdef) if isinstance(c, ast.Call) and isinstance(c.func, ast.Name) and c.func.id in ("_run", "_call")]:
+            if fdef.name == "_run":
+                continue                                              # (_run's own _call passes the name through)
+            if isinstance(c.args[0], ast.Constant):
+                entries = [c.args[0].value]
+            else:                                                     # a shared body: the entries its callers name
+                entries = [k.args[0].value for k in calls if k.func.id == fdef.name]
+                assert len(entries) == 2, fdef.name
+            fields = {k.arg for k in c.keywords if k.arg is not None} if c.func.id == "_run" else set()
+            for entry in entries:
+                have = {f for f, _ in structs[_abi.ENTRY_ARGS[entry]]._fields_}
+                assert fields <= have, (entry, sorted(fields - have))
+                assert ops._ENTRY_STRUCT[entry] is structs[_abi.ENTRY_ARGS[entry]]
+                seen.add(entry)
+    assert seen == set(_abi.ENTRY_ARGS), sorted(set(_abi.ENTRY_ARGS) - seen)
+    assert {f"x{i}" for i in range(8)} <= {f for f, _ in _abi.STRUCTS["wj_instnorm_mean_args"]._fields_}      # instnorm_mean's **kw
+
+
 def test_engine_pair_rule_matches_the_library():
     """engine._pair_pays (which dgrads take the row form because the library will run them as K-split pairs) must agree with the
     library's own eligibility rule (wj_workspace_bytes > 0) on every shape of a grid -- two copies of one rule, kept honest."""

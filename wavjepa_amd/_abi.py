@@ -31,75 +31,69 @@ def _strip_comments(text: str) -> str:
     return re.sub(r"//[^\n]*", "", text)
 
 
-def parse_header(path: str = HEADER) -> Tuple[Dict[str, List[Tuple[str, object]]], List[str], Dict[str, int]]:
-    """Returns ({struct name: [(field, ctype)]}, [function names], {enum constant: value})."""
-    text = _strip_comments(open(path).read())
-    defines = {k: int(v, 0) for k, v in re.findall(r"^\s*#\s*define\s+(WJ_\w+)\s+(-?(?:0x[0-9a-fA-F]+|\d+))\s*$", text, flags=re.M)}
-    structs: Dict[str, List[Tuple[str, object]]] = {}
-    for body, name in re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", text, flags=re.S):
-        fields: List[Tuple[str, object]] = []
-        for decl in body.split(";"):
-            decl = decl.strip()
-            if not decl:
-                continue
-            is_ptr = "*" in decl
-            toks = decl.replace("*", " * ").split()
-            toks = [t for t in toks if t != "const"]
-            base = toks[0]
-            names = "".join(toks[1:]).replace("*", "").split(",")
-            for n in names:
-                n = n.strip()
-                if not n:
+class Header:
+    """What the binding needs of one header: {struct: [(field, ctype)]}, {function: (restype, [argtypes])} in declaration order,
+    {stream entry `int f(const S*, void* stream)`: S}, {enum constant: value} and the integer `#define WJ_x value` constants."""
+
+    def __init__(self, path: str):
+        text = _strip_comments(open(path).read())
+        self.defines = {k: int(v, 0) for k, v in re.findall(r"^\s*#\s*define\s+(WJ_\w+)\s+(-?(?:0x[0-9a-fA-F]+|\d+))\s*$", text, flags=re.M)}
+        self.structs: Dict[str, List[Tuple[str, object]]] = {}
+        for body, name in re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", text, flags=re.S):
+            fields: List[Tuple[str, object]] = []
+            for decl in body.split(";"):
+                decl = decl.strip()
+                if not decl:
                     continue
-                ctype = ctypes.c_void_p if is_ptr else _SCALARS[base]
-                arr = re.match(r"(\w+)\[(\w+)\]$", n)          # fixed-size array member: name[N] (N a number or a #define)
-                if arr:
-                    n, dim = arr.group(1), arr.group(2)
-                    ctype = ctype * (int(dim) if dim.isdigit() else defines[dim])
-                fields.append((n, ctype))
-        structs[name] = fields
-    funcs = re.findall(r"\bint\s+(wj_\w+)\s*\(", text)
-    enums: Dict[str, int] = {}
-    for body in re.findall(r"enum\s*\{(.*?)\}\s*;", text, flags=re.S):
-        val = -1
-        for item in body.split(","):
-            item = item.strip()
-            if not item:
-                continue
-            if "=" in item:
-                k, v = item.split("=")
-                val = int(v.strip(), 0)
-                enums[k.strip()] = val
-            else:
-                val += 1
-                enums[item] = val
-    return structs, funcs, enums
+                is_ptr = "*" in decl
+                toks = decl.replace("*", " * ").split()
+                toks = [t for t in toks if t != "const"]
+                base = toks[0]
+                names = "".join(toks[1:]).replace("*", "").split(",")
+                for n in names:
+                    n = n.strip()
+                    if not n:
+                        continue
+                    ctype = ctypes.c_void_p if is_ptr else _SCALARS[base]
+                    arr = re.match(r"(\w+)\[(\w+)\]$", n)          # fixed-size array member: name[N] (N a number or a #define)
+                    if arr:
+                        n, dim = arr.group(1), arr.group(2)
+                        ctype = ctype * (int(dim) if dim.isdigit() else self.defines[dim])
+                    fields.append((n, ctype))
+            self.structs[name] = fields
+        self.functions: Dict[str, Tuple[object, list]] = {}
+        self.entry_args: Dict[str, str] = {}
+        for ret, name, params in re.findall(r"\b(int|int64_t)\s+(wj_\w+)\s*\(([^)]*)\)\s*;", text):
+            params = [" ".join(p.replace("*", " * ").split()) for p in params.split(",") if p.strip() != "void"]
+            self.functions[name] = (_SCALARS[ret], [_param_ctype(p) for p in params])
+            entry = re.fullmatch(r"const (wj_\w+) \*", params[0]) if len(params) == 2 and params[1] == "void * stream" else None
+            if entry:
+                self.entry_args[name] = entry.group(1)
+        self.enums: Dict[str, int] = {}
+        for body in re.findall(r"enum\s*\{(.*?)\}\s*;", text, flags=re.S):
+            val = -1
+            for item in filter(None, map(str.strip, body.split(","))):
+                k, _, v = item.partition("=")
+                val = int(v.strip(), 0) if v else val + 1
+                self.enums[k.strip()] = val
 
 
-def parse_defines(path: str = HEADER) -> Dict[str, int]:
-    """Integer `#define NAME value` constants of the header (WJ_ABI_VERSION, WJ_GROUP_STATS_SPLIT, ...)."""
-    text = _strip_comments(open(path).read())
-    return {k: int(v, 0) for k, v in re.findall(r"^\s*#\s*define\s+(WJ_\w+)\s+(-?(?:0x[0-9a-fA-F]+|\d+))\s*$", text, flags=re.M)}
+def _param_ctype(param: str):
+    """ctypes type of one prototype parameter: `const char*` is a string, any other pointer an address, the rest a scalar."""
+    if "*" in param:
+        return ctypes.c_char_p if param.startswith("const char *") else ctypes.c_void_p
+    return _SCALARS[param.split()[0]]
 
 
-_STRUCT_FIELDS, FUNCTIONS, ENUMS = parse_header()
-DEFINES = parse_defines()
-_LAB_STRUCT_FIELDS, LAB_FUNCTIONS, _ = parse_header(LAB_HEADER)
+_HEADER, _LAB = Header(HEADER), Header(LAB_HEADER)
+_STRUCT_FIELDS, ENUMS, DEFINES = _HEADER.structs, _HEADER.enums, _HEADER.defines
+FUNCTIONS, LAB_FUNCTIONS = list(_HEADER.functions), list(_LAB.functions)
+_PROTOTYPES = {**_HEADER.functions, **_LAB.functions}            # name -> (restype, argtypes)
+ENTRY_ARGS = {**_HEADER.entry_args, **_LAB.entry_args}           # stream entry -> its argument struct
 
 
-def _make_struct(name: str, fields):
-    return type(name, (ctypes.Structure,), {"_fields_": fields})
-
-
-STRUCTS = {name: _make_struct(name, fields) for name, fields in _STRUCT_FIELDS.items()}
-LAB_STRUCTS = {name: _make_struct(name, fields) for name, fields in _LAB_STRUCT_FIELDS.items()}
-_NO_STREAM_FUNCS = {"wj_abi_version": [], "wj_device_count": [], "wj_struct_size": [ctypes.c_char_p],
-                    "wj_debug_persist_stamps": [ctypes.c_void_p, ctypes.c_int], "wj_gemm_release_stream": [ctypes.c_void_p],
-                    "wj_ln_bwd_partial_rows": [ctypes.c_int, ctypes.c_int], "wj_ln_pre_bwd_partial_rows": [ctypes.c_int, ctypes.c_int],
-                    "wj_conv_ln_bwd_partial_rows": [ctypes.c_int, ctypes.c_int],
-                    "wj_scatter_fill_bwd_partial_rows": [ctypes.c_int, ctypes.c_int],
-                    "wj_rccl_unique_id": [ctypes.c_void_p],
-                    "wj_rccl_bucket_allreduce_init": [ctypes.c_void_p], "wj_rccl_bucket_allreduce_finalize": []}
+STRUCTS = {name: type(name, (ctypes.Structure,), {"_fields_": fields}) for name, fields in _STRUCT_FIELDS.items()}
+LAB_STRUCTS = {name: type(name, (ctypes.Structure,), {"_fields_": fields}) for name, fields in _LAB.structs.items()}
 
 _lib = None
 _lab_lib = None
@@ -144,18 +138,10 @@ def _load(LIB_PATH: str, FUNCTIONS, STRUCTS):
         if not hasattr(lib, fn):
             raise WavJepaHipError(f"{LIB_PATH} does not export {fn} (declared in include/wavjepa_hip.h); rebuild it")
         f = getattr(lib, fn)
-        f.restype = ctypes.c_int
-        if fn in _NO_STREAM_FUNCS:
-            f.argtypes = _NO_STREAM_FUNCS[fn]
-        else:
-            f.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        f.restype, f.argtypes = _PROTOTYPES[fn]
     if lib.wj_abi_version() != DEFINES["WJ_ABI_VERSION"]:
         raise WavJepaHipError(f"{LIB_PATH} reports ABI version {lib.wj_abi_version()}, include/wavjepa_hip.h declares "
                               f"{DEFINES['WJ_ABI_VERSION']}: stale library, rebuild it (python -m wavjepa_amd.build)")
-    if not hasattr(lib, "wj_workspace_bytes"):
-        raise WavJepaHipError(f"{LIB_PATH} does not export wj_workspace_bytes; rebuild it")
-    lib.wj_workspace_bytes.restype = ctypes.c_int64
-    lib.wj_workspace_bytes.argtypes = [ctypes.c_char_p, ctypes.c_void_p]
     for name, cls in STRUCTS.items():
         want = lib.wj_struct_size(name.encode())
         if want != ctypes.sizeof(cls):

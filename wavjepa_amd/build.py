@@ -1,6 +1,7 @@
 """Build libwavjepa_hip.so (gfx950) in-tree with hipcc.  No torch dependency: plain HIP + a C ABI."""
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -12,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libwavjepa_hip.so")
 LAB_LIB = os.path.join(LIBDIR, "libwavjepa_hip_lab.so")      # the same sources with -DWJ_LAB (include/wavjepa_hip_lab.h): diagnostics + A/B switches
-SOURCES = ["gemm.hip", "gemm_persist.hip", "gemm_pde.hip", "gemm_panel.hip", "norm.hip", "attention.hip", "attention_stream.hip", "conv0.hip", "conv_ln.hip", "misc.hip", "fp8.hip", "scene.hip", "denoise.hip", "audio_prep.hip", "noise_prep.hip", "rccl_bucket.hip"]
+SOURCES = ["gemm.hip", "gemm_persist.hip", "gemm_pde.hip", "gemm_panel.hip", "norm.hip", "attention.hip", "attention_stream.hip", "conv0.hip", "conv_ln.hip", "misc.hip", "abi.hip", "fp8.hip", "scene.hip", "denoise.hip", "audio_prep.hip", "noise_prep.hip", "rccl_bucket.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-value"]
 
 
@@ -38,7 +39,7 @@ def build(force: bool = False, verbose: bool = True, lab: bool = False) -> str:
     objdir = os.path.join(LIBDIR, "obj_lab" if lab else "obj")
     os.makedirs(objdir, exist_ok=True)
     inc = os.path.join(os.path.dirname(HERE), "include")
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_internal.h"), os.path.join(CSRC, "gemm_pieces.h"), os.path.join(CSRC, "attention_pieces.h"), os.path.join(inc, "wavjepa_hip.h"), os.path.join(inc, "wavjepa_hip_lab.h")]
+    headers = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(inc, "*.h"))
     flags = FLAGS + (["-DWJ_LAB"] if lab else [])
     lib = LAB_LIB if lab else LIB
     jobs = []

@@ -524,6 +524,9 @@ extern "C" int wj_attn_fwd(const wj_attn_fwd_args* a, void* stream) {
     return WJ_OK;
 }
 
+// scratch of wj_attn_bwd and wj_attn_stream_bwd: the dbias_ws rows attn_fold_dbias folds
+int64_t wj_attn_bwd_ws_bytes(const wj_attn_bwd_args* a) { return a->B * attn_dbias_row(a) * 4; }
+
 extern "C" int wj_attn_bwd(const wj_attn_bwd_args* a, void* stream) {
     WJ_CLEAR_STALE_ERROR();
     int rc = attn_check_args(a, WHOLE_IMAGE_LIMITS);

@@ -352,12 +352,14 @@ inline int attn_check_args(const wj_attn_bwd_args* a, AttnLimits lim) {
     if (rc != WJ_OK) return rc;
     return a->dbias && !a->dbias_ws ? WJ_ERR_ARG : WJ_OK;
 }
+// dbias_ws of both backward entries: one row of 3 * H * hd floats per sequence
+inline int64_t attn_dbias_row(const wj_attn_bwd_args* a) { return (int64_t)3 * a->H * a->hd; }
 // The tail of both backward entries: the B rows of dbias_ws into dbias, unless the caller folds them later.
 inline int attn_fold_dbias(const wj_attn_bwd_args* a, void* stream) {
     if (!a->dbias || a->defer_fold) return WJ_OK;
     wj_colsum_args c = {};
     c.deterministic = a->deterministic;
-    c.x = a->dbias_ws; c.out = a->dbias; c.ldx = 3L * a->H * a->hd; c.M = a->B; c.N = 3 * a->H * a->hd;
+    c.x = a->dbias_ws; c.out = a->dbias; c.ldx = attn_dbias_row(a); c.M = a->B; c.N = (int)attn_dbias_row(a);
     return wj_colsum_f32(&c, stream);
 }
 

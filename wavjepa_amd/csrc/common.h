@@ -45,6 +45,11 @@ static inline int wj_lab_env_int(const char*, int dflt) { return dflt; }
 static inline const char* wj_lab_env_str(const char*) { return nullptr; }
 #endif
 
+// Most partial rows ([rows][3][D] floats: dgamma | dbeta | dbias) a LayerNorm backward leaves in its workspace: the grid cap of
+// wj_layernorm_bwd / wj_layernorm_pre_bwd (norm.hip) and of wj_conv_ln_gelu_bwd (conv_ln.hip), whose callers hold the same scratch,
+// and the size wj_workspace_bytes answers for the first two.
+constexpr int LN_BWD_MAX_PARTIAL_ROWS = 1536;
+
 __device__ __forceinline__ float bf2f(bf16_t x) { return (float)x; }
 __device__ __forceinline__ bf16_t f2bf(float x) { return (bf16_t)x; }  // v_cvt_pk_bf16_f32: RNE, NaN-preserving
 

@@ -67,8 +67,7 @@ __device__ __forceinline__ void conv4(float (&y)[4], float (&x)[TAPS], const flo
 }
 
 // floats per partial record of the forward statistics pass
-template <int TAPS>
-__host__ __device__ constexpr long fwd_record(int C, int want_yx) { return want_yx ? 2L * C + (long)C * TAPS + TAPS : 2L * C; }
+__host__ __device__ constexpr long fwd_record(int C, int taps, int want_yx) { return want_yx ? 2L * C + (long)C * taps + taps : 2L * C; }
 
 // out[n][i] = sum over chunks (in chunk order) of part[n][chunk][i]; the record is split over up to three outputs
 // ([0, n0) -> o0, [n0, n0 + n1) -> o1, the rest -> o2, each [N][.]).  cnt_off != NULL: clip n only has
@@ -116,6 +115,7 @@ inline int stats_tcs(int N, int L_out, int C_in) {
     const int cap = 2176 / (C_in > 0 ? C_in : 1) / 32 * 32;           // the chunk's audio samples live in LDS (bf16, C_in x ~5 tcs): <= ~44 KB
     return tcs > cap ? (cap < 32 ? 32 : cap) : tcs;
 }
+inline int stats_chunks(int L_out, int TCS) { return (L_out + TCS - 1) / TCS; }
 // ---- pass 1, algebraic form (round 5; WJ_CONV0_STATS=mfma selects the pass below instead).  Everything pass 1 produces is a sum over
 // the time axis of products of the conv output y_t = sum_k w_k x_{t,k} with 1, y_t or a patch element x_{t,q}:
 //     sum_t y_t = w . X1,   sum_t y_t^2 = w^T X2 w,   sum_t y_t x_{t,q} = (w^T X2)_q,   with X1 = sum_t x_t, X2 = sum_t x_t x_t^T
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(256) void conv0_stats_mfma_kernel(const bf16_t* __r
     extern __shared__ __attribute__((aligned(16))) bf16_t xa[];   // [C_in][span] samples of this chunk (0 past the clip)
     constexpr int QT = (TAPS + 15) / 16;
     const int n = blockIdx.y, t0 = blockIdx.x * TCS;
-    const long rec = fwd_record<TAPS>(g.C, want_yx);
+    const long rec = fwd_record(g.C, TAPS, want_yx);
     float* sums = part + ((long)n * gridDim.x + blockIdx.x) * rec;   // [C][2]
     float* yx = want_yx ? sums + 2L * g.C : nullptr;                 // [C][TAPS]
     float* x1 = want_yx ? yx + (long)g.C * TAPS : nullptr;           // [TAPS]
@@ -648,8 +648,8 @@ void launch_fwd(const wj_conv0_fwd_args* a, const Geo& g, int span_max, hipStrea
     dim3 grid2((a->P + TC - 1) / TC, a->N), block(NTH);
     const int want_yx = a->yx != nullptr;
     const int TCS = stats_tcs(a->N, a->L_out, a->C_in);
-    const int chunks = (a->L_out + TCS - 1) / TCS;
-    const long rec = fwd_record<TAPS>(a->C, want_yx);
+    const int chunks = stats_chunks(a->L_out, TCS);
+    const long rec = fwd_record(a->C, TAPS, want_yx);
     float* sums = a->workspace;                       // [N][C][2] folded statistics
     float* part = a->workspace + 2L * a->N * a->C;    // [N][chunks][rec] partial records
     const int span = (TCS - 1) * a->stride + a->k;
@@ -657,7 +657,7 @@ void launch_fwd(const wj_conv0_fwd_args* a, const Geo& g, int span_max, hipStrea
     constexpr long G = TAPS + (long)TAPS * TAPS;
     // (the partial Grams -- doubles -- and their fold share the scratch the pass below sizes for its partial records: they fit unless
     // C < ~4 TAPS)
-    if (gram_mode && 2 * G * (chunks + 1) <= (long)chunks * fwd_record<TAPS>(a->C, 1)) {
+    if (gram_mode && 2 * G * (chunks + 1) <= (long)chunks * fwd_record(a->C, TAPS, 1)) {
         double* gpart = reinterpret_cast<double*>(part);          // [N][chunks][G]   (part is 8-byte aligned: 2 N C floats past a 256-byte-aligned base)
         double* gfold = gpart + (long)a->N * chunks * G;          // [N][G]
         hipLaunchKernelGGL(conv0_gram_kernel<TAPS>, dim3(chunks, a->N), dim3(256), (size_t)a->C_in * span * sizeof(bf16_t), s,
@@ -689,6 +689,10 @@ void launch_fwd(const wj_conv0_fwd_args* a, const Geo& g, int span_max, hipStrea
                        a->gamma, a->beta, (const float*)sums, (bf16_t*)a->act, a->mean, a->rstd, g, span_max, a->eps);
 }
 
+// the backward's scratch: [N][rec] folded + [N][chunks][rec] partial records
+constexpr long bwd_record(int C, int taps) { return (long)C * (2 + taps); }
+inline int bwd_chunks(int max_rows) { return (max_rows + BR - 1) / BR; }
+
 template <int TAPS>
 void launch_bwd(const wj_conv0_bwd_args* a, const Geo& g, hipStream_t s) {
     const size_t lds = (size_t)(BR * TAPS + BR + (2 + TAPS) * 4 * 128) * sizeof(float);
@@ -696,8 +700,8 @@ void launch_bwd(const wj_conv0_bwd_args* a, const Geo& g, hipStream_t s) {
     if (max_rows <= 0) return;
     static int attr = hipFuncSetAttribute((const void*)conv0_bwd_rows_kernel<TAPS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     (void)attr;
-    const int chunks = (max_rows + BR - 1) / BR;
-    const long rec = (long)a->C * (2 + TAPS);
+    const int chunks = bwd_chunks(max_rows);
+    const long rec = bwd_record(a->C, TAPS);
     float* folded = a->workspace;                     // [N][C][2 + TAPS]
     float* part = a->workspace + (long)a->N * rec;    // [N][chunks][C][2 + TAPS]
     dim3 grid(chunks, a->N), block(NTH);
@@ -713,16 +717,14 @@ void launch_bwd(const wj_conv0_bwd_args* a, const Geo& g, hipStream_t s) {
 
 // scratch sizes (wj_workspace_bytes): folded statistics + one partial record per (clip, chunk)
 int64_t wj_conv0_fwd_ws_bytes(const wj_conv0_fwd_args* a) {
-    const int TCS = stats_tcs(a->N, a->L_out, a->C_in);
-    const int taps = a->C_in * a->k, chunks = (a->L_out + TCS - 1) / TCS;
-    const long rec = 2L * a->C + (long)a->C * taps + taps;      // sized for the training form (yx / x1 requested)
+    if (a->L_out <= 0) return -1;                                // (stats_tcs divides by a chunk count taken from L_out)
+    const int chunks = stats_chunks(a->L_out, stats_tcs(a->N, a->L_out, a->C_in));
+    const long rec = fwd_record(a->C, a->C_in * a->k, 1);       // sized for the training form (yx / x1 requested)
     return (2L * a->N * a->C + (long)a->N * chunks * rec) * 4;
 }
 int64_t wj_conv0_bwd_ws_bytes(const wj_conv0_bwd_args* a) {
-    const int taps = a->C_in * a->k;
     const int max_rows = a->max_rows > 0 ? a->max_rows : a->L_out;   // 0: sized for the dense form (every row t < L_out)
-    const int chunks = (max_rows + BR - 1) / BR;
-    return (long)a->N * (1 + chunks) * a->C * (2 + taps) * 4;
+    return (long)a->N * (1 + bwd_chunks(max_rows)) * bwd_record(a->C, a->C_in * a->k) * 4;
 }
 
 extern "C" int wj_conv0_gn_gelu_fwd(const wj_conv0_fwd_args* a, void* stream) {

@@ -196,7 +196,7 @@ int bwd_grid(int rows, int C) {
     const int per_wg = NW * (512 / C) * 4;       // four passes of a workgroup's row slots
     int grid = (rows + per_wg - 1) / per_wg;
     grid = grid < 1 ? 1 : grid;
-    return grid > 1536 ? 1536 : grid;            // the partial rows fit the scratch wj_layernorm_bwd's callers hold ([1536][3][D])
+    return grid > LN_BWD_MAX_PARTIAL_ROWS ? LN_BWD_MAX_PARTIAL_ROWS : grid;   // the partial rows fit the scratch wj_layernorm_bwd's callers hold
 }
 
 bool width_ok(int C) { return C == 64 || C == 128 || C == 256 || C == 512; }
@@ -272,13 +272,12 @@ __global__ __launch_bounds__(THREADS) void conv0_ln_fwd_kernel(wj_conv0_ln_fwd_a
 // Workgroup (chunk, clip): up to BR0 rows of one clip -- listed rows [row_off[n] + chunk * BR0, ...) or time steps chunk * BR0 ... -- and ONE
 // partial record  [C][TAPS] dw | [C] dbias | [C] dgamma | [C] dbeta  stored at part[n][chunk] (zeros when the clip has no row there).
 constexpr int BR0 = 512;
-template <int TAPS>
-__host__ __device__ constexpr int record_floats(int C) { return C * (TAPS + 3); }
+__host__ __device__ constexpr int64_t record_floats(int C, int taps) { return (int64_t)C * (taps + 3); }
 
 template <int LPR, int TAPS>
 __global__ __launch_bounds__(THREADS) void conv0_ln_bwd_kernel(wj_conv0_ln_bwd_args a, long clip_stride, float* __restrict__ part) {
     const RowLanes<LPR> L;
-    constexpr int C = RowLanes<LPR>::C, RPW = RowLanes<LPR>::RPW, REC = record_floats<TAPS>(C);
+    constexpr int C = RowLanes<LPR>::C, RPW = RowLanes<LPR>::RPW, REC = record_floats(C, TAPS);
     __shared__ float racc[REC];
     bf16x2 w2[8][TAPS / 2];                      // the lane's weights, two taps per register
     float bi[8], gam[8], bet[8], dw[8][TAPS], dbs[8], dg[8], db[8];
@@ -385,7 +384,7 @@ int conv0_chunks(int L_out, int max_rows) { return ((max_rows > 0 ? max_rows : L
 
 template <int LPR, int TAPS>
 void launch_conv0_bwd(const wj_conv0_ln_bwd_args* a, long clip_stride, hipStream_t s) {
-    constexpr int C = LPR * 8, REC = record_floats<TAPS>(C);
+    constexpr int C = LPR * 8, REC = record_floats(C, TAPS);
     const int chunks = conv0_chunks(a->L_out, a->rows ? a->max_rows : 0);
     float* folded = a->workspace;                         // [N][REC]
     float* part = a->workspace + (long)a->N * REC;        // [N][chunks][REC]
@@ -402,8 +401,7 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // scratch of wj_conv0_ln_gelu_bwd -- wj_workspace_bytes("wj_conv0_ln_gelu_bwd", args): folded [N][rec] + partial records [N][chunks][rec]
 int64_t wj_conv0_ln_bwd_ws_bytes(const wj_conv0_ln_bwd_args* a) {
     if (!a || a->N <= 0 || a->C <= 0 || a->C_in <= 0 || a->k <= 0 || a->L_out <= 0 || a->max_rows < 0) return -1;
-    const int64_t rec = (int64_t)a->C * (a->C_in * a->k + 3);
-    return (int64_t)a->N * (1 + conv0_chunks(a->L_out, a->max_rows)) * rec * 4;
+    return (int64_t)a->N * (1 + conv0_chunks(a->L_out, a->max_rows)) * record_floats(a->C, a->C_in * a->k) * 4;
 }
 
 extern "C" int wj_conv_ln_gelu_fwd(const wj_conv_ln_fwd_args* a, void* stream) {
@@ -425,6 +423,11 @@ extern "C" int wj_conv_ln_gelu_fwd(const wj_conv_ln_fwd_args* a, void* stream) {
 extern "C" int wj_conv_ln_bwd_partial_rows(int rows, int C) {
     if (rows < 0 || !width_ok(C)) return -1;
     return bwd_grid(rows, C);
+}
+// workspace of wj_conv_ln_gelu_bwd: its partial rows [rows][3][C]
+int64_t wj_conv_ln_bwd_ws_bytes(const wj_conv_ln_bwd_args* a) {
+    const int rows = wj_conv_ln_bwd_partial_rows(a->rows ? a->n_rows : a->M, a->C);
+    return rows < 0 ? -1 : (int64_t)rows * 3 * a->C * 4;
 }
 
 extern "C" int wj_conv_ln_gelu_bwd(const wj_conv_ln_bwd_args* a, void* stream) {

@@ -1,7 +1,6 @@
 // HBM-bound plumbing kernels of the WavJEPA step for gfx950: token gather/scatter, positions, conv weight layouts,
 // GELU backward, teacher targets (joint instance norm), masked MSE, EMA, AdamW (+ global-norm clip), casts and the
 // crop/normalise batch preparation.  All are vectorised (8-16 B per lane) streaming kernels or small reductions.
-#include <string.h>
 #include "common.h"
 #include "../../include/wavjepa_hip.h"
 #ifdef WJ_LAB
@@ -616,88 +615,6 @@ __global__ __launch_bounds__(1024) void crop_kernel(wj_crop_args a) {
 
 #define STREAM ((hipStream_t)stream)
 
-extern "C" int wj_abi_version(void) { return WJ_ABI_VERSION; }
-extern "C" int wj_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-extern "C" int wj_struct_size(const char* name) {
-    if (!name) return -1;
-#define WJ_SZ(T) if (!strcmp(name, #T)) return (int)sizeof(T);
-    WJ_SZ(wj_gemm_args) WJ_SZ(wj_ln_fwd_args) WJ_SZ(wj_ln_bwd_args) WJ_SZ(wj_ln_pre_fwd_args) WJ_SZ(wj_ln_pre_bwd_args) WJ_SZ(wj_colsum_args) WJ_SZ(wj_attn_fwd_args)
-    WJ_SZ(wj_attn_bwd_args) WJ_SZ(wj_conv0_fwd_args) WJ_SZ(wj_conv0_bwd_args) WJ_SZ(wj_gelu_bwd_args) WJ_SZ(wj_conv_w_args)
-    WJ_SZ(wj_add_pos_args) WJ_SZ(wj_gather_args) WJ_SZ(wj_scatter_fill_args) WJ_SZ(wj_scatter_fill_bwd_args)
-    WJ_SZ(wj_unmask_rows_args) WJ_SZ(wj_instnorm_args) WJ_SZ(wj_mse_args) WJ_SZ(wj_loss_args) WJ_SZ(wj_ema_args) WJ_SZ(wj_sumsq_args)
-    WJ_SZ(wj_adamw_args) WJ_SZ(wj_cast_args) WJ_SZ(wj_crop_args) WJ_SZ(wj_zero_rows_args) WJ_SZ(wj_instnorm_mean_args) WJ_SZ(wj_spin_args)
-    WJ_SZ(wj_gemm_fp8_args) WJ_SZ(wj_quantize_fp8_args) WJ_SZ(wj_wgrad_group_args) WJ_SZ(wj_rir_conv_args) WJ_SZ(wj_snr_mix_args) WJ_SZ(wj_resample_args) WJ_SZ(wj_mse_groups_args) WJ_SZ(wj_transpose_args) WJ_SZ(wj_colsum_group_args) WJ_SZ(wj_rccl_init_args) WJ_SZ(wj_rccl_launch_args) WJ_SZ(wj_rccl_wait_args) WJ_SZ(wj_audio_prepare_args) WJ_SZ(wj_noise_prepare_args)
-    WJ_SZ(wj_conv_ln_fwd_args) WJ_SZ(wj_conv_ln_bwd_args) WJ_SZ(wj_conv0_ln_fwd_args) WJ_SZ(wj_conv0_ln_bwd_args)
-#ifdef WJ_LAB
-    WJ_SZ(wj_collective_footprint_args)
-#endif
-#undef WJ_SZ
-    return -1;
-}
-
-int64_t wj_gemm_ws_bytes(const wj_gemm_args* a);              // csrc/gemm.hip
-int64_t wj_wgrad_group_ws_bytes(const wj_wgrad_group_args* a);
-int64_t wj_colsum_bf16_ws_bytes(const wj_colsum_args* a);     // csrc/norm.hip
-int64_t wj_conv0_fwd_ws_bytes(const wj_conv0_fwd_args* a);   // csrc/conv0.hip
-int64_t wj_conv0_bwd_ws_bytes(const wj_conv0_bwd_args* a);
-int64_t wj_rir_conv_ws_bytes(const wj_rir_conv_args* a);      // csrc/scene.hip
-int64_t wj_snr_mix_ws_bytes(const wj_snr_mix_args* a);
-int64_t wj_mse_groups_ws_bytes(const wj_mse_groups_args* a);  // csrc/denoise.hip
-int64_t wj_audio_prepare_ws_bytes(const wj_audio_prepare_args* a);  // csrc/audio_prep.hip
-int64_t wj_noise_prepare_ws_bytes(const wj_noise_prepare_args* a);  // csrc/noise_prep.hip
-int64_t wj_conv0_ln_bwd_ws_bytes(const wj_conv0_ln_bwd_args* a);    // csrc/conv_ln.hip
-
-extern "C" int64_t wj_workspace_bytes(const char* fn, const void* args) {
-    if (!fn || !args) return -1;
-    if (!strcmp(fn, "wj_gemm_bf16")) return wj_gemm_ws_bytes((const wj_gemm_args*)args);
-    if (!strcmp(fn, "wj_wgrad_grouped")) return wj_wgrad_group_ws_bytes((const wj_wgrad_group_args*)args);
-    if (!strcmp(fn, "wj_colsum_bf16")) return wj_colsum_bf16_ws_bytes((const wj_colsum_args*)args);
-    if (!strcmp(fn, "wj_mask_scatter_fill_pos_bwd")) {           // `partials`: one row of D floats per workgroup
-        const wj_scatter_fill_bwd_args* a = (const wj_scatter_fill_bwd_args*)args;
-        return (int64_t)wj_scatter_fill_bwd_partial_rows(a->B, a->T) * a->D * 4;
-    }
-    if (!strcmp(fn, "wj_layernorm_bwd")) return 1536LL * 3 * ((const wj_ln_bwd_args*)args)->D * 4;
-    if (!strcmp(fn, "wj_layernorm_pre_bwd")) return 1536LL * 3 * ((const wj_ln_pre_bwd_args*)args)->D * 4;   // the same grid cap
-    if (!strcmp(fn, "wj_attn_bwd") || !strcmp(fn, "wj_attn_stream_bwd")) {      // dbias_ws: one row per sequence in both families
-        const wj_attn_bwd_args* a = (const wj_attn_bwd_args*)args;
-        return (int64_t)a->B * 3 * a->H * a->hd * 4;
-    }
-    if (!strcmp(fn, "wj_conv0_gn_gelu_fwd")) return wj_conv0_fwd_ws_bytes((const wj_conv0_fwd_args*)args);
-    if (!strcmp(fn, "wj_conv0_gn_gelu_bwd")) return wj_conv0_bwd_ws_bytes((const wj_conv0_bwd_args*)args);
-    if (!strcmp(fn, "wj_masked_mse")) {
-        const wj_mse_args* a = (const wj_mse_args*)args;
-        return (2 + (int64_t)a->B * a->G * a->T) * 4;
-    }
-    if (!strcmp(fn, "wj_masked_loss")) {
-        const wj_loss_args* a = (const wj_loss_args*)args;
-        return (2 + (int64_t)a->B * a->G * a->T) * 4;
-    }
-    if (!strcmp(fn, "wj_grad_sumsq")) return 1024 * 4;
-    if (!strcmp(fn, "wj_rir_convolve")) return wj_rir_conv_ws_bytes((const wj_rir_conv_args*)args);
-    if (!strcmp(fn, "wj_snr_mix")) return wj_snr_mix_ws_bytes((const wj_snr_mix_args*)args);
-    if (!strcmp(fn, "wj_mse_groups")) return wj_mse_groups_ws_bytes((const wj_mse_groups_args*)args);
-    if (!strcmp(fn, "wj_audio_prepare")) return wj_audio_prepare_ws_bytes((const wj_audio_prepare_args*)args);
-    if (!strcmp(fn, "wj_noise_prepare")) return wj_noise_prepare_ws_bytes((const wj_noise_prepare_args*)args);
-    if (!strcmp(fn, "wj_conv0_ln_gelu_bwd")) return wj_conv0_ln_bwd_ws_bytes((const wj_conv0_ln_bwd_args*)args);
-    if (!strcmp(fn, "wj_conv_ln_gelu_bwd")) {                     // its partial rows [rows][3][C]
-        const wj_conv_ln_bwd_args* a = (const wj_conv_ln_bwd_args*)args;
-        const int rows = wj_conv_ln_bwd_partial_rows(a->rows ? a->n_rows : a->M, a->C);
-        return rows < 0 ? -1 : (int64_t)rows * 3 * a->C * 4;
-    }
-    static const char* const none[] = {"wj_conv_ln_gelu_fwd", "wj_conv0_ln_gelu_fwd", "wj_layernorm_fwd", "wj_layernorm_pre_fwd", "wj_colsum_f32", "wj_attn_fwd", "wj_attn_stream_fwd", "wj_gelu_bwd_bf16",
-        "wj_conv_weight_layout", "wj_add_pos", "wj_mask_gather_rows", "wj_mask_scatter_fill_pos",
-        "wj_unmask_rows_f32", "wj_instnorm_accumulate", "wj_instnorm_mean", "wj_ema_update", "wj_adamw_step", "wj_cast_f32_to_bf16",
-        "wj_crop_normalize_bf16", "wj_zero_rows", "wj_spin", "wj_gemm_mxfp8", "wj_quantize_mxfp8", "wj_resample_fir", "wj_transpose_bf16", "wj_colsum_f32_group", "wj_rccl_bucket_allreduce_launch", "wj_rccl_bucket_allreduce_wait", "wj_collective_footprint"};
-    for (const char* n : none)
-        if (!strcmp(fn, n)) return 0;
-    return -1;
-}
-
 extern "C" int wj_gelu_bwd_bf16(const wj_gelu_bwd_args* a, void* stream) {
     WJ_CLEAR_STALE_ERROR();
     if (a && a->rows) {
@@ -834,13 +751,15 @@ extern "C" int wj_mask_scatter_fill_pos(const wj_scatter_fill_args* a, void* str
 }
 
 extern "C" int wj_scatter_fill_bwd_partial_rows(int B, int T) { return (int)(((long)B * T + SFB_ROWS - 1) / SFB_ROWS); }
+// `partials`: one row of D floats per workgroup
+int64_t wj_scatter_fill_bwd_ws_bytes(const wj_scatter_fill_bwd_args* a) { return (int64_t)wj_scatter_fill_bwd_partial_rows(a->B, a->T) * a->D * 4; }
 
 extern "C" int wj_mask_scatter_fill_pos_bwd(const wj_scatter_fill_bwd_args* a, void* stream) {
     WJ_CLEAR_STALE_ERROR();
     if (!a || !a->d_in || !a->inv || !a->d_ctx_feats || a->B <= 0 || a->T <= 0 || a->D <= 0 || (a->D & 3) || a->D > 1024 ||
         a->G <= 0 || a->G > 15)              // (a wave's 4 rows x (G + 1) indices are fetched by one load per lane)
         return WJ_ERR_ARG;
-    const int grid = (a->B * a->T + SFB_ROWS - 1) / SFB_ROWS;
+    const int grid = wj_scatter_fill_bwd_partial_rows(a->B, a->T);
     if (a->D <= 512) hipLaunchKernelGGL(scatter_fill_bwd_kernel<2>, dim3(grid), dim3(256), (size_t)4 * a->D * sizeof(float), STREAM, *a);
     else hipLaunchKernelGGL(scatter_fill_bwd_kernel<4>, dim3(grid), dim3(256), (size_t)4 * a->D * sizeof(float), STREAM, *a);
     WJ_CHECK_LAUNCH();
@@ -900,6 +819,11 @@ static int masked_loss_launch(const wj_loss_args* a, void* stream) {
     return WJ_OK;
 }
 
+// workspace of both entries: the target count and the loss sum, then one partial per dense position
+static int64_t masked_loss_ws_bytes(int B, int G, int T) { return (2 + (int64_t)B * G * T) * 4; }
+int64_t wj_masked_mse_ws_bytes(const wj_mse_args* a) { return masked_loss_ws_bytes(a->B, a->G, a->T); }
+int64_t wj_masked_loss_ws_bytes(const wj_loss_args* a) { return masked_loss_ws_bytes(a->B, a->G, a->T); }
+
 extern "C" int wj_masked_mse(const wj_mse_args* a, void* stream) {
     WJ_CLEAR_STALE_ERROR();
     if (!a) return WJ_ERR_ARG;
@@ -922,10 +846,13 @@ extern "C" int wj_ema_update(const wj_ema_args* a, void* stream) {
     return WJ_OK;
 }
 
+constexpr int SUMSQ_MAX_GRID = 1024;           // one partial float per workgroup in the workspace
+int64_t wj_grad_sumsq_ws_bytes(const wj_sumsq_args*) { return SUMSQ_MAX_GRID * 4; }
+
 extern "C" int wj_grad_sumsq(const wj_sumsq_args* a, void* stream) {
     WJ_CLEAR_STALE_ERROR();
     if (!a || !a->g || !a->out || !a->workspace || a->n <= 0 || (a->n & 3)) return WJ_ERR_ARG;
-    int grid = grid_for(a->n / 4, 256, 1024);
+    int grid = grid_for(a->n / 4, 256, SUMSQ_MAX_GRID);
     if (a->workgroups > 0 && a->workgroups < grid) grid = a->workgroups;
     hipLaunchKernelGGL(sumsq_partial_kernel, dim3(grid), dim3(256), 0, STREAM, a->g, a->workspace, (long)a->n);
     hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(1024), 0, STREAM, (const float*)a->workspace, a->out, grid, a->accumulate);

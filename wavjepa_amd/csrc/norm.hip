@@ -621,7 +621,7 @@ int ln_bwd_grid(int M, int D) {
     // not all sit in the same phase).
     const int passes = (half ? (M + 1) / 2 : M) <= ln_bwd_one_pass_rows() ? 1 : 4;
     int grid = (M + 2 * passes * nw * rpw - 1) / (2 * passes * nw * rpw);
-    return grid > 1536 ? 1536 : grid;
+    return grid > LN_BWD_MAX_PARTIAL_ROWS ? LN_BWD_MAX_PARTIAL_ROWS : grid;
 }
 
 // launch of either backward kernel on ln_bwd_grid, then the fold of its workspace rows where gradient outputs are given
@@ -668,6 +668,10 @@ extern "C" int wj_ln_bwd_partial_rows(int M, int D) {
     if (M <= 0 || D <= 0) return -1;
     return ln_bwd_grid(M, D);
 }
+// workspace of either backward, sized for any M: the grid cap's partial rows
+static int64_t ln_bwd_ws_bytes(int D) { return (int64_t)LN_BWD_MAX_PARTIAL_ROWS * 3 * D * 4; }
+int64_t wj_ln_bwd_ws_bytes(const wj_ln_bwd_args* a) { return ln_bwd_ws_bytes(a->D); }
+int64_t wj_ln_pre_bwd_ws_bytes(const wj_ln_pre_bwd_args* a) { return ln_bwd_ws_bytes(a->D); }
 
 extern "C" int wj_colsum_f32_group(const wj_colsum_group_args* a, void* stream) {
     WJ_CLEAR_STALE_ERROR();
