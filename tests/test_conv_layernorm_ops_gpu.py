@@ -75,7 +75,7 @@ def valid_rows():
     return (torch.arange(NCLIP * P) % P) < L
 
 
-@pytest.fixture(scope="module", params=[64, 512])
+@pytest.fixture(scope="module", params=[64, 128, 256, 512])
 def layer(request, ops):
     """One draw per width, shared by the tests of the streaming kernels: inputs, the HIP forward and the three references."""
     C = request.param
@@ -219,7 +219,8 @@ def conv0_refs(audio, w, bias, gamma, beta, dact):
     return out
 
 
-@pytest.mark.parametrize("C,C_in,with_bias,strided", [(64, 1, True, False), (64, 2, False, False), (512, 1, False, True), (512, 2, True, False)])
+@pytest.mark.parametrize("C,C_in,with_bias,strided", [(64, 1, True, False), (64, 2, False, False), (128, 2, True, False), (256, 1, False, True), (512, 1, False, True),
+                                                        (512, 2, True, False)])
 def test_conv0_ln_fwd_bwd(ops, C, C_in, with_bias, strided):
     taps = C_in * K0
     batch = rnd(N0, 2 if strided else C_in, LA, seed=200 + C + C_in, dtype=torch.bfloat16)

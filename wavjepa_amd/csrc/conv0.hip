@@ -12,7 +12,7 @@
 // So the backward is ONE pass over the listed active rows (A1, A2, S) plus a tiny per-(n,c) finalize; the dense part of
 // GroupNorm's backward never touches the activation-sized tensors.
 #include <string.h>
-#include "common.h"
+#include "conv_pieces.h"
 #include "../../include/wavjepa_hip.h"
 
 namespace {
@@ -22,71 +22,17 @@ constexpr int NTH = 256;  // threads
 
 struct Geo {
     int N, C_in, L, C, k, stride, L_out, P;
-    long clip_stride;   // elements between consecutive clips of the audio (C_in * L when packed; larger for one channel of a
-                        // multi-channel batch: wavjepa/extractors/audio_channel_feature_extractor.py:163-172 runs x[:, [c]])
+    long clip_stride;   // elements between consecutive clips of the audio (packed_clip_stride)
 };
 
-template <int TAPS>
-__device__ __forceinline__ void load_weights(float (&w)[4][TAPS], const bf16_t* __restrict__ wsrc, int c4) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int tp = 0; tp < TAPS; ++tp) w[j][tp] = bf2f(wsrc[(long)(c4 + j) * TAPS + tp]);
-}
-
-// audio chunk for output steps [t0, t0+TC): xs[ci][i] = audio[n][ci][t0*stride + i], i < span
-__device__ __forceinline__ int stage_audio(float* xs, const bf16_t* __restrict__ audio, const Geo& g, int n, int t0, int span_max) {
-    const int span = min(span_max, g.L - t0 * g.stride);
-    for (int ci = 0; ci < g.C_in; ++ci)
-        for (int i = threadIdx.x; i < span_max; i += NTH)
-            xs[ci * span_max + i] = i < span ? bf2f(audio[(long)n * g.clip_stride + (long)ci * g.L + (long)t0 * g.stride + i]) : 0.f;
-    return span;
-}
-
-template <int TAPS>
-__device__ __forceinline__ void tap_offsets(int (&off)[TAPS], const Geo& g, int span_max) {
-#pragma unroll
-    for (int tp = 0; tp < TAPS; ++tp) {
-        const int ci = tp / g.k, kk = tp - ci * g.k;
-        off[tp] = ci * span_max + kk;
-    }
-}
-
-template <int TAPS>
-__device__ __forceinline__ void conv4(float (&y)[4], float (&x)[TAPS], const float (&w)[4][TAPS], const float* xs,
-                                      const int (&off)[TAPS], int tl, int stride) {
-#pragma unroll
-    for (int tp = 0; tp < TAPS; ++tp) x[tp] = xs[off[tp] + tl * stride];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        float a = 0.f;
-#pragma unroll
-        for (int tp = 0; tp < TAPS; ++tp) a = fmaf(x[tp], w[j][tp], a);
-        y[j] = bf2f(f2bf(a));  // the conv output is a bf16 tensor in the reference's autocast flow
-    }
+// the samples of output steps [t0, t0 + chunk) of clip n into LDS: xs[ci][i] = audio[n][ci][t0 * stride + i], i < span
+template <int NT, class T>
+__device__ __forceinline__ void stage_steps(T* xs, const bf16_t* __restrict__ audio, const Geo& g, int n, int t0, int span) {
+    stage_chunk<NT>(xs, audio, (long)n * g.clip_stride, g.C_in, g.L, (long)t0 * g.stride, span);
 }
 
 // floats per partial record of the forward statistics pass
 __host__ __device__ constexpr long fwd_record(int C, int taps, int want_yx) { return want_yx ? 2L * C + (long)C * taps + taps : 2L * C; }
-
-// out[n][i] = sum over chunks (in chunk order) of part[n][chunk][i]; the record is split over up to three outputs
-// ([0, n0) -> o0, [n0, n0 + n1) -> o1, the rest -> o2, each [N][.]).  cnt_off != NULL: clip n only has
-// ceil((cnt_off[n+1] - cnt_off[n]) / per_chunk) chunks written (sparse backward), else `chunks`.
-__global__ __launch_bounds__(256) void conv0_fold_kernel(const float* __restrict__ part, int chunks, long rec, float* __restrict__ o0,
-                                                         long n0, float* __restrict__ o1, long n1, float* __restrict__ o2,
-                                                         const int32_t* __restrict__ cnt_off, int per_chunk) {
-    const int n = blockIdx.y;
-    int nch = chunks;
-    if (cnt_off) nch = min(chunks, (cnt_off[n + 1] - cnt_off[n] + per_chunk - 1) / per_chunk);
-    const float* src = part + (long)n * chunks * rec;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < rec; i += (long)gridDim.x * 256) {
-        float s = 0.f;
-        for (int ch = 0; ch < nch; ++ch) s += src[ch * rec + i];
-        if (i < n0) o0[n * n0 + i] = s;
-        else if (i < n0 + n1) o1[n * n1 + (i - n0)] = s;
-        else o2[n * (rec - n0 - n1) + (i - n0 - n1)] = s;
-    }
-}
 
 // ---- pass 1 (forward) on the matrix cores (C % 16 == 0): per-(n,c) sum and sum of squares of the bf16-rounded conv output;
 //      when want_yx also YX[n][c][q] = sum_t y_t x_{t,q} and X1[n][q] = sum_t x_{t,q} (what the backward needs of the dense
@@ -94,7 +40,7 @@ __global__ __launch_bounds__(256) void conv0_fold_kernel(const float* __restrict
 //      accumulates YX, so the VALU only rounds and sums.
 //      Every workgroup (one TCS-step chunk of one clip) STORES its partial record
 //          part[n][chunk][ 2C sums | C*TAPS yx | TAPS x1 ]
-//      and conv0_fold_kernel adds the chunks in chunk order: no float atomics, so the GroupNorm statistics -- and with them
+//      and ordered_fold_kernel adds the chunks in chunk order: no float atomics, so the GroupNorm statistics -- and with them
 //      every activation of the step -- are bit-reproducible from run to run.
 //   mfma(P, Q): lane (i, g) gets  sum_k Q[row i][k] P[row 4g+r][k], r < 4;  operand lane (i, g) holds row i, k = 8g .. 8g+7.
 //   conv : P = audio patches (rows = 16 time steps), Q = weights (rows = 16 channels)  -> lane: channel i, times 4g+r
@@ -127,7 +73,7 @@ inline int stats_chunks(int L_out, int TCS) { return (L_out + TCS - 1) / TCS; }
 // sees it.  The rounding errors of 6430 values average out: the means differ by <= ~1.5e-4 of the channel's standard deviation, rstd by a
 // few 1e-5 relative (tests/test_ops_gpu.py::test_conv0_fwd_bwd) -- 1/30 and 1/100 of one bf16 step of the activations they shift and
 // scale, and on the fp32 side of the reference's own values.
-// conv0_gram_kernel: one workgroup per (chunk of TCS time steps, clip) STORES part[n][chunk][TAPS | TAPS * TAPS]; conv0_fold_f64_kernel adds
+// conv0_gram_kernel: one workgroup per (chunk of TCS time steps, clip) STORES part[n][chunk][TAPS | TAPS * TAPS]; ordered_fold_kernel<double> adds
 // the chunks in order (no atomics: bit-reproducible).  conv0_stats_from_gram_kernel: one thread per (clip, channel).
 template <int TAPS>
 __global__ __launch_bounds__(256) void conv0_gram_kernel(const bf16_t* __restrict__ audio, double* __restrict__ part, Geo g, int span, int TCS) {
@@ -135,19 +81,14 @@ __global__ __launch_bounds__(256) void conv0_gram_kernel(const bf16_t* __restric
     constexpr int G = TAPS + TAPS * TAPS;
     __shared__ double red[4][G];
     const int n = blockIdx.y, t0 = blockIdx.x * TCS;
-    for (int ci = 0; ci < g.C_in; ++ci)
-        for (int i = threadIdx.x; i < span; i += 256) {
-            const long src = (long)t0 * g.stride + i;
-            xa[ci * span + i] = src < g.L ? audio[(long)n * g.clip_stride + (long)ci * g.L + src] : f2bf(0.f);
-        }
+    stage_steps<256>(xa, audio, g, n, t0, span);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tcount = min(TCS, g.L_out - t0);
     for (int p = lane; p < G; p += 64) {
         const bool one = p < TAPS;
         const int qa = one ? p : (p - TAPS) / TAPS, qb = one ? 0 : (p - TAPS) - qa * TAPS;
-        const int ca = qa / g.k, cb = qb / g.k;
-        const int offa = ca * span + (qa - ca * g.k), offb = cb * span + (qb - cb * g.k);
+        const int offa = tap_at(qa, g.k, span), offb = tap_at(qb, g.k, span);
         double acc = 0.0;
         for (int t = wave; t < tcount; t += 4) {
             const float a = bf2f(xa[offa + t * g.stride]);
@@ -159,17 +100,6 @@ __global__ __launch_bounds__(256) void conv0_gram_kernel(const bf16_t* __restric
     __syncthreads();
     double* o = part + ((long)n * gridDim.x + blockIdx.x) * G;
     for (int p = threadIdx.x; p < G; p += 256) o[p] = (red[0][p] + red[1][p]) + (red[2][p] + red[3][p]);
-}
-
-// out[n][i] = sum over chunks, in chunk order, of part[n][chunk][i]
-__global__ __launch_bounds__(256) void conv0_fold_f64_kernel(const double* __restrict__ part, int chunks, int rec, double* __restrict__ out) {
-    const int n = blockIdx.y;
-    const double* src = part + (long)n * chunks * rec;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < rec; i += gridDim.x * 256) {
-        double s = 0.0;
-        for (int ch = 0; ch < chunks; ++ch) s += src[(long)ch * rec + i];
-        out[(long)n * rec + i] = s;
-    }
 }
 
 template <int TAPS>
@@ -212,31 +142,17 @@ __global__ __launch_bounds__(256) void conv0_stats_mfma_kernel(const bf16_t* __r
     float* sums = part + ((long)n * gridDim.x + blockIdx.x) * rec;   // [C][2]
     float* yx = want_yx ? sums + 2L * g.C : nullptr;                 // [C][TAPS]
     float* x1 = want_yx ? yx + (long)g.C * TAPS : nullptr;           // [TAPS]
-    for (int ci = 0; ci < g.C_in; ++ci)
-        for (int i = threadIdx.x; i < span; i += 256) {
-            const long src = (long)t0 * g.stride + i;
-            xa[ci * span + i] = src < g.L ? audio[(long)n * g.clip_stride + (long)ci * g.L + src] : f2bf(0.f);
-        }
+    stage_steps<256>(xa, audio, g, n, t0, span);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, gq = lane >> 4;
     const int tcount = min(TCS, g.L_out - t0);
     const bf16_t zero = f2bf(0.f);
     int offc[8];
     bool okc[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int q = 8 * gq + j, ci = q / g.k;
-        okc[j] = q < TAPS;
-        offc[j] = ci * span + (q - ci * g.k);
-    }
+    tap_map<TAPS>(offc, okc, 8 * gq, 1, g.k, span);
     int offq[QT];
     bool okq[QT];
-#pragma unroll
-    for (int qt = 0; qt < QT; ++qt) {
-        const int q = 16 * qt + i, ci = q / g.k;
-        okq[qt] = q < TAPS;
-        offq[qt] = ci * span + (q - ci * g.k);
-    }
+    tap_map<TAPS>(offq, okq, i, 16, g.k, span);
     const int ntile = g.C / 16;
     for (int ctg = wave * 8; ctg < ntile; ctg += 32) {            // 8 channel tiles per wave per pass
         bf16x8 wf[8];
@@ -338,7 +254,7 @@ __global__ __launch_bounds__(NTH) void conv0_apply_kernel(const bf16_t* __restri
     extern __shared__ float xs[];
     const int n = blockIdx.y, t0 = blockIdx.x * TC;
     const int half = threadIdx.x >> 7, cl = threadIdx.x & 127;
-    stage_audio(xs, audio, g, n, t0, span_max);
+    stage_steps<NTH>(xs, audio, g, n, t0, span_max);
     __syncthreads();
     const int tmax = min(TC, g.P - t0);
     const float invL = 1.0f / (float)g.L_out;
@@ -346,14 +262,11 @@ __global__ __launch_bounds__(NTH) void conv0_apply_kernel(const bf16_t* __restri
         const int c4 = cb + cl * 4;
         if (c4 >= g.C) continue;
         float w[4][TAPS];
-        load_weights<TAPS>(w, wsrc, c4);
+        load_weights(w, wsrc, c4);
         float mu[4], rs[4], ga[4], be[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float s1 = sums[((long)n * g.C + c4 + j) * 2], s2 = sums[((long)n * g.C + c4 + j) * 2 + 1];
-            mu[j] = s1 * invL;
-            const float var = fmaxf(s2 * invL - mu[j] * mu[j], 0.f);
-            rs[j] = rsqrtf(var + eps);
+            gn_stats(sums[((long)n * g.C + c4 + j) * 2], sums[((long)n * g.C + c4 + j) * 2 + 1], invL, eps, mu[j], rs[j]);
             ga[j] = gamma[c4 + j];
             be[j] = beta[c4 + j];
             if (blockIdx.x == 0 && half == 0) {
@@ -362,13 +275,14 @@ __global__ __launch_bounds__(NTH) void conv0_apply_kernel(const bf16_t* __restri
             }
         }
         int off[TAPS];
-        tap_offsets<TAPS>(off, g, span_max);
+        tap_offsets(off, g.k, span_max);
         for (int tl = half; tl < tmax; tl += 2) {
             const int t = t0 + tl;
             bf16x4 o;
             if (t < g.L_out) {
                 float y[4], x[TAPS];
-                conv4<TAPS>(y, x, w, xs, off, tl, g.stride);
+                load_patch(x, xs + tl * g.stride, off);
+                conv_row(y, x, [&](int j, int q) { return w[j][q]; }, nullptr);
 #pragma unroll
                 for (int j = 0; j < 4; j += 2) {      // this pass is VALU-bound: erf-GELU on the packed fp32 pipe
                     f32x2 z, gl, unused;
@@ -407,11 +321,7 @@ __global__ __launch_bounds__(512, MINB == 2 ? 4 : 1) void conv0_apply_mfma_kerne
                                                                float eps) {
     extern __shared__ __attribute__((aligned(16))) bf16_t xa[];   // [C_in][span] samples of this chunk (0 past the clip)
     const int n = blockIdx.y, t0 = blockIdx.x * TCA;
-    for (int ci = 0; ci < g.C_in; ++ci)
-        for (int i = threadIdx.x; i < span; i += 512) {
-            const long src = (long)t0 * g.stride + i;
-            xa[ci * span + i] = src < g.L ? audio[(long)n * g.clip_stride + (long)ci * g.L + src] : f2bf(0.f);
-        }
+    stage_steps<512>(xa, audio, g, n, t0, span);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, gq = lane >> 4;
     const int tmax = min(TCA, g.P - t0);            // rows this workgroup writes (rows >= L_out are zero padding)
@@ -421,11 +331,7 @@ __global__ __launch_bounds__(512, MINB == 2 ? 4 : 1) void conv0_apply_mfma_kerne
     int offc[8];
     bool okc[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int q = 8 * gq + j, ci = q / g.k;
-        okc[j] = q < TAPS;
-        offc[j] = ci * span + (q - ci * g.k);
-    }
+    for (int j = 0; j < 8; ++j) offc[j] = tap_at<TAPS>(8 * gq + j, g.k, span, okc[j]);
     for (int cb = wave * 64; cb < g.C; cb += 512) {        // eight waves: 64 channels (four tiles) each
         bf16x8 wf[4];
         float ka[4][4], kb[4][4];
@@ -437,10 +343,8 @@ __global__ __launch_bounds__(512, MINB == 2 ? 4 : 1) void conv0_apply_mfma_kerne
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int c = cb + 32 * (u >> 1) + 8 * gq + 4 * (u & 1) + r;                // channel of this lane's output r of tile u
-                const float s1 = sums[((long)n * g.C + c) * 2], s2 = sums[((long)n * g.C + c) * 2 + 1];
-                const float mu = s1 * invL;
-                const float var = fmaxf(s2 * invL - mu * mu, 0.f);
-                const float rs = rsqrtf(var + eps);
+                float mu, rs;
+                gn_stats(sums[((long)n * g.C + c) * 2], sums[((long)n * g.C + c) * 2 + 1], invL, eps, mu, rs);
                 ka[u][r] = rs * gamma[c];
                 kb[u][r] = fmaf(-mu, ka[u][r], beta[c]);
                 if (blockIdx.x == 0 && i == 0) {
@@ -493,7 +397,7 @@ __global__ __launch_bounds__(512, MINB == 2 ? 4 : 1) void conv0_apply_mfma_kerne
 }
 
 // ---- backward, pass over the listed rows: A1 = sum dz, A2 = sum dz xh, S[q] = sum dz x_q  per (n, c) ------------------
-// Every workgroup = (chunk of BR listed rows, clip) STORES its partial part[n][chunk][C][2 + TAPS]; conv0_fold_kernel adds a
+// Every workgroup = (chunk of BR listed rows, clip) STORES its partial part[n][chunk][C][2 + TAPS]; ordered_fold_kernel adds a
 // clip's chunks in order (no float atomics).  rows == NULL: every row t < L_out of every clip.
 constexpr int BR = 256;
 template <int TAPS>
@@ -515,9 +419,8 @@ __global__ __launch_bounds__(NTH) void conv0_bwd_rows_kernel(const bf16_t* __res
     for (int j = threadIdx.x; j < jn; j += NTH) tl[j] = rows ? rows[first + j0 + j] - n * g.P : j0 + j;
     __syncthreads();
     for (int idx = threadIdx.x; idx < jn * TAPS; idx += NTH) {
-        const int j = idx / TAPS, tp = idx - j * TAPS;
-        const int ci = tp / g.k, kk = tp - ci * g.k;
-        xs[idx] = bf2f(audio[(long)n * g.clip_stride + (long)ci * g.L + (long)tl[j] * g.stride + kk]);
+        const int j = idx / TAPS;
+        xs[idx] = bf2f(audio[(long)n * g.clip_stride + (long)tl[j] * g.stride + tap_at(idx - j * TAPS, g.k, g.L)]);
     }
     __syncthreads();
     for (int cb = 0; cb < g.C; cb += 512) {
@@ -530,7 +433,7 @@ __global__ __launch_bounds__(NTH) void conv0_bwd_rows_kernel(const bf16_t* __res
             for (int tp = 0; tp < TAPS; ++tp) acc[j][tp] = 0.f;
         if (live) {
             float w[4][TAPS];
-            load_weights<TAPS>(w, wsrc, c4);
+            load_weights(w, wsrc, c4);
             float mu[4], rs[4], ga[4], be[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -552,17 +455,14 @@ __global__ __launch_bounds__(NTH) void conv0_bwd_rows_kernel(const bf16_t* __res
                 for (int u = 0; u < RB; ++u) {
                     const int jj = jj0 + 2 * u;
                     if (jj >= jn) break;
-                    float x[TAPS];
+                    float x[TAPS], y[4];
 #pragma unroll
-                    for (int tp = 0; tp < TAPS; ++tp) x[tp] = xs[jj * TAPS + tp];
+                    for (int tp = 0; tp < TAPS; ++tp) x[tp] = xs[jj * TAPS + tp];      // a gathered patch: its taps are contiguous
+                    conv_row(y, x, [&](int j, int q) { return w[j][q]; }, nullptr);
                     const bf16x4 d = dv[u];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        float a = 0.f;
-#pragma unroll
-                        for (int tp = 0; tp < TAPS; ++tp) a = fmaf(x[tp], w[j][tp], a);
-                        const float y = bf2f(f2bf(a));
-                        const float xh = (y - mu[j]) * rs[j];
+                        const float xh = (y[j] - mu[j]) * rs[j];
                         const float dz = bf2f(d[j]) * gelu_grad_f(xh * ga[j] + be[j]);
                         a1[j] += dz;
                         a2[j] = fmaf(dz, xh, a2[j]);
@@ -636,10 +536,17 @@ __global__ __launch_bounds__(256) void conv0_bwd_final_kernel(const float* __res
     }
 }
 
-inline Geo geo_of(int N, int C_in, int L, int C, int k, int stride, int L_out, int P, long clip_stride) {
-    Geo g; g.N = N; g.C_in = C_in; g.L = L; g.C = C; g.k = k; g.stride = stride; g.L_out = L_out; g.P = P;
-    g.clip_stride = clip_stride > 0 ? clip_stride : (long)C_in * L;
-    return g;
+template <class A>
+Geo geo_of(const A* a) {
+    return Geo{a->N, a->C_in, a->L, a->C, a->k, a->stride, a->L_out, a->P, packed_clip_stride(a->audio_clip_stride, a->C_in, a->L)};
+}
+
+// the MFMA apply pass at MINB workgroups per CU
+template <int TAPS, int MINB>
+void launch_apply_mfma(const wj_conv0_fwd_args* a, const Geo& g, const float* sums, hipStream_t s) {
+    const int span = (TCA - 1) * a->stride + a->k;
+    hipLaunchKernelGGL((conv0_apply_mfma_kernel<TAPS, MINB>), dim3((a->P + TCA - 1) / TCA, a->N), dim3(512), (size_t)a->C_in * span * sizeof(bf16_t),
+                       s, (const bf16_t*)a->audio, (const bf16_t*)a->w, a->gamma, a->beta, sums, (bf16_t*)a->act, a->mean, a->rstd, g, span, a->eps);
 }
 
 template <int TAPS>
@@ -662,27 +569,19 @@ void launch_fwd(const wj_conv0_fwd_args* a, const Geo& g, int span_max, hipStrea
         double* gfold = gpart + (long)a->N * chunks * G;          // [N][G]
         hipLaunchKernelGGL(conv0_gram_kernel<TAPS>, dim3(chunks, a->N), dim3(256), (size_t)a->C_in * span * sizeof(bf16_t), s,
                            (const bf16_t*)a->audio, gpart, g, span, TCS);
-        hipLaunchKernelGGL(conv0_fold_f64_kernel, dim3(1, a->N), dim3(256), 0, s, (const double*)gpart, chunks, (int)G, gfold);
+        fold_records(s, 1, a->N, (const double*)gpart, chunks, G, gfold, G);
         hipLaunchKernelGGL(conv0_stats_from_gram_kernel<TAPS>, dim3((a->C + 255) / 256, a->N), dim3(256), 0, s, (const double*)gfold,
                            (const bf16_t*)a->w, sums, a->yx, a->x1, g);
     } else {
         hipLaunchKernelGGL(conv0_stats_mfma_kernel<TAPS>, dim3(chunks, a->N), dim3(256), (size_t)a->C_in * span * sizeof(bf16_t), s,
                            (const bf16_t*)a->audio, (const bf16_t*)a->w, part, want_yx, g, span, TCS);
-        hipLaunchKernelGGL(conv0_fold_kernel, dim3((unsigned)((rec + 1023) / 1024), a->N), dim3(256), 0, s, (const float*)part, chunks, rec,
-                           sums, 2L * a->C, a->yx, (long)a->C * TAPS, a->x1, (const int32_t*)nullptr, 1);
+        fold_records(s, (unsigned)((rec + 1023) / 1024), a->N, (const float*)part, chunks, rec, sums, 2L * a->C, a->yx, (long)a->C * TAPS, a->x1);
     }
     static const int use_mfma = wj_lab_env_int("WJ_CONV0_APPLY_MFMA", 1);   // 0: the VALU form (A/B runs)
     if (use_mfma && a->C % 64 == 0 && TAPS <= 32) {
-        const int span_a = (TCA - 1) * a->stride + a->k;
         static const int occ = wj_lab_env_int("WJ_CONV0_APPLY_OCC", 1);      // 2: 128 VGPRs, two workgroups per CU -- measured 836 against 851 us alone and nothing on top of the re-chunked statistics pass (profiles/r05_conv0_variants.log): the pass is VALU-throughput-bound, not latency-bound
-        if (occ >= 2)
-            hipLaunchKernelGGL((conv0_apply_mfma_kernel<TAPS, 2>), dim3((a->P + TCA - 1) / TCA, a->N), dim3(512), (size_t)a->C_in * span_a * sizeof(bf16_t),
-                               s, (const bf16_t*)a->audio, (const bf16_t*)a->w, a->gamma, a->beta, (const float*)sums, (bf16_t*)a->act, a->mean,
-                               a->rstd, g, span_a, a->eps);
-        else
-            hipLaunchKernelGGL((conv0_apply_mfma_kernel<TAPS, 1>), dim3((a->P + TCA - 1) / TCA, a->N), dim3(512), (size_t)a->C_in * span_a * sizeof(bf16_t),
-                               s, (const bf16_t*)a->audio, (const bf16_t*)a->w, a->gamma, a->beta, (const float*)sums, (bf16_t*)a->act, a->mean,
-                               a->rstd, g, span_a, a->eps);
+        if (occ >= 2) launch_apply_mfma<TAPS, 2>(a, g, sums, s);
+        else launch_apply_mfma<TAPS, 1>(a, g, sums, s);
         return;
     }
     hipLaunchKernelGGL(conv0_apply_kernel<TAPS>, grid2, block, lds, s, (const bf16_t*)a->audio, (const bf16_t*)a->w,
@@ -707,8 +606,8 @@ void launch_bwd(const wj_conv0_bwd_args* a, const Geo& g, hipStream_t s) {
     dim3 grid(chunks, a->N), block(NTH);
     hipLaunchKernelGGL(conv0_bwd_rows_kernel<TAPS>, grid, block, lds, s, (const bf16_t*)a->audio, (const bf16_t*)a->w, a->gamma,
                        a->beta, a->mean, a->rstd, (const bf16_t*)a->dact, a->rows, a->row_off, part, g);
-    hipLaunchKernelGGL(conv0_fold_kernel, dim3((unsigned)((rec + 1023) / 1024), a->N), dim3(256), 0, s, (const float*)part, chunks, rec,
-                       folded, rec, (float*)nullptr, 0L, (float*)nullptr, a->rows ? a->row_off : (const int32_t*)nullptr, BR);
+    fold_records(s, (unsigned)((rec + 1023) / 1024), a->N, (const float*)part, chunks, rec, folded, rec, (float*)nullptr, 0L, (float*)nullptr,
+                 a->rows ? a->row_off : (const int32_t*)nullptr, BR);
     hipLaunchKernelGGL(conv0_bwd_final_kernel<TAPS>, dim3((a->C * TAPS + 31) / 32), dim3(256), 0, s, a->gamma, a->mean, a->rstd,
                        (const float*)folded, a->yx, a->x1, a->dw, a->dgamma, a->dbeta, g);
 }
@@ -733,15 +632,10 @@ extern "C" int wj_conv0_gn_gelu_fwd(const wj_conv0_fwd_args* a, void* stream) {
     if (a->N <= 0 || a->C <= 0 || (a->C & 15) || a->L_out <= 0 || a->P < a->L_out) return WJ_ERR_ARG;
     if ((a->L_out - 1) * a->stride + a->k > a->L) return WJ_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    const Geo g = geo_of(a->N, a->C_in, a->L, a->C, a->k, a->stride, a->L_out, a->P, a->audio_clip_stride);
+    const Geo g = geo_of(a);
     const int span_max = (TC - 1) * a->stride + a->k;
     if ((a->yx == nullptr) != (a->x1 == nullptr)) return WJ_ERR_ARG;
-    const int taps = a->C_in * a->k;
-    switch (taps) {
-        case 10: launch_fwd<10>(a, g, span_max, s); break;
-        case 20: launch_fwd<20>(a, g, span_max, s); break;
-        default: return WJ_ERR_UNSUPPORTED;
-    }
+    if (!taps_dispatch(a->C_in * a->k, [&](auto taps) { launch_fwd<decltype(taps)::value>(a, g, span_max, s); })) return WJ_ERR_UNSUPPORTED;
     WJ_CHECK_LAUNCH();
     return WJ_OK;
 }
@@ -754,13 +648,8 @@ extern "C" int wj_conv0_gn_gelu_bwd(const wj_conv0_bwd_args* a, void* stream) {
     if (a->N <= 0 || a->C <= 0 || (a->C & 3) || a->L_out <= 0 || a->P < a->L_out) return WJ_ERR_ARG;
     if (a->rows && (!a->row_off || a->max_rows < 0)) return WJ_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    const Geo g = geo_of(a->N, a->C_in, a->L, a->C, a->k, a->stride, a->L_out, a->P, a->audio_clip_stride);
-    const int taps = a->C_in * a->k;
-    switch (taps) {
-        case 10: launch_bwd<10>(a, g, s); break;
-        case 20: launch_bwd<20>(a, g, s); break;
-        default: return WJ_ERR_UNSUPPORTED;
-    }
+    const Geo g = geo_of(a);
+    if (!taps_dispatch(a->C_in * a->k, [&](auto taps) { launch_bwd<decltype(taps)::value>(a, g, s); })) return WJ_ERR_UNSUPPORTED;
     WJ_CHECK_LAUNCH();
     return WJ_OK;
 }

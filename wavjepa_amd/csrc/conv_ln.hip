@@ -8,9 +8,8 @@
 //                lane's 8 x taps weights live in registers.
 // Parameter gradients: every lane keeps its columns' sums in registers across its rows (a fixed row -> lane assignment), sub-rows are
 // folded by shuffles, waves through LDS in wave order, and each workgroup STORES one partial row; the partial rows are added in row order
-// by wj_colsum_f32_group (layers >= 1) or the two fold kernels below (layer 0).  No float atomics anywhere in this file.
-#include <type_traits>
-#include "common.h"
+// by wj_colsum_f32_group (layers >= 1) or ordered_fold_kernel and conv0_ln_final_kernel (layer 0).  No float atomics anywhere in this file.
+#include "conv_pieces.h"
 #include "../../include/wavjepa_hip.h"
 
 namespace {
@@ -213,30 +212,17 @@ void width_dispatch(int C, F&& f) {
 }
 
 // ---- layer 0 -----------------------------------------------------------------------------------------------------------------------
-// offsets (elements from the row's first sample) of the row's taps: q = ci * k + kk -> ci * L + kk
-template <int TAPS>
-__device__ __forceinline__ void tap_offsets(int (&off)[TAPS], int k, int L) {
-#pragma unroll
-    for (int q = 0; q < TAPS; ++q) {
-        const int ci = q / k;
-        off[q] = ci * L + (q - ci * k);
-    }
-}
-
 template <int LPR, int TAPS>
 __global__ __launch_bounds__(THREADS) void conv0_ln_fwd_kernel(wj_conv0_ln_fwd_args a, long clip_stride) {
     const RowLanes<LPR> L;
     constexpr int C = RowLanes<LPR>::C, RPW = RowLanes<LPR>::RPW;
     float w[8][TAPS], bi[8], gam[8], bet[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-#pragma unroll
-        for (int q = 0; q < TAPS; ++q) w[j][q] = bf2f(((const bf16_t*)a.w)[(long)(L.col + j) * TAPS + q]);
+    load_weights(w, (const bf16_t*)a.w, L.col);
     load8(a.bias ? a.bias + L.col : nullptr, bi);
     load8(a.gamma + L.col, gam);
     load8(a.beta + L.col, bet);
     int off[TAPS];
-    tap_offsets<TAPS>(off, a.k, a.L);
+    tap_offsets(off, a.k, a.L);
     const int total = a.N * a.P, stride = gridDim.x * NW * RPW;
     for (int r = (blockIdx.x * NW + L.wave) * RPW + L.sr; r < total; r += stride) {
         const int n = r / a.P, t = r - n * a.P;
@@ -251,15 +237,8 @@ __global__ __launch_bounds__(THREADS) void conv0_ln_fwd_kernel(wj_conv0_ln_fwd_a
         }
         const bf16_t* ap = (const bf16_t*)a.audio + (long)n * clip_stride + (long)t * a.stride;
         float x[TAPS], y[8], mean, rstd;
-#pragma unroll
-        for (int q = 0; q < TAPS; ++q) x[q] = bf2f(ap[off[q]]);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float acc = 0.f;
-#pragma unroll
-            for (int q = 0; q < TAPS; ++q) acc = fmaf(x[q], w[j][q], acc);
-            y[j] = bf2f(f2bf(acc + bi[j]));      // the conv output is a bf16 tensor in the autocast flow
-        }
+        load_patch(x, ap, off);
+        conv_row(y, x, [&](int j, int q) { return w[j][q]; }, bi);
         row_stats<LPR>(y, a.eps, mean, rstd);
         *dst = ln_gelu8(y, mean, rstd, gam, bet);
         if (L.li == 0) {
@@ -297,7 +276,7 @@ __global__ __launch_bounds__(THREADS) void conv0_ln_bwd_kernel(wj_conv0_ln_bwd_a
 #pragma unroll
         for (int q = 0; q < TAPS; ++q) dw[j][q] = 0.f;
     int off[TAPS];
-    tap_offsets<TAPS>(off, a.k, a.L);
+    tap_offsets(off, a.k, a.L);
     const int n = blockIdx.y;
     const int first = a.rows ? a.row_off[n] : 0;
     const int cnt = a.rows ? a.row_off[n + 1] - first : a.L_out;
@@ -309,16 +288,9 @@ __global__ __launch_bounds__(THREADS) void conv0_ln_bwd_kernel(wj_conv0_ln_bwd_a
         const long r = (long)n * a.P + t;
         const bf16_t* ap = (const bf16_t*)a.audio + (long)n * clip_stride + (long)t * a.stride;
         float x[TAPS], y[8], d[8], dx[8];
-#pragma unroll
-        for (int q = 0; q < TAPS; ++q) x[q] = bf2f(ap[off[q]]);
+        load_patch(x, ap, off);
         unpack8(*reinterpret_cast<const bf16x8*>((const bf16_t*)a.dact + r * C + L.col), d);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float acc = 0.f;
-#pragma unroll
-            for (int q = 0; q < TAPS; ++q) acc = fmaf(x[q], bf2f(w2[j][q / 2][q & 1]), acc);
-            y[j] = bf2f(f2bf(acc + bi[j]));
-        }
+        conv_row(y, x, [&](int j, int q) { return bf2f(w2[j][q / 2][q & 1]); }, bi);
         ln_gelu_bwd8<LPR>(y, d, a.mean[r], a.rstd[r], gam, bet, dx, dg, db);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -355,16 +327,6 @@ __global__ __launch_bounds__(THREADS) void conv0_ln_bwd_kernel(wj_conv0_ln_bwd_a
     for (int i = threadIdx.x; i < REC; i += THREADS) o[i] = racc[i];
 }
 
-// out[g][i] = sum over the group's `count` records, in record order, of part[g][r][i]
-__global__ __launch_bounds__(256) void conv0_ln_fold_kernel(const float* __restrict__ part, int count, int rec, float* __restrict__ out) {
-    const int g = blockIdx.y;
-    const float* src = part + (long)g * count * rec;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < rec; i += gridDim.x * 256) {
-        float s = 0.f;
-        for (int r = 0; r < count; ++r) s += src[(long)r * rec + i];
-        out[(long)g * rec + i] = s;
-    }
-}
 // gradient += sum over clips, in clip order, of folded[n][i]; one thread owns an element: a plain accumulate into the gradient buffers
 __global__ __launch_bounds__(256) void conv0_ln_final_kernel(const float* __restrict__ folded, int N, int C, int taps, float* __restrict__ dw,
                                                              float* __restrict__ dbias, float* __restrict__ dgamma, float* __restrict__ dbeta) {
@@ -389,12 +351,22 @@ void launch_conv0_bwd(const wj_conv0_ln_bwd_args* a, long clip_stride, hipStream
     float* folded = a->workspace;                         // [N][REC]
     float* part = a->workspace + (long)a->N * REC;        // [N][chunks][REC]
     hipLaunchKernelGGL((conv0_ln_bwd_kernel<LPR, TAPS>), dim3(chunks, a->N), dim3(THREADS), 0, s, *a, clip_stride, part);
-    hipLaunchKernelGGL(conv0_ln_fold_kernel, dim3((REC + 255) / 256, a->N), dim3(256), 0, s, (const float*)part, chunks, REC, folded);
+    fold_records(s, (REC + 255) / 256, a->N, (const float*)part, chunks, REC, folded, REC);
     hipLaunchKernelGGL(conv0_ln_final_kernel, dim3((REC + 255) / 256), dim3(256), 0, s, (const float*)folded, a->N, C, TAPS, a->dw, a->dbias,
                        a->dgamma, a->dbeta);
 }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// geometry of the two layer-0 entries (`rows16` = the [N * P][C] tensor the entry streams); args_ok = the entry's own argument rules
+template <class A>
+int layer0_check(const A* a, const void* rows16, bool args_ok = true) {
+    if (a->N <= 0 || a->C <= 0 || a->C_in <= 0 || a->k <= 0 || a->stride <= 0 || a->L_out <= 0 || a->P < a->L_out || !aligned16(rows16)) return WJ_ERR_ARG;
+    if ((long)(a->L_out - 1) * a->stride + a->k > a->L || (long)a->N * a->P >= (1L << 31)) return WJ_ERR_ARG;
+    if (a->audio_clip_stride != 0 && a->audio_clip_stride < (int64_t)a->C_in * a->L) return WJ_ERR_ARG;
+    if (!args_ok) return WJ_ERR_ARG;
+    return width_ok(a->C) && taps_ok(a->C_in * a->k) ? WJ_OK : WJ_ERR_UNSUPPORTED;
+}
 
 }  // namespace
 
@@ -410,11 +382,8 @@ extern "C" int wj_conv_ln_gelu_fwd(const wj_conv_ln_fwd_args* a, void* stream) {
     if (a->seg_rows < 0 || (a->seg_rows > 0 && (a->seg_valid <= 0 || a->seg_valid > a->seg_rows))) return WJ_ERR_ARG;
     if (!width_ok(a->C)) return WJ_ERR_UNSUPPORTED;
     WJ_CLEAR_STALE_ERROR();
-    const int per_wg = NW * (512 / a->C);
-    int grid = (a->M + per_wg - 1) / per_wg;
-    grid = grid > 8192 ? 8192 : grid;
     width_dispatch(a->C, [&](auto lpr) {
-        hipLaunchKernelGGL((conv_ln_fwd_kernel<decltype(lpr)::value>), dim3(grid), dim3(THREADS), 0, (hipStream_t)stream, *a);
+        hipLaunchKernelGGL((conv_ln_fwd_kernel<decltype(lpr)::value>), dim3(row_grid(a->M, NW * (512 / a->C))), dim3(THREADS), 0, (hipStream_t)stream, *a);
     });
     WJ_CHECK_LAUNCH();
     return WJ_OK;
@@ -456,20 +425,15 @@ extern "C" int wj_conv_ln_gelu_bwd(const wj_conv_ln_bwd_args* a, void* stream) {
 
 extern "C" int wj_conv0_ln_gelu_fwd(const wj_conv0_ln_fwd_args* a, void* stream) {
     if (!a || !a->audio || !a->w || !a->gamma || !a->beta || !a->act || !a->mean || !a->rstd) return WJ_ERR_ARG;
-    if (a->N <= 0 || a->C <= 0 || a->C_in <= 0 || a->k <= 0 || a->stride <= 0 || a->L_out <= 0 || a->P < a->L_out || !aligned16(a->act)) return WJ_ERR_ARG;
-    if ((long)(a->L_out - 1) * a->stride + a->k > a->L || (long)a->N * a->P >= (1L << 31)) return WJ_ERR_ARG;
-    if (a->audio_clip_stride != 0 && a->audio_clip_stride < (int64_t)a->C_in * a->L) return WJ_ERR_ARG;
-    const int taps = a->C_in * a->k;
-    if (!width_ok(a->C) || (taps != 10 && taps != 20)) return WJ_ERR_UNSUPPORTED;
+    if (const int bad = layer0_check(a, a->act)) return bad;
     WJ_CLEAR_STALE_ERROR();
-    const long clip_stride = a->audio_clip_stride > 0 ? a->audio_clip_stride : (long)a->C_in * a->L;
-    const int per_wg = NW * (512 / a->C);
-    long grid = ((long)a->N * a->P + per_wg - 1) / per_wg;
-    grid = grid > 8192 ? 8192 : grid;
+    const long clip_stride = packed_clip_stride(a->audio_clip_stride, a->C_in, a->L);
+    const unsigned grid = row_grid((long)a->N * a->P, NW * (512 / a->C));
     width_dispatch(a->C, [&](auto lpr) {
-        constexpr int LPR = decltype(lpr)::value;
-        if (taps == 10) hipLaunchKernelGGL((conv0_ln_fwd_kernel<LPR, 10>), dim3((unsigned)grid), dim3(THREADS), 0, (hipStream_t)stream, *a, clip_stride);
-        else hipLaunchKernelGGL((conv0_ln_fwd_kernel<LPR, 20>), dim3((unsigned)grid), dim3(THREADS), 0, (hipStream_t)stream, *a, clip_stride);
+        taps_dispatch(a->C_in * a->k, [&](auto taps) {
+            hipLaunchKernelGGL((conv0_ln_fwd_kernel<decltype(lpr)::value, decltype(taps)::value>), dim3(grid), dim3(THREADS), 0, (hipStream_t)stream, *a,
+                               clip_stride);
+        });
     });
     WJ_CHECK_LAUNCH();
     return WJ_OK;
@@ -479,20 +443,13 @@ extern "C" int wj_conv0_ln_gelu_bwd(const wj_conv0_ln_bwd_args* a, void* stream)
     if (!a || !a->audio || !a->w || !a->gamma || !a->beta || !a->mean || !a->rstd || !a->dact || !a->dw || !a->dgamma || !a->dbeta ||
         !a->workspace)
         return WJ_ERR_ARG;
-    if (a->N <= 0 || a->C <= 0 || a->C_in <= 0 || a->k <= 0 || a->stride <= 0 || a->L_out <= 0 || a->P < a->L_out || !aligned16(a->dact)) return WJ_ERR_ARG;
-    if ((long)(a->L_out - 1) * a->stride + a->k > a->L || (long)a->N * a->P >= (1L << 31)) return WJ_ERR_ARG;
-    if (a->audio_clip_stride != 0 && a->audio_clip_stride < (int64_t)a->C_in * a->L) return WJ_ERR_ARG;
-    if (a->rows && (!a->row_off || a->max_rows < 0)) return WJ_ERR_ARG;
-    if ((bool)a->bias != (bool)a->dbias) return WJ_ERR_ARG;
-    const int taps = a->C_in * a->k;
-    if (!width_ok(a->C) || (taps != 10 && taps != 20)) return WJ_ERR_UNSUPPORTED;
+    const bool lists_ok = !a->rows || (a->row_off && a->max_rows >= 0);
+    if (const int bad = layer0_check(a, a->dact, lists_ok && (bool)a->bias == (bool)a->dbias)) return bad;
     if (a->rows && a->max_rows == 0) return WJ_OK;        // no listed row in any clip: nothing to add
     WJ_CLEAR_STALE_ERROR();
-    const long clip_stride = a->audio_clip_stride > 0 ? a->audio_clip_stride : (long)a->C_in * a->L;
+    const long clip_stride = packed_clip_stride(a->audio_clip_stride, a->C_in, a->L);
     width_dispatch(a->C, [&](auto lpr) {
-        constexpr int LPR = decltype(lpr)::value;
-        if (taps == 10) launch_conv0_bwd<LPR, 10>(a, clip_stride, (hipStream_t)stream);
-        else launch_conv0_bwd<LPR, 20>(a, clip_stride, (hipStream_t)stream);
+        taps_dispatch(a->C_in * a->k, [&](auto taps) { launch_conv0_bwd<decltype(lpr)::value, decltype(taps)::value>(a, clip_stride, (hipStream_t)stream); });
     });
     WJ_CHECK_LAUNCH();
     return WJ_OK;
