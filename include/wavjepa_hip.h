@@ -786,9 +786,11 @@ typedef struct {
 int wj_grad_sumsq(const wj_sumsq_args*, void* stream);
 
 /* AdamW with fused global-norm clipping (torch.optim.AdamW as configured at jepa.py:215-228 + gradient_clip_val=5):
- *   c = min(1, max_norm / (sqrt(sumsq[0]) + 1e-6));  g = c * grad * grad_scale;
+ *   norm = sqrt(sumsq[0]) * grad_scale;  c = min(1, max_norm / (norm + 1e-6));  g = c * grad * grad_scale;
+ *   (clip_grad_norm_ applied to the SCALED gradient: sumsq is that of the unscaled buffer, and a caller that averages over ranks through
+ *   grad_scale clips the averaged gradient's norm; tests/test_optimizer_bounds_gpu.py, kind `scaled`, pins this)
  *   p *= 1 - lr*wd;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
- * Also refreshes the bf16 shadow copy of p when p_bf16 != NULL.  max_norm <= 0 disables clipping. */
+ * Also refreshes the bf16 shadow copy of p when p_bf16 != NULL.  max_norm <= 0 or sumsq == NULL disables clipping. */
 typedef struct {
     float* p;
     float* g;            /* read; with zero_grad also cleared */
