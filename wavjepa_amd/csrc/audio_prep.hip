@@ -19,8 +19,7 @@
 // LDS rows are padded to KC + 1
 // floats: lanes that differ in the phase (table) or in the frame (gathered window) hit different banks of ds_read_b32.
 // Every output is ONE fmaf chain over k ascending -- the order of wj_resample_fir, so the two agree bit for bit on the same input.
-#include "common.h"
-#include "../../include/wavjepa_hip.h"
+#include "stream_pieces.h"
 
 namespace {
 
@@ -197,7 +196,7 @@ __global__ __launch_bounds__(256) void prep_scale_kernel(prep_dims d, prep_chunk
     const long L_r = resampled_len(c.len[j], d.orig, d.nw);
     const float g = d.gains[c.first + j];
     float* y = d.out + (long)c.index[j] * d.out_len;
-    for (long o = (long)blockIdx.x * 256 + threadIdx.x; o < d.out_len; o += (long)gridDim.x * 256) y[o] = o < L_r ? y[o] * g : 0.f;
+    for_each_flat(d.out_len, [&](long o) { y[o] = o < L_r ? y[o] * g : 0.f; });
 }
 
 struct prep_plan {
@@ -251,7 +250,7 @@ int64_t wj_audio_prepare_ws_bytes(const wj_audio_prepare_args* a) {
 }
 
 extern "C" int wj_audio_prepare(const wj_audio_prepare_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a || !a->pcm || !a->offsets || !a->lengths || !a->clips || !a->out || !a->workspace) return WJ_ERR_ARG;
     if (a->pcm_kind != 2 && !a->bits) return WJ_ERR_ARG;
     const int rc = check_dims(a);
@@ -311,6 +310,5 @@ extern "C" int wj_audio_prepare(const wj_audio_prepare_args* a, void* stream) {
         hipLaunchKernelGGL(prep_gain_kernel, dim3(m), dim3(256), 0, st, d, c, pl.frame_block, pl.phase_tiles);
         hipLaunchKernelGGL(prep_scale_kernel, dim3((unsigned)((a->out_len + 1023) / 1024), m), dim3(256), 0, st, d, c);
     }
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }

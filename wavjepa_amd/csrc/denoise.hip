@@ -6,8 +6,7 @@
 //   * wj_mse_groups    -- loss = sum_g w[g] * mean((preds[g] - targets)^2) over G prediction sets against ONE target tensor
 //                         (denoiser.py:350-355: alpha * mse(clean) + (1 - alpha) * mse(generated)), plus d loss / d preds.
 // Both HBM-bound streaming kernels; reductions go through per-workgroup partials folded in a fixed order (bit-reproducible).
-#include "common.h"
-#include "../../include/wavjepa_hip.h"
+#include "stream_pieces.h"
 
 namespace {
 
@@ -54,10 +53,9 @@ __global__ __launch_bounds__(256) void mse_groups_partial_kernel(wj_mse_groups_a
         s = fmaf(d, d, s);
     }
     __shared__ float red[4];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    stage_wave_sum(s, red);
     __syncthreads();
-    if (threadIdx.x == 0) a.workspace[(long)g * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    if (threadIdx.x == 0) a.workspace[(long)g * gridDim.x + blockIdx.x] = fold4(red);
 }
 
 __global__ __launch_bounds__(64) void mse_groups_final_kernel(wj_mse_groups_args a, int nblocks) {
@@ -78,7 +76,7 @@ __global__ __launch_bounds__(256) void mse_groups_grad_kernel(wj_mse_groups_args
     const float c = 2.0f * a.w[g] / (float)a.n * (a.gscale ? a.gscale[0] : 1.0f);
     const float* p = a.preds + (long)g * a.n;
     float* d = a.dpreds + (long)g * a.n;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (long)gridDim.x * 256) d[i] = c * (p[i] - a.targets[i]);
+    for_each_flat(a.n, [&](long i) { d[i] = c * (p[i] - a.targets[i]); });
 }
 
 }  // namespace
@@ -86,7 +84,7 @@ __global__ __launch_bounds__(256) void mse_groups_grad_kernel(wj_mse_groups_args
 int64_t wj_mse_groups_ws_bytes(const wj_mse_groups_args* a) { return a->G > 0 ? (int64_t)a->G * MSE_BLOCKS * 4 : -1; }
 
 extern "C" int wj_resample_fir(const wj_resample_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a || !a->x || !a->y || !a->kernel) return WJ_ERR_ARG;
     if (a->B <= 0 || a->L_in <= 0 || a->L_out <= 0 || a->orig <= 0 || a->nw <= 0 || a->width < 0 || a->taps != 2 * a->width + a->orig)
         return WJ_ERR_ARG;
@@ -95,17 +93,15 @@ extern "C" int wj_resample_fir(const wj_resample_args* a, void* stream) {
     const long frames = (a->L_out + a->nw - 1) / a->nw;
     hipLaunchKernelGGL(resample_fir_kernel, dim3((unsigned)((frames + RS_THREADS - 1) / RS_THREADS), a->B), dim3(RS_THREADS), (size_t)lds,
                        (hipStream_t)stream, *a);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }
 
 extern "C" int wj_mse_groups(const wj_mse_groups_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a || !a->preds || !a->targets || !a->loss || !a->workspace || a->G <= 0 || a->G > 4 || a->n <= 0) return WJ_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(mse_groups_partial_kernel, dim3(MSE_BLOCKS, a->G), dim3(256), 0, st, *a);
     hipLaunchKernelGGL(mse_groups_final_kernel, dim3(1), dim3(64), 0, st, *a, MSE_BLOCKS);
     if (a->dpreds) hipLaunchKernelGGL(mse_groups_grad_kernel, dim3(2048, a->G), dim3(256), 0, st, *a);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }

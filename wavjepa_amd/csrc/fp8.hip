@@ -2,16 +2,13 @@
 // v_mfma_scale_f32_16x16x128_f8f6f4; see wj_gemm_mxfp8 in gemm.hip).  HBM-bound: 2 B read, 1 B + 1/32 B written per element.
 //   thread = 8 consecutive elements (16-B load, 8-B store); a 32-element block = 4 lanes (two shuffles for its max);
 //   a 128-element K tile = 16 lanes: their four scale bytes are packed into ONE dword scales[kt][row] by a lane of the group.
-#include "common.h"
-#include "../../include/wavjepa_hip.h"
+#include "stream_pieces.h"
 
 namespace {
 
 __global__ __launch_bounds__(256) void quantize_mxfp8_kernel(wj_quantize_fp8_args a) {
-    const int per_row = a.K / 8;                     // threads per row (a multiple of 16)
-    const long total = (long)a.M * per_row;
-    for (long t = blockIdx.x * 256L + threadIdx.x; t < total; t += (long)gridDim.x * 256) {     // uniform trip count per wave: total % 16 == 0, 64 | 256
-        const int row = (int)(t / per_row), c8 = (int)(t - (long)row * per_row);
+    // K / 8 threads per row (a multiple of 16); uniform trip count per wave: the total % 16 == 0, 64 | 256
+    for_each_row_col(a.M, a.K / 8, [&](int row, int c8) {
         const bf16x8 v = *reinterpret_cast<const bf16x8*>((const bf16_t*)a.x + (long)row * a.ldx + c8 * 8);
         float f[8], amax = 0.f;
 #pragma unroll
@@ -39,19 +36,15 @@ __global__ __launch_bounds__(256) void quantize_mxfp8_kernel(wj_quantize_fp8_arg
         const unsigned s0 = __shfl(sbyte, base + 0, 64), s1 = __shfl(sbyte, base + 4, 64), s2 = __shfl(sbyte, base + 8, 64),
                        s3 = __shfl(sbyte, base + 12, 64);
         if ((lane & 15) == 0) ((uint32_t*)a.scales)[(long)(c8 / 16) * a.ld_scale + row] = s0 | (s1 << 8) | (s2 << 16) | (s3 << 24);
-    }
+    });
 }
 
 }  // namespace
 
 extern "C" int wj_quantize_mxfp8(const wj_quantize_fp8_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a || !a->x || !a->q || !a->scales || a->M <= 0 || a->K <= 0 || (a->K % 128) || (a->ldx & 7) || (a->ldq & 7) || a->ld_scale < a->M)
         return WJ_ERR_ARG;
-    const long total = (long)a->M * (a->K / 8);
-    long grid = (total + 255) / 256;
-    if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(quantize_mxfp8_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, *a);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    hipLaunchKernelGGL(quantize_mxfp8_kernel, dim3(grid_for((long)a->M * (a->K / 8), 256)), dim3(256), 0, (hipStream_t)stream, *a);
+    return entry.launched();
 }

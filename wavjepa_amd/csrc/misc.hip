@@ -1,31 +1,20 @@
 // HBM-bound plumbing kernels of the WavJEPA step for gfx950: token gather/scatter, positions, conv weight layouts,
 // GELU backward, teacher targets (joint instance norm), masked MSE, EMA, AdamW (+ global-norm clip), casts and the
 // crop/normalise batch preparation.  All are vectorised (8-16 B per lane) streaming kernels or small reductions.
-#include "common.h"
-#include "../../include/wavjepa_hip.h"
+#include "stream_pieces.h"
 #ifdef WJ_LAB
 #include "../../include/wavjepa_hip_lab.h"
 #endif
 
 namespace {
 
-inline int grid_for(long n_items, int per_block, int cap = 8192) {
-    long g = (n_items + per_block - 1) / per_block;
-    if (g < 1) g = 1;
-    return (int)(g > cap ? cap : g);
-}
-
 // ------------------------------------------------------------------------------------------- GELU backward (bf16)
 __global__ __launch_bounds__(256) void gelu_bwd_kernel(const bf16_t* __restrict__ dpost, const bf16_t* __restrict__ pre,
                                                        bf16_t* __restrict__ dpre, long n8) {
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
-        const bf16x8 d = *reinterpret_cast<const bf16x8*>(dpost + i * 8);
-        const bf16x8 p = *reinterpret_cast<const bf16x8*>(pre + i * 8);
-        bf16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(d[e]) * gelu_grad_f(bf2f(p[e])));
-        *reinterpret_cast<bf16x8*>(dpre + i * 8) = o;
-    }
+    for_each_flat(n8, [&](long i) {
+        *reinterpret_cast<bf16x8*>(dpre + i * 8) =
+            gelu_bwd8(*reinterpret_cast<const bf16x8*>(dpost + i * 8), *reinterpret_cast<const bf16x8*>(pre + i * 8));
+    });
 }
 
 // listed rows only (sparse conv backward); the consumed dpost rows are zeroed on the way (clear_dpost) so that the buffer
@@ -33,75 +22,58 @@ __global__ __launch_bounds__(256) void gelu_bwd_kernel(const bf16_t* __restrict_
 __global__ __launch_bounds__(256) void gelu_bwd_rows_kernel(bf16_t* __restrict__ dpost, const bf16_t* __restrict__ pre,
                                                             bf16_t* __restrict__ dpre, const int32_t* __restrict__ rows,
                                                             int n_rows, int row8, int clear_dpost) {
-    const long n8 = (long)n_rows * row8;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
-        const int r = (int)(i / row8), c = (int)(i - (long)r * row8);
+    for_each_row_col(n_rows, row8, [&](int r, int c) {
         const long off = ((long)rows[r] * row8 + c) * 8;
-        const bf16x8 d = *reinterpret_cast<const bf16x8*>(dpost + off);
-        const bf16x8 p = *reinterpret_cast<const bf16x8*>(pre + off);
-        bf16x8 o, z;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { o[e] = f2bf(bf2f(d[e]) * gelu_grad_f(bf2f(p[e]))); z[e] = f2bf(0.f); }
-        *reinterpret_cast<bf16x8*>(dpre + off) = o;
-        if (clear_dpost) *reinterpret_cast<bf16x8*>(dpost + off) = z;
-    }
+        *reinterpret_cast<bf16x8*>(dpre + off) =
+            gelu_bwd8(*reinterpret_cast<const bf16x8*>(dpost + off), *reinterpret_cast<const bf16x8*>(pre + off));
+        if (clear_dpost) *reinterpret_cast<bf16x8*>(dpost + off) = bf16x8{};
+    });
 }
 
 __global__ __launch_bounds__(256) void zero_rows_kernel(char* __restrict__ buf, const int32_t* __restrict__ rows, int n_rows,
                                                         int row16) {
-    const long n = (long)n_rows * row16;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const int r = (int)(i / row16), c = (int)(i - (long)r * row16);
+    for_each_row_col(n_rows, row16, [&](int r, int c) {
         *reinterpret_cast<uint4*>(buf + ((long)rows[r] * row16 + c) * 16) = make_uint4(0, 0, 0, 0);
-    }
+    });
 }
 
 // ------------------------------------------------------------------------------------------- conv weight layouts
 __global__ __launch_bounds__(256) void conv_w_kernel(wj_conv_w_args a) {
     const int Co = a.C_out, Ci = a.C_in, k = a.k;
     if (a.mode == 0) {  // wp[o][kk*Ci + c] = w[o][c][kk]
-        const long n = (long)Co * Ci * k;
-        for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        for_each_flat((long)Co * Ci * k, [&](long i) {
             const int c = (int)(i % Ci);
             const int kk = (int)((i / Ci) % k);
             const int o = (int)(i / ((long)Ci * k));
             ((bf16_t*)a.dst)[i] = f2bf(((const float*)a.src)[((long)o * Ci + c) * k + kk]);
-        }
+        });
     } else if (a.mode == 1) {  // wd[v*Co + o][c] = w[o][c][rho + stride*(U-1-v)]
-        const long n = (long)a.U * Co * Ci;
-        for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        for_each_flat((long)a.U * Co * Ci, [&](long i) {
             const int c = (int)(i % Ci);
             const int o = (int)((i / Ci) % Co);
             const int v = (int)(i / ((long)Ci * Co));
             const int kk = a.rho + a.stride * (a.U - 1 - v);
             ((bf16_t*)a.dst)[i] = f2bf(((const float*)a.src)[((long)o * Ci + c) * k + kk]);
-        }
+        });
     } else {  // dw[o][c][kk] += dwp[o][kk*Ci + c]
-        const long n = (long)Co * Ci * k;
-        for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        for_each_flat((long)Co * Ci * k, [&](long i) {
             const int kk = (int)(i % k);
             const int c = (int)((i / k) % Ci);
             const int o = (int)(i / ((long)Ci * k));
             ((float*)a.dst)[i] += ((const float*)a.src)[(long)o * Ci * k + (long)kk * Ci + c];
-        }
+        });
     }
 }
 
 // ------------------------------------------------------------------------------------------- + positions
 __global__ __launch_bounds__(256) void add_pos_kernel(wj_add_pos_args a) {
-    const int D4 = a.D / 4;
-    const long n = (long)a.M * D4;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const int m = (int)(i / D4), c = (int)(i - (long)m * D4) * 4;
-        const bf16x4 x = *reinterpret_cast<const bf16x4*>((const bf16_t*)a.x + (long)m * a.D + c);
-        const f32x4 p = *reinterpret_cast<const f32x4*>(a.pos + (long)(m % a.T) * a.D + c);
-        f32x4 y;
-        bf16x4 yb;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { y[e] = bf2f(x[e]) + p[e]; yb[e] = f2bf(y[e]); }
+    for_each_row_col(a.M, a.D / 4, [&](int m, int c4) {
+        const int c = c4 * 4;
+        const f32x4 y = to_f32x4(*reinterpret_cast<const bf16x4*>((const bf16_t*)a.x + (long)m * a.D + c)) +
+                        *reinterpret_cast<const f32x4*>(a.pos + (long)(m % a.T) * a.D + c);
         if (a.y_f32) *reinterpret_cast<f32x4*>(a.y_f32 + (long)m * a.D + c) = y;
-        if (a.y_bf16) *reinterpret_cast<bf16x4*>((bf16_t*)a.y_bf16 + (long)m * a.D + c) = yb;
-    }
+        if (a.y_bf16) *reinterpret_cast<bf16x4*>((bf16_t*)a.y_bf16 + (long)m * a.D + c) = to_bf16x4(y);
+    });
 }
 
 // ------------------------------------------------------------------------------------------- mask gather (bit-exact copy)
@@ -124,19 +96,9 @@ __global__ __launch_bounds__(256) void scatter_fill_kernel(wj_scatter_fill_args 
         const int b = m / a.T, t = m - b * a.T;
         const int src = a.inv[m];
         for (int c = lane * 4; c < D; c += 256) {
-            f32x4 tok;
-            if (src >= 0) {
-                const bf16x4 v = *reinterpret_cast<const bf16x4*>((const bf16_t*)a.ctx_feats + (long)src * D + c);
-                tok = f32x4{bf2f(v[0]), bf2f(v[1]), bf2f(v[2]), bf2f(v[3])};
-            } else {
-                const f32x4 mt = *reinterpret_cast<const f32x4*>(a.mask_token + c);
-                // mask_token.repeat(...).type_as(bf16 features): the token is rounded to bf16 first
-                tok = f32x4{bf2f(f2bf(mt[0])), bf2f(f2bf(mt[1])), bf2f(f2bf(mt[2])), bf2f(f2bf(mt[3]))};
-            }
-            const f32x4 y = tok + *reinterpret_cast<const f32x4*>(a.pos + (long)t * D + c);
+            f32x4 y;
             bf16x4 yb;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) yb[e] = f2bf(y[e]);
+            fill_token(a, src, t, c, y, yb);
             for (int g = 0; g < a.G; ++g) {
                 const long orow = ((long)b * a.G + g) * a.T + t;
                 if (a.out_f32) *reinterpret_cast<f32x4*>(a.out_f32 + orow * D + c) = y;
@@ -155,18 +117,9 @@ __global__ __launch_bounds__(256) void scatter_fill_rows_kernel(wj_scatter_fill_
         const int bg = dense / a.T, t = dense - bg * a.T, b = bg / a.G;
         const int src = a.inv[b * a.T + t];
         for (int c = lane * 4; c < D; c += 256) {
-            f32x4 tok;
-            if (src >= 0) {
-                const bf16x4 v = *reinterpret_cast<const bf16x4*>((const bf16_t*)a.ctx_feats + (long)src * D + c);
-                tok = f32x4{bf2f(v[0]), bf2f(v[1]), bf2f(v[2]), bf2f(v[3])};
-            } else {
-                const f32x4 mt = *reinterpret_cast<const f32x4*>(a.mask_token + c);
-                tok = f32x4{bf2f(f2bf(mt[0])), bf2f(f2bf(mt[1])), bf2f(f2bf(mt[2])), bf2f(f2bf(mt[3]))};
-            }
-            const f32x4 y = tok + *reinterpret_cast<const f32x4*>(a.pos + (long)t * D + c);
+            f32x4 y;
             bf16x4 yb;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) yb[e] = f2bf(y[e]);
+            fill_token(a, src, t, c, y, yb);
             if (a.out_f32) *reinterpret_cast<f32x4*>(a.out_f32 + (long)r * D + c) = y;
             if (a.out_bf16) *reinterpret_cast<bf16x4*>((bf16_t*)a.out_bf16 + (long)r * D + c) = yb;
         }
@@ -242,14 +195,8 @@ __global__ __launch_bounds__(256) void scatter_fill_bwd_kernel(wj_scatter_fill_b
         for (int j = 0; j < JMAX; ++j) {
             const int c = lane * 4 + 256 * j;
             if (c < D) {
-                if (dst >= 0) {
-                    bf16x4 o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = f2bf(s[j][e]);
-                    *reinterpret_cast<bf16x4*>((bf16_t*)a.d_ctx_feats + (long)dst * D + c) = o;
-                } else {
-                    mt[j] += s[j];
-                }
+                if (dst >= 0) *reinterpret_cast<bf16x4*>((bf16_t*)a.d_ctx_feats + (long)dst * D + c) = to_bf16x4(s[j]);
+                else mt[j] += s[j];
             }
         }
     }
@@ -261,7 +208,7 @@ __global__ __launch_bounds__(256) void scatter_fill_bwd_kernel(wj_scatter_fill_b
     }
     __syncthreads();
     for (int c = threadIdx.x; c < D; c += 256) {
-        const float v = (macc_dyn[c] + macc_dyn[D + c]) + (macc_dyn[2 * D + c] + macc_dyn[3 * D + c]);
+        const float v = fold4(macc_dyn + c, D);
         if (a.partials) a.partials[(long)blockIdx.x * D + c] = v;
         else atomicAdd(a.d_mask_token + c, v);
     }
@@ -269,57 +216,31 @@ __global__ __launch_bounds__(256) void scatter_fill_bwd_kernel(wj_scatter_fill_b
 
 // dst[m] = inv[m] >= 0 ? src[inv[m]] : 0     (gradient of the mask gather, jepa.py:399; inv == NULL: identity)
 __global__ __launch_bounds__(256) void unmask_rows_kernel(wj_unmask_rows_args a) {
-    const int D4 = a.D / 4;
-    const long n = (long)a.M * D4;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const int m = (int)(i / D4), c = (int)(i - (long)m * D4) * 4;
+    for_each_row_col(a.M, a.D / 4, [&](int m, int c4) {
+        const int c = c4 * 4;
         const int src = a.inv ? a.inv[m] : m;
         f32x4 y = f32x4{0.f, 0.f, 0.f, 0.f};
         if (src >= 0) {
-            if (a.src_is_f32) {
-                y = *reinterpret_cast<const f32x4*>((const float*)a.src + (long)src * a.D + c);
-            } else {
-                const bf16x4 v = *reinterpret_cast<const bf16x4*>((const bf16_t*)a.src + (long)src * a.D + c);
-                y = f32x4{bf2f(v[0]), bf2f(v[1]), bf2f(v[2]), bf2f(v[3])};
-            }
+            if (a.src_is_f32) y = *reinterpret_cast<const f32x4*>((const float*)a.src + (long)src * a.D + c);
+            else y = to_f32x4(*reinterpret_cast<const bf16x4*>((const bf16_t*)a.src + (long)src * a.D + c));
         }
-        if (a.dst_is_bf16) {
-            bf16x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = f2bf(y[e]);
-            *reinterpret_cast<bf16x4*>((bf16_t*)a.dst + (long)m * a.D + c) = o;
-        } else {
-            *reinterpret_cast<f32x4*>((float*)a.dst + (long)m * a.D + c) = y;
-        }
-    }
+        if (a.dst_is_bf16) *reinterpret_cast<bf16x4*>((bf16_t*)a.dst + (long)m * a.D + c) = to_bf16x4(y);
+        else *reinterpret_cast<f32x4*>((float*)a.dst + (long)m * a.D + c) = y;
+    });
 }
 
 // ------------------------------------------------------------------------------------------- teacher targets
 __global__ __launch_bounds__(1024) void instnorm_kernel(wj_instnorm_args a) {
     __shared__ float red[16];
     const long base = (long)blockIdx.x * a.TD;
-    const float* x = a.x + base;
     const int n4 = a.TD / 4;
-    float s = 0.f;
-    for (int i = threadIdx.x; i < n4; i += 1024) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x + i * 4);
-        s += v[0] + v[1] + v[2] + v[3];
-    }
-    const float mean = block_sum(s, red) / (float)a.TD;
-    float q = 0.f;
-    for (int i = threadIdx.x; i < n4; i += 1024) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x + i * 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { const float d = v[e] - mean; q += d * d; }
-    }
-    const float var = block_sum(q, red) / (float)a.TD;
+    const auto x = [&](int i) { return *reinterpret_cast<const f32x4*>(a.x + base + i * 4); };
+    float mean;
+    const float var = mean_sqdev(n4, (float)a.TD, x, red, mean) / (float)a.TD;
     const float k = rsqrtf(var + a.eps) * a.scale;
     float* t = a.targets + base;
     for (int i = threadIdx.x; i < n4; i += 1024) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x + i * 4);
-        f32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (v[e] - mean) * k;
+        f32x4 o = (x(i) - mean) * k;
         if (a.accumulate) o += *reinterpret_cast<const f32x4*>(t + i * 4);
         *reinterpret_cast<f32x4*>(t + i * 4) = o;
     }
@@ -450,9 +371,7 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(wj_loss_args a) {
 
 __global__ __launch_bounds__(1024) void mse_final_kernel(float* __restrict__ ws, float* __restrict__ loss, long R) {
     __shared__ float red[16];
-    float s = 0.f;
-    for (long i = threadIdx.x; i < R; i += 1024) s += ws[2 + i];
-    s = block_sum(s, red);
+    const float s = fold_partials(ws + 2, R, red);
     if (threadIdx.x == 0) {
         loss[0] = s / (ws[1] + 1e-8f);
         loss[1] = ws[1];
@@ -463,37 +382,30 @@ __global__ __launch_bounds__(1024) void mse_final_kernel(float* __restrict__ ws,
 __global__ __launch_bounds__(256) void ema_kernel(wj_ema_args a) {
     const long n4 = a.n / 4;
     const float r = a.r, q = 1.0f - a.r;
+    // (the plain loop, not for_each_flat: inside the walker's lambda the compiler contracts t * r + q * s around the other product -- other bits)
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         const f32x4 s = *reinterpret_cast<const f32x4*>(a.student + i * 4);
         f32x4 t = *reinterpret_cast<const f32x4*>(a.teacher + i * 4);
 #pragma unroll
         for (int e = 0; e < 4; ++e) t[e] = t[e] * r + q * s[e];
         *reinterpret_cast<f32x4*>(a.teacher + i * 4) = t;
-        if (a.teacher_bf16) {
-            bf16x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = f2bf(t[e]);
-            *reinterpret_cast<bf16x4*>((bf16_t*)a.teacher_bf16 + i * 4) = o;
-        }
+        if (a.teacher_bf16) *reinterpret_cast<bf16x4*>((bf16_t*)a.teacher_bf16 + i * 4) = to_bf16x4(t);
     }
 }
 
 __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ g, float* __restrict__ ws, long n) {
     __shared__ float red[16];
-    const long n4 = n / 4;
     float s = 0.f;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    for_each_flat(n / 4, [&](long i) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(g + i * 4);
         s += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
-    }
+    });
     s = block_sum(s, red);
     if (threadIdx.x == 0) ws[blockIdx.x] = s;
 }
 __global__ __launch_bounds__(1024) void sumsq_final_kernel(const float* __restrict__ ws, float* __restrict__ out, int n, int accumulate) {
     __shared__ float red[16];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < n; i += 1024) s += ws[i];
-    s = block_sum(s, red);
+    const float s = fold_partials(ws, n, red);
     if (threadIdx.x == 0) out[0] = accumulate ? out[0] + s : s;
 }
 
@@ -507,6 +419,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(wj_adamw_args a) {
     const float decay = 1.0f - a.lr * a.weight_decay;
     const float step = a.lr / a.bc1;
     const float rbc2 = rsqrtf(a.bc2);
+    // (the plain loop, as in ema_kernel: the moment updates are sums of two products)
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         f32x4 p = *reinterpret_cast<const f32x4*>(a.p + i * 4);
         const f32x4 g = *reinterpret_cast<const f32x4*>(a.g + i * 4);
@@ -524,25 +437,14 @@ __global__ __launch_bounds__(256) void adamw_kernel(wj_adamw_args a) {
         *reinterpret_cast<f32x4*>(a.p + i * 4) = p;
         *reinterpret_cast<f32x4*>(a.m + i * 4) = m;
         *reinterpret_cast<f32x4*>(a.v + i * 4) = v;
-        if (a.p_bf16) {
-            bf16x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = f2bf(p[e]);
-            *reinterpret_cast<bf16x4*>((bf16_t*)a.p_bf16 + i * 4) = o;
-        }
+        if (a.p_bf16) *reinterpret_cast<bf16x4*>((bf16_t*)a.p_bf16 + i * 4) = to_bf16x4(p);
     }
 }
 
 __global__ __launch_bounds__(256) void cast_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, long n) {
     const long n4 = n / 4;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        const f32x4 s = *reinterpret_cast<const f32x4*>(src + i * 4);
-        bf16x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = f2bf(s[e]);
-        *reinterpret_cast<bf16x4*>(dst + i * 4) = o;
-    }
-    for (long i = n4 * 4 + blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) dst[i] = f2bf(src[i]);
+    for_each_flat(n4, [&](long i) { *reinterpret_cast<bf16x4*>(dst + i * 4) = to_bf16x4(*reinterpret_cast<const f32x4*>(src + i * 4)); });
+    for_each_flat(n - n4 * 4, [&](long i) { dst[n4 * 4 + i] = f2bf(src[n4 * 4 + i]); });      // the 1..3 elements behind the last whole group
 }
 
 // ------------------------------------------------------------------------------------------- batched bf16 transposes (W^T shadows)
@@ -589,26 +491,16 @@ __global__ __launch_bounds__(1024) void crop_kernel(wj_crop_args a) {
     const int start = a.starts[bs];
     const long n = (long)a.C * a.length;
     const float* src = a.src + (long)b * a.C * a.L_full;
-    float s = 0.f;
-    for (long i = threadIdx.x; i < n; i += 1024) {
+    const auto x = [&](long i) {       // element i of the crop: channel c, sample start + l
         const int c = (int)(i / a.length), l = (int)(i - (long)c * a.length);
-        s += src[(long)c * a.L_full + start + l];
-    }
-    const float mean = block_sum(s, red) / (float)n;
-    float q = 0.f;
-    for (long i = threadIdx.x; i < n; i += 1024) {
-        const int c = (int)(i / a.length), l = (int)(i - (long)c * a.length);
-        const float d = src[(long)c * a.L_full + start + l] - mean;
-        q += d * d;
-    }
-    const float stdv = sqrtf(block_sum(q, red) / (float)(n - 1));
+        return src[(long)c * a.L_full + start + l];
+    };
+    float mean;
+    const float stdv = sqrtf(mean_sqdev(n, (float)n, x, red, mean) / (float)(n - 1));
     const float inv = 1.0f / (stdv + 1e-5f);
     const int orow = a.perm_inv ? a.perm_inv[bs] : bs;
     bf16_t* out = (bf16_t*)a.out + (long)orow * n;
-    for (long i = threadIdx.x; i < n; i += 1024) {
-        const int c = (int)(i / a.length), l = (int)(i - (long)c * a.length);
-        out[i] = f2bf((src[(long)c * a.L_full + start + l] - mean) * inv);
-    }
+    for (long i = threadIdx.x; i < n; i += 1024) out[i] = f2bf((x(i) - mean) * inv);
 }
 
 }  // namespace
@@ -616,21 +508,19 @@ __global__ __launch_bounds__(1024) void crop_kernel(wj_crop_args a) {
 #define STREAM ((hipStream_t)stream)
 
 extern "C" int wj_gelu_bwd_bf16(const wj_gelu_bwd_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (a && a->rows) {
         if (!a->dpost || !a->pre || !a->dpre || a->n_rows < 0 || a->row_elems <= 0 || (a->row_elems & 7)) return WJ_ERR_ARG;
         if (a->n_rows == 0) return WJ_OK;
         hipLaunchKernelGGL(gelu_bwd_rows_kernel, dim3(grid_for((long)a->n_rows * (a->row_elems / 8), 256)), dim3(256), 0, STREAM,
                            (bf16_t*)a->dpost, (const bf16_t*)a->pre, (bf16_t*)a->dpre, a->rows, a->n_rows, a->row_elems / 8,
                            a->clear_dpost);
-        WJ_CHECK_LAUNCH();
-        return WJ_OK;
+        return entry.launched();
     }
     if (!a || !a->dpost || !a->pre || !a->dpre || a->n <= 0 || (a->n & 7)) return WJ_ERR_ARG;
     hipLaunchKernelGGL(gelu_bwd_kernel, dim3(grid_for(a->n / 8, 256)), dim3(256), 0, STREAM, (const bf16_t*)a->dpost,
                        (const bf16_t*)a->pre, (bf16_t*)a->dpre, (long)(a->n / 8));
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }
 
 __global__ void spin_kernel(long ticks) {
@@ -639,11 +529,10 @@ __global__ void spin_kernel(long ticks) {
 }
 
 extern "C" int wj_spin(const wj_spin_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a || a->ticks < 0 || a->ticks > (1LL << 32)) return WJ_ERR_ARG;
     hipLaunchKernelGGL(spin_kernel, dim3(1), dim3(64), 0, STREAM, (long)a->ticks);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }
 
 #ifdef WJ_LAB
@@ -681,47 +570,43 @@ __global__ __launch_bounds__(512) void collective_footprint_kernel(cf_u32x4* __r
 }
 
 extern "C" int wj_collective_footprint(const wj_collective_footprint_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a || !a->buf || a->bytes <= 0 || (a->bytes & 15) || ((uintptr_t)a->buf & 15) || a->workgroups < 1 || a->workgroups > 256 ||
         a->passes < 1 || a->passes > 8 || a->min_ticks < 0)
         return WJ_ERR_ARG;
     hipLaunchKernelGGL(collective_footprint_kernel, dim3(a->workgroups), dim3(512), 0, STREAM, (cf_u32x4*)a->buf, (long)(a->bytes / 16),
                        (long)a->min_ticks, a->passes);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }
 #endif
 
 extern "C" int wj_zero_rows(const wj_zero_rows_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a || !a->buf || !a->rows || a->n_rows < 0 || a->row_bytes <= 0 || (a->row_bytes & 15)) return WJ_ERR_ARG;
     if (a->n_rows == 0) return WJ_OK;
     hipLaunchKernelGGL(zero_rows_kernel, dim3(grid_for((long)a->n_rows * (a->row_bytes / 16), 256)), dim3(256), 0, STREAM,
                        (char*)a->buf, a->rows, a->n_rows, a->row_bytes / 16);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }
 
 extern "C" int wj_conv_weight_layout(const wj_conv_w_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a || !a->src || !a->dst || a->C_out <= 0 || a->C_in <= 0 || a->k <= 0 || a->mode < 0 || a->mode > 2) return WJ_ERR_ARG;
     if (a->mode == 1 && (a->U <= 0 || a->rho < 0 || a->rho + a->stride * (a->U - 1) >= a->k)) return WJ_ERR_ARG;
     const long n = a->mode == 1 ? (long)a->U * a->C_out * a->C_in : (long)a->C_out * a->C_in * a->k;
     hipLaunchKernelGGL(conv_w_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, STREAM, *a);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }
 
 extern "C" int wj_add_pos(const wj_add_pos_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a || !a->x || !a->pos || a->M <= 0 || a->T <= 0 || a->D <= 0 || (a->D & 3)) return WJ_ERR_ARG;
     hipLaunchKernelGGL(add_pos_kernel, dim3(grid_for((long)a->M * a->D / 4, 256)), dim3(256), 0, STREAM, *a);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }
 
 extern "C" int wj_mask_gather_rows(const wj_gather_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a || !a->x || !a->idx || !a->out || a->n_rows < 0 || a->D <= 0) return WJ_ERR_ARG;
     if (a->elem_bytes != 2 && a->elem_bytes != 4) return WJ_ERR_ARG;
     const int row_bytes = a->D * a->elem_bytes;
@@ -729,12 +614,11 @@ extern "C" int wj_mask_gather_rows(const wj_gather_args* a, void* stream) {
     if (a->n_rows == 0) return WJ_OK;
     hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for(a->n_rows, 1, 16384)), dim3(256), 0, STREAM, (const char*)a->x, a->idx,
                        (char*)a->out, a->n_rows, row_bytes);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }
 
 extern "C" int wj_mask_scatter_fill_pos(const wj_scatter_fill_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a || !a->ctx_feats || !a->inv || !a->mask_token || !a->pos || a->B <= 0 || a->T <= 0 || a->D <= 0 || (a->D & 3) ||
         a->G <= 0)
         return WJ_ERR_ARG;
@@ -742,12 +626,10 @@ extern "C" int wj_mask_scatter_fill_pos(const wj_scatter_fill_args* a, void* str
         if (a->n_rows < 0) return WJ_ERR_ARG;
         if (a->n_rows == 0) return WJ_OK;
         hipLaunchKernelGGL(scatter_fill_rows_kernel, dim3(grid_for((long)a->n_rows, 4)), dim3(256), 0, STREAM, *a);
-        WJ_CHECK_LAUNCH();
-        return WJ_OK;
+        return entry.launched();
     }
     hipLaunchKernelGGL(scatter_fill_kernel, dim3(grid_for((long)a->B * a->T, 4)), dim3(256), 0, STREAM, *a);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }
 
 extern "C" int wj_scatter_fill_bwd_partial_rows(int B, int T) { return (int)(((long)B * T + SFB_ROWS - 1) / SFB_ROWS); }
@@ -755,48 +637,42 @@ extern "C" int wj_scatter_fill_bwd_partial_rows(int B, int T) { return (int)(((l
 int64_t wj_scatter_fill_bwd_ws_bytes(const wj_scatter_fill_bwd_args* a) { return (int64_t)wj_scatter_fill_bwd_partial_rows(a->B, a->T) * a->D * 4; }
 
 extern "C" int wj_mask_scatter_fill_pos_bwd(const wj_scatter_fill_bwd_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a || !a->d_in || !a->inv || !a->d_ctx_feats || a->B <= 0 || a->T <= 0 || a->D <= 0 || (a->D & 3) || a->D > 1024 ||
         a->G <= 0 || a->G > 15)              // (a wave's 4 rows x (G + 1) indices are fetched by one load per lane)
         return WJ_ERR_ARG;
     const int grid = wj_scatter_fill_bwd_partial_rows(a->B, a->T);
     if (a->D <= 512) hipLaunchKernelGGL(scatter_fill_bwd_kernel<2>, dim3(grid), dim3(256), (size_t)4 * a->D * sizeof(float), STREAM, *a);
     else hipLaunchKernelGGL(scatter_fill_bwd_kernel<4>, dim3(grid), dim3(256), (size_t)4 * a->D * sizeof(float), STREAM, *a);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }
 
 extern "C" int wj_unmask_rows_f32(const wj_unmask_rows_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a || !a->src || !a->dst || a->M <= 0 || a->D <= 0 || (a->D & 3)) return WJ_ERR_ARG;
     hipLaunchKernelGGL(unmask_rows_kernel, dim3(grid_for((long)a->M * a->D / 4, 256)), dim3(256), 0, STREAM, *a);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }
 
 extern "C" int wj_instnorm_accumulate(const wj_instnorm_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a || !a->x || !a->targets || a->B <= 0 || a->TD <= 0 || (a->TD & 3)) return WJ_ERR_ARG;
     hipLaunchKernelGGL(instnorm_kernel, dim3(a->B), dim3(1024), 0, STREAM, *a);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }
 
 extern "C" int wj_instnorm_mean(const wj_instnorm_mean_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a || !a->stats || !a->targets || a->B <= 0 || a->TD <= 0 || (a->TD & 3) || a->K < 1 || a->K > 8) return WJ_ERR_ARG;
     const float* xs[8] = {a->x0, a->x1, a->x2, a->x3, a->x4, a->x5, a->x6, a->x7};
     for (int l = 0; l < a->K; ++l)
         if (!xs[l]) return WJ_ERR_ARG;
-    int gx = (a->TD / 4 + 255) / 256;
-    if (gx > 32) gx = 32;
-    hipLaunchKernelGGL(instnorm_mean_kernel, dim3(gx, a->B), dim3(256), 0, STREAM, *a);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    hipLaunchKernelGGL(instnorm_mean_kernel, dim3(grid_for(a->TD / 4, 256, 32), a->B), dim3(256), 0, STREAM, *a);
+    return entry.launched();
 }
 
 // count -> rows<kind> -> final: one launch sequence for wj_masked_mse (kind MSE) and wj_masked_loss; validation precedes every launch
-static int masked_loss_launch(const wj_loss_args* a, void* stream) {
+static int masked_loss_launch(const wj_loss_args* a, void* stream, const CheckedEntry& entry) {
     if (!a->preds || !a->targets || !a->tgt || !a->loss || !a->workspace) return WJ_ERR_ARG;
     if (a->B <= 0 || a->G <= 0 || a->T <= 0 || a->D <= 0 || (a->D & 3)) return WJ_ERR_ARG;
     const long Rd = (long)a->B * a->G * a->T;          // dense positions (the target count runs over all of them)
@@ -815,8 +691,7 @@ static int masked_loss_launch(const wj_loss_args* a, void* stream) {
         }
     }
     hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(1024), 0, STREAM, a->workspace, a->loss, R);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }
 
 // workspace of both entries: the target count and the loss sum, then one partial per dense position
@@ -825,73 +700,67 @@ int64_t wj_masked_mse_ws_bytes(const wj_mse_args* a) { return masked_loss_ws_byt
 int64_t wj_masked_loss_ws_bytes(const wj_loss_args* a) { return masked_loss_ws_bytes(a->B, a->G, a->T); }
 
 extern "C" int wj_masked_mse(const wj_mse_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a) return WJ_ERR_ARG;
     const wj_loss_args l = {a->preds, a->targets, a->tgt, a->rows, a->loss, a->dpreds, a->workspace, a->gscale_ptr,
                             a->B, a->G, a->T, a->D, a->n_rows, a->gscale, WJ_LOSS_MSE, 0.f};
-    return masked_loss_launch(&l, stream);
+    return masked_loss_launch(&l, stream, entry);
 }
 
 extern "C" int wj_masked_loss(const wj_loss_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a) return WJ_ERR_ARG;
-    return masked_loss_launch(a, stream);
+    return masked_loss_launch(a, stream, entry);
 }
 
 extern "C" int wj_ema_update(const wj_ema_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a || !a->student || !a->teacher || a->n <= 0 || (a->n & 3)) return WJ_ERR_ARG;
     hipLaunchKernelGGL(ema_kernel, dim3(grid_for(a->n / 4, 256)), dim3(256), 0, STREAM, *a);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }
 
 constexpr int SUMSQ_MAX_GRID = 1024;           // one partial float per workgroup in the workspace
 int64_t wj_grad_sumsq_ws_bytes(const wj_sumsq_args*) { return SUMSQ_MAX_GRID * 4; }
 
 extern "C" int wj_grad_sumsq(const wj_sumsq_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a || !a->g || !a->out || !a->workspace || a->n <= 0 || (a->n & 3)) return WJ_ERR_ARG;
     int grid = grid_for(a->n / 4, 256, SUMSQ_MAX_GRID);
     if (a->workgroups > 0 && a->workgroups < grid) grid = a->workgroups;
     hipLaunchKernelGGL(sumsq_partial_kernel, dim3(grid), dim3(256), 0, STREAM, a->g, a->workspace, (long)a->n);
     hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(1024), 0, STREAM, (const float*)a->workspace, a->out, grid, a->accumulate);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }
 
 extern "C" int wj_adamw_step(const wj_adamw_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a || !a->p || !a->g || !a->m || !a->v || a->n <= 0 || (a->n & 3)) return WJ_ERR_ARG;
     int grid = grid_for(a->n / 4, 256);
     if (a->workgroups > 0 && a->workgroups < grid) grid = a->workgroups;
     hipLaunchKernelGGL(adamw_kernel, dim3(grid), dim3(256), 0, STREAM, *a);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }
 
 extern "C" int wj_transpose_bf16(const wj_transpose_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a || !a->src || !a->dst || !a->table || a->n_mats <= 0 || a->n_tiles <= 0) return WJ_ERR_ARG;
     if (((uintptr_t)a->src | (uintptr_t)a->dst) & 15) return WJ_ERR_ARG;
     hipLaunchKernelGGL(transpose_tiles_kernel, dim3(a->n_tiles), dim3(256), 0, STREAM, *a);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }
 
 extern "C" int wj_cast_f32_to_bf16(const wj_cast_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a || !a->src || !a->dst || a->n <= 0) return WJ_ERR_ARG;
     hipLaunchKernelGGL(cast_kernel, dim3(grid_for(a->n / 4 + 1, 256)), dim3(256), 0, STREAM, a->src, (bf16_t*)a->dst, (long)a->n);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }
 
 extern "C" int wj_crop_normalize_bf16(const wj_crop_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a || !a->src || !a->starts || !a->out || a->B <= 0 || a->S <= 0 || a->C <= 0 || a->length <= 1 || a->L_full < a->length)
         return WJ_ERR_ARG;
     hipLaunchKernelGGL(crop_kernel, dim3(a->B * a->S), dim3(1024), 0, STREAM, *a);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }

@@ -17,8 +17,7 @@
 // 16-byte aligned; the memory pipeline takes dword-aligned dwordx4 accesses, and where the ragged offset allows (the loader
 // rounds every clip's offset up to four floats) they are aligned.  The last 1..3 samples of a block and every group that touches
 // a row edge or a ramp go element by element.
-#include "common.h"
-#include "../../include/wavjepa_hip.h"
+#include "stream_pieces.h"
 
 namespace {
 
@@ -143,7 +142,7 @@ int64_t wj_noise_prepare_ws_bytes(const wj_noise_prepare_args* a) {
 }
 
 extern "C" int wj_noise_prepare(const wj_noise_prepare_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a || !a->noise || !a->out || !a->workspace || !a->offsets || !a->lengths || !a->cut_start || !a->place_start || !a->clips)
         return WJ_ERR_ARG;
     const int rc = check_dims(a);
@@ -190,6 +189,5 @@ extern "C" int wj_noise_prepare(const wj_noise_prepare_args* a, void* stream) {
         hipLaunchKernelGGL(noise_sumsq_kernel, dim3((unsigned)(((long)longest + SUM_BLOCK - 1) / SUM_BLOCK), m), dim3(256), 0, st, d, c);
         hipLaunchKernelGGL(noise_write_kernel, dim3((unsigned)(((long)T + ROW_BLOCK - 1) / ROW_BLOCK), m), dim3(256), 0, st, d, c);
     }
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }

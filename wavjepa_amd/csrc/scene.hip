@@ -23,8 +23,7 @@
 // fixed order (per-chunk partials, then a serial fold: bit-reproducible), a = sqrt(Ex / (En + 1e-9) * 10^(-snr/10)),
 // out = source + a * noise.
 #include <string.h>
-#include "common.h"
-#include "../../include/wavjepa_hip.h"
+#include "stream_pieces.h"
 
 namespace {
 
@@ -273,12 +272,12 @@ __global__ __launch_bounds__(256) void snr_partial_kernel(const float* __restric
         ex = fmaf(a, a, ex); en = fmaf(c, c, en);
     }
     __shared__ float red[2][8];
-    ex = wave_sum(ex); en = wave_sum(en);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = ex; red[1][threadIdx.x >> 6] = en; }
+    stage_wave_sum(ex, red[0]);
+    stage_wave_sum(en, red[1]);
     __syncthreads();
     if (threadIdx.x == 0) {
-        part[((long)bc * MIX_CHUNKS + ch) * 2 + 0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        part[((long)bc * MIX_CHUNKS + ch) * 2 + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+        part[((long)bc * MIX_CHUNKS + ch) * 2 + 0] = fold4(red[0]);
+        part[((long)bc * MIX_CHUNKS + ch) * 2 + 1] = fold4(red[1]);
     }
 }
 
@@ -333,7 +332,7 @@ int64_t wj_snr_mix_ws_bytes(const wj_snr_mix_args* a) {
 }
 
 extern "C" int wj_rir_convolve(const wj_rir_conv_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     ConvPlan p;
     if (!a || !a->x || !a->h || !a->y || !a->workspace || !plan(a, p)) return WJ_ERR_ARG;
     if (a->h_stride_c < a->L || a->h_stride_b < (int64_t)(a->C - 1) * a->h_stride_c + a->L) return WJ_ERR_ARG;
@@ -353,20 +352,17 @@ extern "C" int wj_rir_convolve(const wj_rir_conv_args* a, void* stream) {
                            (long)a->h_stride_b, (long)a->h_stride_c, p.nb, p.P);
         hipLaunchKernelGGL((scene_mac_ifft_kernel<Fft1024>), g2, blk, LDS1K, st, X, H, a->y, a->B, a->C, a->T, p.nb, p.P, a->accumulate);
     }
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }
 
 extern "C" int wj_snr_mix(const wj_snr_mix_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
+    const CheckedEntry entry(__func__);
     if (!a || !a->source || !a->noise || !a->out || !a->snr || !a->start || !a->length || !a->workspace) return WJ_ERR_ARG;
     if (a->B <= 0 || a->C <= 0 || a->T <= 0) return WJ_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(snr_partial_kernel, dim3(a->B * a->C, MIX_CHUNKS), dim3(256), 0, st, a->source, a->noise, a->start, a->length,
                        a->workspace, a->C, a->T);
-    const int chunks = max(1, min(256, (a->T + 8191) / 8192));
-    hipLaunchKernelGGL(snr_apply_kernel, dim3(a->B * a->C, chunks), dim3(256), 0, st, a->source, a->noise, a->snr, a->workspace, a->out,
+    hipLaunchKernelGGL(snr_apply_kernel, dim3(a->B * a->C, grid_for(a->T, 8192, 256)), dim3(256), 0, st, a->source, a->noise, a->snr, a->workspace, a->out,
                        a->C, a->T);
-    WJ_CHECK_LAUNCH();
-    return WJ_OK;
+    return entry.launched();
 }
