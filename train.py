@@ -86,7 +86,9 @@ class ComponentFactory:
                        resample_sr=cfg.data.sr, process_audio_seconds=cfg.data.process_seconds,
                        nr_samples_per_audio=cfg.data.samples_per_audio, compile_modules=cfg.trainer.compile_modules,
                        average_top_k_layers=cfg.trainer.average_top_k_layers, size=cfg.trainer.get("size", "base"),
-                       warmup_steps=cfg.trainer.get("warmup_steps", 100000), loss_fn=losses[loss]())
+                       warmup_steps=cfg.trainer.get("warmup_steps", 100000), loss_fn=losses[loss](),
+                       # trainer.use_gradient_checkpointing: recompute layer activations in the backward (student and predictor)
+                       use_gradient_checkpointing=bool(cfg.trainer.get("use_gradient_checkpointing", False)))
         except Exception as e:
             raise RuntimeError(f"Failed to create network instance: {str(e)}")
 

@@ -44,6 +44,7 @@ class EngineConfig:
     conv_bias: bool = False        # conv layers carry a bias (mode "layer_norm" only)
     loss_kind: str = "mse"         # per-element loss of the masked objective: "mse" | "l1" | "smooth_l1" | "huber" (ops.masked_loss)
     loss_beta: float = 1.0         # smooth-L1's beta / Huber's delta
+    recompute: bool = False        # activation recomputation in the student and the predictor (JEPA use_gradient_checkpointing; _alloc_ring)
 
 
 @dataclass
@@ -245,6 +246,8 @@ class _Acts:
 
 
 class JepaEngine:
+    BW_RING = dict(enc=(4, 2), dec=(2, 1))     # per stack: (slots of the backward's buffer ring, layers per grouped weight-gradient launch)
+
     def __init__(self, cfg: EngineConfig, flat: FlatParams, pos_enc: torch.Tensor, pos_dec: torch.Tensor):
         ops.require_gpu()
         self.cfg, self.flat = cfg, flat
@@ -314,6 +317,9 @@ class JepaEngine:
         # re-quantised from their bf16 shadows once per step, activations by wj_quantize_mxfp8 in front of each GEMM.  The backward
         # is unchanged: it differentiates the bf16 graph (straight-through), with the saved bf16 activations and bf16 weights.
         self.fp8 = _os.environ.get("WJ_FP8", "0") == "1"
+        # activation recomputation (EngineConfig.recompute): a layer of the student / predictor keeps only the output the next layer reads;
+        # everything else it saves lives in a ring of the backward's slot count and is computed again in front of the layer's backward
+        self.recompute = bool(cfg.recompute)
         self._check_fp8()
         self._w8: Dict[int, Tuple[torch.Tensor, torch.Tensor, int, int]] = {}     # bf16 weight pointer -> (q, scales, N, K)
         self._a8: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}               # per stack: activation scratch (q, scales)
@@ -457,6 +463,11 @@ class JepaEngine:
                      if self._row_form_pays(M, n_out) or (pairs and self._pair_pays(M, n_out, k_in)))
 
     def _check_fp8(self) -> None:
+        if self.fp8 and self.recompute:
+            # the fp8 forward hands a layer's output to the next layer in the stack's fp8 scratch as well; a second forward that starts
+            # from a kept bf16 output would quantise it in another launch order, and nothing pins that to the first pass's bits
+            raise RuntimeError("fp8 mode (WJ_FP8=1 / engine.fp8) is not combined with activation recomputation (recompute=True / "
+                               "use_gradient_checkpointing): the second forward runs in bf16")
         if self.fp8 and (self.cfg.norm_first_enc or self.cfg.norm_first_dec):
             raise RuntimeError("fp8 mode (WJ_FP8=1 / engine.fp8) covers post-norm stacks only: a norm_first=True stack runs in bf16")
         if self.fp8 and self.cfg.conv_mode == "layer_norm":
@@ -507,28 +518,46 @@ class JepaEngine:
         self.front.w_fresh = False                  # GEMM layouts of conv layers 1..: rebuilt by the front-end, behind its conv0 launches
 
     # ------------------------------------------------------------------------------------------------ arena
-    def _alloc_stack(self, M: int, D: int, H: int, B: int, layers: int) -> List[_Acts]:
-        bf, f32, dev = torch.bfloat16, torch.float32, self.dev
+    def _alloc_stack(self, M: int, D: int, H: int, B: int, layers: int, skip: Sequence[str] = ()) -> List[_Acts]:
+        """`layers` sets of everything a layer saves for its backward; the buffers named in `skip` are left out (None)."""
+        bf, f32 = torch.bfloat16, torch.float32
+        shapes = dict(qkv=((M, 3 * D), bf), o=((M, D), bf), lse=((B * H * self.T,), f32), p=((M, D), bf), m1=((M,), f32), r1=((M,), f32),
+                      x1=((M, D), f32), x1b=((M, D), bf),
+                      h=((M, 4 * D), bf),           # holds gelu'(linear1 output), see EPI_BIAS_GELU2
+                      g=((M, 4 * D), bf), f=((M, D), bf), m2=((M,), f32), r2=((M,), f32), x2=((M, D), f32), x2b=((M, D), bf))
+        assert tuple(shapes) == _Acts.__slots__
         out = []
         for _ in range(layers):
             a = _Acts()
-            a.qkv = _empty(M, 3 * D, dtype=bf, device=dev)
-            a.o = _empty(M, D, dtype=bf, device=dev)
-            a.lse = _empty(B * H * self.T, dtype=f32, device=dev)
-            a.p = _empty(M, D, dtype=bf, device=dev)
-            a.m1 = _empty(M, dtype=f32, device=dev)
-            a.r1 = _empty(M, dtype=f32, device=dev)
-            a.x1 = _empty(M, D, dtype=f32, device=dev)
-            a.x1b = _empty(M, D, dtype=bf, device=dev)
-            a.h = _empty(M, 4 * D, dtype=bf, device=dev)        # holds gelu'(linear1 output), see EPI_BIAS_GELU2
-            a.g = _empty(M, 4 * D, dtype=bf, device=dev)
-            a.f = _empty(M, D, dtype=bf, device=dev)
-            a.m2 = _empty(M, dtype=f32, device=dev)
-            a.r2 = _empty(M, dtype=f32, device=dev)
-            a.x2 = _empty(M, D, dtype=f32, device=dev)
-            a.x2b = _empty(M, D, dtype=bf, device=dev)
+            for name, (shape, dtype) in shapes.items():
+                setattr(a, name, None if name in skip else _empty(*shape, dtype=dtype, device=self.dev))
             out.append(a)
         return out
+
+    def _alloc_ring(self, stack: str, M: int, B: int):
+        """Recompute mode: (ring, kept, view) of a stack.  ring: as many full activation sets as the backward's buffer ring has slots
+        (BW_RING), without the two buffers that are kept.  kept[i]: what layer i + 1 (or the final norm) reads of layer i, for every
+        layer -- post-norm x2 (fp32) and x2b (bf16), pre-norm the stream x2 (fp32) and the branch output f (bf16) that the next norm
+        adds: 6 D bytes per row.  view[i]: layer i's _Acts, slot i % nbuf of the ring with kept[i] in place of the two buffers, which
+        is what the layer forms and their backward are handed in either pass."""
+        layers, D, H, pre, _ = self._stack(stack)
+        nbuf = self.BW_RING[stack][0]
+        names = ("x2", "f") if pre else ("x2", "x2b")
+        ring = self._alloc_stack(M, D, H, B, min(nbuf, len(layers)), skip=names)
+        kept, view = [], []
+        for i in range(len(layers)):
+            kept.append((_empty(M, D, dtype=torch.float32, device=self.dev), _empty(M, D, dtype=torch.bfloat16, device=self.dev)))
+            v = _Acts()
+            for name in _Acts.__slots__:
+                setattr(v, name, getattr(ring[i % nbuf], name))
+            setattr(v, names[0], kept[i][0])
+            setattr(v, names[1], kept[i][1])
+            view.append(v)
+        return ring, kept, view
+
+    def _acts(self, stack: str) -> List[_Acts]:
+        """Per layer of the stack: where it saves for the backward (recompute mode: ring slot + kept output, _alloc_ring)."""
+        return getattr(self, stack + ("_view" if self.recompute else "_acts"))
 
     def alloc(self, N: int, train: bool = True, G: int = 0, need_enc: int = 0, need_dec: int = 0) -> None:
         """(Re)build the arena for N clips (and, for training, G target groups per clip).
@@ -594,8 +623,12 @@ class JepaEngine:
         self.enc_fr = _empty(M, dtype=f32, device=dev)
         if not train:
             return
-        self.enc_acts = self._alloc_stack(Me, c.d_enc, c.h_enc, N, c.l_enc)
-        self.dec_acts = self._alloc_stack(Md, c.d_dec, c.h_dec, N * G, c.l_dec)
+        if self.recompute:
+            self.enc_acts, self.enc_kept, self.enc_view = self._alloc_ring("enc", Me, N)
+            self.dec_acts, self.dec_kept, self.dec_view = self._alloc_ring("dec", Md, N * G)
+        else:
+            self.enc_acts = self._alloc_stack(Me, c.d_enc, c.h_enc, N, c.l_enc)
+            self.dec_acts = self._alloc_stack(Md, c.d_dec, c.h_dec, N * G, c.l_dec)
         self.ctx_in = _empty(Me, c.d_enc, dtype=bf, device=dev)      # gathered context rows (<= Me)
         self.enc_in = _empty(Me, c.d_enc, dtype=f32, device=dev)     # ragged: local features of the context rows
         self.enc_in_b = _empty(Me, c.d_enc, dtype=bf, device=dev)
@@ -621,7 +654,7 @@ class JepaEngine:
         self.mse_ws = _empty(ops.workspace_bytes("wj_masked_mse", B=N, G=G, T=T) // 4, dtype=f32, device=dev)
         # backward scratch, one set per stack width
         self.bw = {}
-        for tag, (m, d, nbuf, group) in dict(enc=(Me, c.d_enc, 4, 2), dec=(Md, c.d_dec, 2, 1)).items():
+        for tag, (m, d, (nbuf, group)) in dict(enc=(Me, c.d_enc, self.BW_RING["enc"]), dec=(Md, c.d_dec, self.BW_RING["dec"])).items():
             # The weight gradients of `group` consecutive layers go out as ONE grouped launch on the side stream (wj_wgrad_grouped:
             # one small split-K factor for 4-8 problems instead of a large one per problem).  The buffers it reads (dY of every
             # linear) therefore exist 2 * group times (slot = layer % nbuf), so that the main chain may run a whole group ahead.
@@ -670,24 +703,29 @@ class JepaEngine:
         ops.mask_gather_rows(x, rows, self.tail_x, n_rows=M, D=D, elem_bytes=4)
         return self.tail_o, self.tail_x, M
 
-    def _mlp_fwd(self, stack: str, w: _Layer, a: _Acts, xb: torch.Tensor, M: int, D: int, save: bool) -> None:
-        """a.f = linear2(gelu(linear1(xb))) in bf16; `save` also keeps gelu'(linear1 output) in a.h for the backward."""
+    def _mlp_fwd(self, stack: str, w: _Layer, a: _Acts, xb: torch.Tensor, M: int, D: int, save: bool, out: bool = True) -> None:
+        """a.f = linear2(gelu(linear1(xb))) in bf16; `save` also keeps gelu'(linear1 output) in a.h for the backward.
+        out=False: linear1 only (a.g and a.h), for a second forward whose a.f was kept from the first."""
         if save:
             self._linear_fwd(stack, xb, w.w1, a.h, M=M, N=4 * D, K=D, bias=w.b1, epilogue=ops.EPI_BIAS_GELU2, C2=a.g)
         else:
             self._linear_fwd(stack, xb, w.w1, a.g, M=M, N=4 * D, K=D, bias=w.b1, epilogue=ops.EPI_BIAS_GELU)
-        self._linear_fwd(stack, a.g, w.w2, a.f, M=M, N=D, K=4 * D, bias=w.b2)
+        if out:
+            self._linear_fwd(stack, a.g, w.w2, a.f, M=M, N=D, K=4 * D, bias=w.b2)
 
     def _layer_fwd(self, w: _Layer, a: _Acts, x_in: torch.Tensor, xb_in: torch.Tensor, M: int, D: int, H: int, B: int,
                    mask: Optional[torch.Tensor], seq: Optional[Tuple[torch.Tensor, int]] = None, save: bool = True,
                    x2_out: Optional[torch.Tensor] = None, x2_stats: Optional[torch.Tensor] = None,
-                   sub: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None, stack: str = "enc", xq_ready: bool = False) -> bool:
+                   sub: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None, stack: str = "enc", xq_ready: bool = False,
+                   redo: bool = False) -> bool:
         """Post-norm layer: x1 = LN1(x + out_proj(attn(in_proj(x)))); x2 = LN2(x1 + linear2(gelu(linear1(x1)))).
         `seq` = (offsets int32 [B+1], longest sequence) selects the ragged form: M packed rows, no key mask.
         save=False (teacher / inference): nothing is kept for a backward (no gelu' output, no softmax statistics).
         sub = (rows int32 [Ms], inverse int32 [M], Ms): only these rows continue after the attention (the last predictor layer:
         context rows are keys / values there and nothing reads their outputs).
-        xq_ready / return value (fp8 mode): the stack's small fp8 buffer already / now holds this layer's input / output."""
+        xq_ready / return value (fp8 mode): the stack's small fp8 buffer already / now holds this layer's input / output.
+        redo (recompute mode, in front of the layer's backward): the same launches once more; x2 / x2b were kept from the first pass --
+        the side stream may be reading x2b -- so norm2 writes its row statistics only."""
         eps = self.cfg.ln_eps
         # fp8 mode with an eligible width (K = D a multiple of 256): the GEMM inputs are produced directly in the MX fp8 operand
         # format by their producers -- LayerNorm (x1 for linear1, x2 for the next layer's in_proj) and linear1's GELU epilogue
@@ -725,7 +763,8 @@ class JepaEngine:
             self._mlp_fwd(stack, w, a, a.x1b, M, D, save)
         # x2_out / x2_stats (teacher): the layer output goes to its own buffer and its per-clip (sum, sum of squares) is
         # accumulated on the way, so that the targets are ONE pass over the kept layers (wj_instnorm_mean)
-        ops.layernorm_fwd(a.x1, w.g2, w.be2, M=M, D=D, eps=eps, r=a.f, y_f32=a.x2 if x2_out is None else x2_out, y_bf16=a.x2b,
+        y2 = (None, None) if redo else (a.x2 if x2_out is None else x2_out, a.x2b)
+        ops.layernorm_fwd(a.x1, w.g2, w.be2, M=M, D=D, eps=eps, r=a.f, y_f32=y2[0], y_bf16=y2[1],
                           mean=a.m2, rstd=a.r2, group_stats=x2_stats, group_rows=self.T if x2_stats is not None else 0,
                           workgroups=lean if x2_stats is None else 0, **f8_out)
         return f8 and sub is None              # the small fp8 buffer now holds x2 for the next layer of this stack
@@ -733,14 +772,15 @@ class JepaEngine:
     def _layer_fwd_pre(self, w: _Layer, a: _Acts, x_in, r_in, M: int, D: int, H: int, B: int, mask: Optional[torch.Tensor],
                        seq: Optional[Tuple[torch.Tensor, int]] = None, save: bool = True, s_out: Optional[torch.Tensor] = None,
                        s_stats: Optional[torch.Tensor] = None, sub: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None,
-                       stack: str = "enc"):
+                       stack: str = "enc", redo: bool = False):
         """Pre-norm layer (norm_first=True): s1 = s0 + out_proj(attn(in_proj(LN1(s0)))); s2 = s1 + linear2(gelu(linear1(LN2(s1)))).
         The residual add of a branch is fused into the NEXT norm (wj_layernorm_pre_fwd), so the layer takes its input as the pair
         (x_in, r_in) -- s0 = x_in + r_in, r_in = the previous layer's linear2 output, None for the first layer of a stack -- and returns
         its output as the pair (s1, linear2 output): the next layer's norm1, or the stack's final norm, adds them.
         Saved in `a`: x1 = s0 (when r_in is None, s0 is x_in itself and nothing is stored), x1b = LN1(s0), x2 = s1, x2b = LN2(s1).
         s_out / s_stats (teacher): s0 -- the previous layer's output -- goes to its own buffer, with its per-clip (sum, sum of squares).
-        seq, save, sub: as _layer_fwd."""
+        seq, save, sub: as _layer_fwd.  redo (recompute mode, in front of the layer's backward): the same launches once more, without
+        the two outputs that were kept from the first pass (x2 is not written again, linear2 is not run: no backward reads a.f)."""
         eps = self.cfg.ln_eps
         s0 = x_in if (r_in is None and s_out is None) else (a.x1 if s_out is None else s_out)
         ops.layernorm_pre_fwd(x_in, w.g1, w.be1, M=M, D=D, eps=eps, r=r_in, s_f32=None if s0 is x_in else s0, y_bf16=a.x1b,
@@ -752,9 +792,9 @@ class JepaEngine:
         if sub is not None:
             o_in, s0, M = self._tail_gather(a, s0, sub, D)
         self._linear_fwd(stack, o_in, w.wo, a.p, M=M, N=D, K=D, bias=w.bo)
-        ops.layernorm_pre_fwd(s0, w.g2, w.be2, M=M, D=D, eps=eps, r=a.p, s_f32=a.x2, y_bf16=a.x2b, mean=a.m2 if save else None,
-                              rstd=a.r2 if save else None)
-        self._mlp_fwd(stack, w, a, a.x2b, M, D, save)
+        ops.layernorm_pre_fwd(s0, w.g2, w.be2, M=M, D=D, eps=eps, r=a.p, s_f32=None if redo else a.x2, y_bf16=a.x2b,
+                              mean=a.m2 if save else None, rstd=a.r2 if save else None)
+        self._mlp_fwd(stack, w, a, a.x2b, M, D, save, out=not redo)
         return a.x2, a.f
 
     def _gemm8(self, q, sc, w_ptr: int, out, *, M: int, N: int, K: int, bias, epilogue: int = ops.EPI_BF16, C2=None, **extra) -> None:
@@ -1053,7 +1093,8 @@ class JepaEngine:
         Returns flushed = True when the weight-gradient queue went out (_wgrads: the queued layers' gradients are then final in
         side-stream order)."""
         ds, dxb, dqkv = bw["ds"], bw["dxb"], bw["dqkv"][parity]
-        self._slot_wait(bw, parity)
+        if not self.recompute:             # (recompute mode: _redo_layer waited for the slot before it wrote the activations)
+            self._slot_wait(bw, parity)
         Ms, x_ln1 = M, x_in
         if sub is not None:              # dy holds the sub-rows only; everything up to the attention works on them
             Ms, x_ln1 = sub[2], self.tail_x
@@ -1079,7 +1120,8 @@ class JepaEngine:
         goes to dx_out (fp32) for the consumers below the stack.  s0: the stream the layer read (a.x1, or the stack's input for the
         first layer).  Returns (d(s0) buffer, flushed)."""
         ds, dxb = bw["ds"], bw["dxb"]
-        self._slot_wait(bw, parity)
+        if not self.recompute:             # (recompute mode: waited for in front of the layer's second forward, see _redo_layer)
+            self._slot_wait(bw, parity)
         Ms = M if sub is None else sub[2]      # ds holds the sub-rows only; everything up to the attention works on them
         self._mlp_bwd(w, a, a.x2b, bw, parity, Ms, D)
         # norm2: d(s1) = d(s2) + LN2'(d LN2(s1)), in place; its bf16 rounding is out_proj's dY, its column sums out_proj.bias's gradient
@@ -1136,15 +1178,37 @@ class JepaEngine:
         ops.layernorm_fwd(x, gamma, beta, M=Mo, D=D, eps=c.norm_eps,
                           workgroups=self.ln_lean_wgs if (lean and self._lean_now and stack in self.ln_lean) else 0, **out)
 
+    def _redo_layer(self, stack: str, i: int, x0: torch.Tensor, xb0: torch.Tensor, M: int, B: int, mask: Optional[torch.Tensor],
+                    seq: Optional[Tuple[torch.Tensor, int]], sub: Optional[Tuple[torch.Tensor, torch.Tensor, int]]) -> None:
+        """Recompute mode: layer i's forward once more, from the kept output of layer i - 1 (or the stack's input) into ring slot
+        i % nbuf, with the masks, offsets and sub-rows of the first pass.  The slot's last readers are the grouped weight gradients of
+        layer i + nbuf on the side stream: the main stream waits for the event that guards the slot before it writes -- once per
+        layer: the layer's backward, which waits for the same event with the flag off, does not wait again."""
+        bw, acts = self.bw[stack], self._acts(stack)
+        layers, D, H, pre, _ = self._stack(stack)
+        if not (pre and i < len(layers) - 1):      # (pre-norm: the backward of layer i + 1 waited for this slot to write its dsb2)
+            self._slot_wait(bw, i % bw["nbuf"])
+        lean_was, self._lean_now = self._lean_now, self.use_side      # (WJ_LN_LEAN: the LayerNorm form of the first pass)
+        try:
+            if pre:
+                x, r = (x0, None) if i == 0 else (acts[i - 1].x2, acts[i - 1].f)
+                self._layer_fwd_pre(layers[i], acts[i], x, r, M, D, H, B, mask, seq, save=True, sub=sub, stack=stack, redo=True)
+            else:
+                x, xb = (x0, xb0) if i == 0 else (acts[i - 1].x2, acts[i - 1].x2b)
+                self._layer_fwd(layers[i], acts[i], x, xb, M, D, H, B, mask, seq, save=True, sub=sub, stack=stack, redo=True)
+        finally:
+            self._lean_now = lean_was
+
     def _stack_bwd(self, stack: str, x0: torch.Tensor, xb0: torch.Tensor, M: int, B: int, mask: Optional[torch.Tensor],
                    seq: Optional[Tuple[torch.Tensor, int]] = None, *, sub: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None,
                    flushed=None) -> torch.Tensor:
         """Backward of _stack_fwd: bw["dx1"] holds the fp32 gradient of the final norm's output (nothing bypasses that norm); returns
         the fp32 gradient of the stack's input (x0, xb0).  The weight gradients of bw["group"] consecutive layers share a grouped
-        launch; `flushed(i)` is called behind layer i when its launch has been queued."""
+        launch; `flushed(i)` is called behind layer i when its launch has been queued.  Recompute mode: every layer's forward is issued
+        again in front of its backward (_redo_layer)."""
         f, bw = self.flat, self.bw[stack]
         layers, D, H, pre, norm = self._stack(stack)
-        acts = self.enc_acts if stack == "enc" else self.dec_acts
+        acts = self._acts(stack)
         fm, fr = getattr(self, stack + "_fm"), getattr(self, stack + "_fr")
         top, nbuf, group = len(layers) - 1, bw["nbuf"], bw["group"]
         Mo = M if sub is None else sub[2]                      # rows that left the stack
@@ -1160,6 +1224,8 @@ class JepaEngine:
         for i in range(top, -1, -1):
             w, a, sub_i = layers[i], acts[i], sub if i == top else None
             flush = (top - i) % group == group - 1 or i == 0
+            if self.recompute:
+                self._redo_layer(stack, i, x0, xb0, M, B, mask, seq, sub_i)
             if pre:
                 dy, done = self._layer_bwd_pre(w, a, x0 if i == 0 else a.x1, layers[i - 1] if i > 0 else None, bw["dy"], M, D, H, B, mask,
                                                bw, i % nbuf, seq, sub=sub_i, flush=flush)
@@ -1239,11 +1305,11 @@ class JepaEngine:
             ops.mask_gather_rows(self.lf, plan.keep, self.enc_in, n_rows=n_ctx, D=De, elem_bytes=4)
             if not c.norm_first_enc:        # (a pre-norm stack's first norm1 makes the bf16 GEMM operand itself)
                 ops.mask_gather_rows(self.lf_b, plan.keep, self.enc_in_b, n_rows=n_ctx, D=De, elem_bytes=2)
-            self._stack_fwd("enc", self.enc_in, self.enc_in_b, n_ctx, N, None, (plan.enc_off, max(plan.max_enc, 1)), acts=self.enc_acts,
+            self._stack_fwd("enc", self.enc_in, self.enc_in_b, n_ctx, N, None, (plan.enc_off, max(plan.max_enc, 1)), acts=self._acts("enc"),
                             lean=True, y_bf16=self.ctx_in, **final)
         else:
             # student encoder over every token (keys restricted to the context), then the boolean-mask gather
-            self._stack_fwd("enc", self.lf, self.lf_b, M, N, plan.ctx_u8, acts=self.enc_acts,
+            self._stack_fwd("enc", self.lf, self.lf_b, M, N, plan.ctx_u8, acts=self._acts("enc"),
                             y_f32=None if c.norm_first_enc else self.enc_out, y_bf16=self.enc_out_b, **final)
             ops.mask_gather_rows(self.enc_out_b, plan.keep, self.ctx_in, n_rows=n_ctx, D=De, elem_bytes=2)
         ops.gemm(self.ctx_in, f.ptr16("encoder_to_decoder_mapper.weight"), self.cf, M=n_ctx, N=Dd, K=De, lda=De, ldb=De, ldc=Dd,
@@ -1259,7 +1325,7 @@ class JepaEngine:
                                       out_f32=self.dec_in, out_bf16=self.dec_in_b)
         self.tail = (plan.tgt_rows, plan.tgt_inv, plan.n_tgt) if (rag and self.trim_tail and plan.n_tgt > 0) else None
         Mo = plan.n_tgt if self.tail is not None else Md      # rows that leave the predictor
-        self._stack_fwd("dec", self.dec_in, self.dec_in_b, Md, N * G, plan.vis_u8, dseq, acts=self.dec_acts, sub=self.tail, lean=True,
+        self._stack_fwd("dec", self.dec_in, self.dec_in_b, Md, N * G, plan.vis_u8, dseq, acts=self._acts("dec"), sub=self.tail, lean=True,
                         y_bf16=self.dec_out_b, mean=self.dec_fm, rstd=self.dec_fr)
         ops.gemm(self.dec_out_b, f.ptr16("decoder_to_encoder_mapper.weight"), self.preds, M=Mo, N=De, K=Dd, lda=Dd, ldb=Dd,
                  ldc=De, bias=f.ptr32("decoder_to_encoder_mapper.bias"))

@@ -298,7 +298,10 @@ class JEPA(_ModuleBase):
         self.target_length = int(resample_sr * process_audio_seconds)
         self.total_patches = feature_extractor.total_patches(self.target_length)
         self.use_compiled_forward = False            # there is no tracing compiler on this path: kernels are hand-written
-        self.use_gradient_checkpointing = False      # the reference's flag is off by default and buggy (drops the mask)
+        # activation recomputation in the engine (EngineConfig.recompute): the student AND the predictor keep one output per layer and
+        # compute the rest again in the backward, with the masks of the first pass (the reference checkpoints the student only, and
+        # its call drops the key mask: jepa.py:449-450)
+        self.use_gradient_checkpointing = bool(use_gradient_checkpointing)
         if HAS_LIGHTNING:        # as the reference does (jepa.py:105-107): hyper-parameters into the checkpoint
             self.save_hyperparameters(ignore=["feature_encoder", "feature_extractor", "loss_fn"])
             self.hparams["adam_betas"] = tuple(adam_betas)
@@ -309,6 +312,8 @@ class JEPA(_ModuleBase):
                                      process_audio_seconds=process_audio_seconds, nr_samples_per_audio=nr_samples_per_audio,
                                      compile_modules=compile_modules, size=size, warmup_steps=warmup_steps,
                                      decoder_embedding_dim=decoder_embedding_dim)
+            if self.use_gradient_checkpointing:      # recorded only when set, the rule of norm_first_encoder below
+                self.hparams["use_gradient_checkpointing"] = True
             self.global_step = 0
             self.trainer = _NullTrainer()
         self.extract_audio = feature_extractor
@@ -459,7 +464,7 @@ class JEPA(_ModuleBase):
                            top_k=int(self.hparams.average_top_k_layers), ln_eps=self.encoder.layer_norm_eps,
                            norm_first_enc=self.encoder.norm_first, norm_first_dec=self.decoder.norm_first,
                            conv_mode=getattr(ext, "mode", "default"), conv_bias=bool(getattr(ext, "conv_bias", False)),
-                           loss_kind=self.loss_kind, loss_beta=self.loss_beta)
+                           loss_kind=self.loss_kind, loss_beta=self.loss_beta, recompute=self.use_gradient_checkpointing)
         self._engine = JepaEngine(cfg, self._flat, self.pos_encoding_encoder.data, self.pos_encoding_decoder.data)
         self._anchor = torch.zeros(1, device=self.device, requires_grad=True)
         self._student_bf16_fresh = False
