@@ -70,6 +70,8 @@ class ComponentFactory:
         # trainer.norm_first: pre-norm layers in every stack; trainer.norm_first_decoder: the predictor's own setting (default: the same)
         norm_first = bool(cfg.trainer.get("norm_first", False))
         norm_first_dec = bool(cfg.trainer.get("norm_first_decoder", norm_first))
+        # trainer.dropout_encoder / trainer.dropout_decoder: dropout of the student's / the predictor's layers in training (default 0)
+        drop_enc, drop_dec = float(cfg.trainer.get("dropout_encoder", 0.0)), float(cfg.trainer.get("dropout_decoder", 0.0))
         # trainer.loss: the per-element objective on target rows; trainer.loss_beta: smooth-L1's beta / Huber's delta
         loss, beta = str(cfg.trainer.get("loss", "mse")), float(cfg.trainer.get("loss_beta", 1.0))
         losses = {"mse": lambda: None, "l1": lambda: torch.nn.L1Loss(reduction="none"),
@@ -79,9 +81,10 @@ class ComponentFactory:
             raise ValueError(f"Unknown trainer.loss: {loss}. Available losses: {list(losses)}")
         try:
             return cls(feature_extractor=extractor, transformer_encoder_cfg=TransformerEncoderCFG.create(),
-                       transformer_encoder_layers_cfg=TransformerLayerCFG.create(norm_first=norm_first),
+                       transformer_encoder_layers_cfg=TransformerLayerCFG.create(norm_first=norm_first, dropout=drop_enc),
                        transformer_decoder_cfg=TransformerEncoderCFG.create(),
-                       transformer_decoder_layers_cfg=TransformerLayerCFG.create(d_model=384, norm_first=norm_first_dec), lr=cfg.optimizer.lr,
+                       transformer_decoder_layers_cfg=TransformerLayerCFG.create(d_model=384, norm_first=norm_first_dec, dropout=drop_dec),
+                       lr=cfg.optimizer.lr,
                        adam_betas=(cfg.optimizer.b1, cfg.optimizer.b2), adam_weight_decay=cfg.optimizer.weight_decay,
                        resample_sr=cfg.data.sr, process_audio_seconds=cfg.data.process_seconds,
                        nr_samples_per_audio=cfg.data.samples_per_audio, compile_modules=cfg.trainer.compile_modules,

@@ -15,11 +15,15 @@ from typing import Dict, List, Tuple
 HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(os.path.dirname(HERE), "include", "wavjepa_hip.h")
 LAB_HEADER = os.path.join(os.path.dirname(HERE), "include", "wavjepa_hip_lab.h")
+DROPOUT_HEADER = os.path.join(os.path.dirname(HERE), "include", "wavjepa_hip_dropout.h")
 LIB_PATH = os.environ.get("WAVJEPA_HIP_LIB") or os.path.join(HERE, "lib", "libwavjepa_hip.so")   # override: A/B and ablation builds
 # the laboratory build of the same sources (-DWJ_LAB): extra diagnostic entries + every A/B switch; loaded only by load_lab()
 LAB_LIB_PATH = os.environ.get("WAVJEPA_HIP_LAB_LIB") or os.path.join(HERE, "lib", "libwavjepa_hip_lab.so")
+# the dropout forms of the LayerNorm / streamed-attention kernels and wj_dropout_rows (include/wavjepa_hip_dropout.h); loaded by load_dropout()
+DROPOUT_LIB_PATH = os.path.join(HERE, "lib", "libwavjepa_hip_dropout.so")
 
-_SCALARS = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "float": ctypes.c_float, "int": ctypes.c_int}
+_SCALARS = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "float": ctypes.c_float, "int": ctypes.c_int,
+            "uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32}
 
 
 class WavJepaHipError(RuntimeError):
@@ -35,10 +39,13 @@ class Header:
     """What the binding needs of one header: {struct: [(field, ctype)]}, {function: (restype, [argtypes])} in declaration order,
     {stream entry `int f(const S*, void* stream)`: S}, {enum constant: value} and the integer `#define WJ_x value` constants."""
 
-    def __init__(self, path: str):
+    def __init__(self, path: str, known: "Header" = None):
+        """known: the header this one includes (its structs may be embedded by value)"""
         text = _strip_comments(open(path).read())
         self.defines = {k: int(v, 0) for k, v in re.findall(r"^\s*#\s*define\s+(WJ_\w+)\s+(-?(?:0x[0-9a-fA-F]+|\d+))\s*$", text, flags=re.M)}
         self.structs: Dict[str, List[Tuple[str, object]]] = {}
+        self.struct_types: Dict[str, type] = {}      # the ctypes classes, in declaration order: a later struct may embed an earlier one by value
+        earlier = dict(known.struct_types) if known is not None else {}
         for body, name in re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", text, flags=re.S):
             fields: List[Tuple[str, object]] = []
             for decl in body.split(";"):
@@ -54,13 +61,14 @@ class Header:
                     n = n.strip()
                     if not n:
                         continue
-                    ctype = ctypes.c_void_p if is_ptr else _SCALARS[base]
+                    ctype = ctypes.c_void_p if is_ptr else ({**earlier, **self.struct_types}[base] if base in earlier or base in self.struct_types else _SCALARS[base])
                     arr = re.match(r"(\w+)\[(\w+)\]$", n)          # fixed-size array member: name[N] (N a number or a #define)
                     if arr:
                         n, dim = arr.group(1), arr.group(2)
                         ctype = ctype * (int(dim) if dim.isdigit() else self.defines[dim])
                     fields.append((n, ctype))
             self.structs[name] = fields
+            self.struct_types[name] = type(name, (ctypes.Structure,), {"_fields_": fields})
         self.functions: Dict[str, Tuple[object, list]] = {}
         self.entry_args: Dict[str, str] = {}
         for ret, name, params in re.findall(r"\b(int|int64_t)\s+(wj_\w+)\s*\(([^)]*)\)\s*;", text):
@@ -92,11 +100,36 @@ _PROTOTYPES = {**_HEADER.functions, **_LAB.functions}            # name -> (rest
 ENTRY_ARGS = {**_HEADER.entry_args, **_LAB.entry_args}           # stream entry -> its argument struct
 
 
-STRUCTS = {name: type(name, (ctypes.Structure,), {"_fields_": fields}) for name, fields in _STRUCT_FIELDS.items()}
-LAB_STRUCTS = {name: type(name, (ctypes.Structure,), {"_fields_": fields}) for name, fields in _LAB.structs.items()}
+STRUCTS, LAB_STRUCTS = _HEADER.struct_types, _LAB.struct_types
+# libwavjepa_hip_dropout.so: a header, a function list and an entry map of its own -- what describes libwavjepa_hip.so above is unchanged
+_DROP = Header(DROPOUT_HEADER, known=_HEADER)
+DROPOUT_STRUCTS, DROPOUT_FUNCTIONS, DROPOUT_ENTRY_ARGS = _DROP.struct_types, list(_DROP.functions), dict(_DROP.entry_args)
 
 _lib = None
 _lab_lib = None
+_dropout_lib = None
+
+
+def load_dropout():
+    """libwavjepa_hip_dropout.so (once), its struct sizes cross-checked against its own wj_dropout_struct_size.  Loaded behind the release
+    library, so that both bind to the HIP runtime torch brought."""
+    global _dropout_lib
+    if _dropout_lib is None:
+        load()
+        if not os.path.exists(DROPOUT_LIB_PATH):
+            raise WavJepaHipError(f"{DROPOUT_LIB_PATH} is missing: run `python -m wavjepa_amd.build` (or __graft_entry__.build())")
+        lib = ctypes.CDLL(DROPOUT_LIB_PATH)
+        for fn in DROPOUT_FUNCTIONS:
+            if not hasattr(lib, fn):
+                raise WavJepaHipError(f"{DROPOUT_LIB_PATH} does not export {fn} (declared in include/wavjepa_hip_dropout.h); rebuild it")
+            f = getattr(lib, fn)
+            f.restype, f.argtypes = _DROP.functions[fn]
+        for name, cls in DROPOUT_STRUCTS.items():
+            want = lib.wj_dropout_struct_size(name.encode())
+            if want != ctypes.sizeof(cls):
+                raise WavJepaHipError(f"struct {name}: header mirror is {ctypes.sizeof(cls)} bytes, library says {want}")
+        _dropout_lib = lib
+    return _dropout_lib
 
 
 def lib_path() -> str:
@@ -151,7 +184,10 @@ def _load(LIB_PATH: str, FUNCTIONS, STRUCTS):
 
 def workspace_bytes(fn_name: str, args_struct) -> int:
     """Scratch bytes the call `fn_name(args_struct)` needs (pointers in the struct are ignored)."""
-    n = int(load().wj_workspace_bytes(fn_name.encode(), ctypes.byref(args_struct)))
+    if fn_name in DROPOUT_ENTRY_ARGS:
+        n = int(load_dropout().wj_dropout_workspace_bytes(fn_name.encode(), ctypes.byref(args_struct)))
+    else:
+        n = int(load().wj_workspace_bytes(fn_name.encode(), ctypes.byref(args_struct)))
     if n < 0:
         raise WavJepaHipError(f"wj_workspace_bytes: unknown entry point {fn_name}")
     return n
@@ -161,6 +197,7 @@ _ERR = {-1: "invalid argument", -2: "kernel launch failed", -3: "unsupported con
 
 
 def call(fn_name: str, args_struct, stream: int, lab: bool = False) -> None:
-    rc = getattr(load_lab() if lab else load(), fn_name)(ctypes.byref(args_struct), stream)
+    lib = load_dropout() if fn_name in DROPOUT_ENTRY_ARGS else (load_lab() if lab else load())
+    rc = getattr(lib, fn_name)(ctypes.byref(args_struct), stream)
     if rc != 0:
         raise WavJepaHipError(f"{fn_name} failed: {_ERR.get(rc, rc)}")

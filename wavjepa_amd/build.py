@@ -15,6 +15,12 @@ LIB = os.path.join(LIBDIR, "libwavjepa_hip.so")
 LAB_LIB = os.path.join(LIBDIR, "libwavjepa_hip_lab.so")      # the same sources with -DWJ_LAB (include/wavjepa_hip_lab.h): diagnostics + A/B switches
 SOURCES = ["gemm.hip", "gemm_persist.hip", "gemm_pde.hip", "gemm_panel.hip", "norm.hip", "attention.hip", "attention_stream.hip", "conv0.hip", "conv_ln.hip", "misc.hip", "abi.hip", "fp8.hip", "scene.hip", "denoise.hip", "audio_prep.hip", "noise_prep.hip", "rccl_bucket.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-value"]
+# libwavjepa_hip_dropout.so (include/wavjepa_hip_dropout.h): the dropout forms of the LayerNorm and streamed-attention kernels, from the
+# SAME sources with -DWJ_DROPOUT_LIB, and wj_dropout_rows.  -fvisibility=hidden: the parent entries those sources also define stay
+# inside it; it exports what the header declares and nothing else.
+DROPOUT_LIB = os.path.join(LIBDIR, "libwavjepa_hip_dropout.so")
+DROPOUT_SOURCES = ["dropout.hip", "norm.hip", "attention_stream.hip", "dropout_abi.hip"]
+DROPOUT_FLAGS = ["-DWJ_DROPOUT_LIB", "-fvisibility=hidden"]
 
 
 def _hipcc() -> str:
@@ -31,19 +37,21 @@ def _stale(target: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force: bool = False, verbose: bool = True, lab: bool = False) -> str:
+def build(force: bool = False, verbose: bool = True, lab: bool = False, dropout: bool = False) -> str:
     """The release library (compute + query entries, production-safe switches only), or with lab=True the laboratory variant
-    (libwavjepa_hip_lab.so: -DWJ_LAB, the extra entries of include/wavjepa_hip_lab.h and every A/B / diagnostic environment switch)."""
+    (libwavjepa_hip_lab.so: -DWJ_LAB, the extra entries of include/wavjepa_hip_lab.h and every A/B / diagnostic environment switch),
+    or with dropout=True libwavjepa_hip_dropout.so."""
     hipcc = _hipcc()
     os.makedirs(LIBDIR, exist_ok=True)
-    objdir = os.path.join(LIBDIR, "obj_lab" if lab else "obj")
+    objdir = os.path.join(LIBDIR, "obj_dropout" if dropout else ("obj_lab" if lab else "obj"))
     os.makedirs(objdir, exist_ok=True)
     inc = os.path.join(os.path.dirname(HERE), "include")
     headers = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(inc, "*.h"))
-    flags = FLAGS + (["-DWJ_LAB"] if lab else [])
-    lib = LAB_LIB if lab else LIB
+    flags = FLAGS + (DROPOUT_FLAGS if dropout else (["-DWJ_LAB"] if lab else []))
+    lib = DROPOUT_LIB if dropout else (LAB_LIB if lab else LIB)
+    sources = DROPOUT_SOURCES if dropout else SOURCES
     jobs = []
-    for src in SOURCES:
+    for src in sources:
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))
         if force or _stale(o, [s] + headers):
@@ -62,7 +70,7 @@ def build(force: bool = False, verbose: bool = True, lab: bool = False) -> str:
             for s in ex.map(compile_one, jobs):
                 if verbose:
                     print(f"[wavjepa_amd.build] compiled {os.path.basename(s)}", file=sys.stderr)
-    objs = [os.path.join(objdir, s.replace(".hip", ".o")) for s in SOURCES]
+    objs = [os.path.join(objdir, s.replace(".hip", ".o")) for s in sources]
     if force or jobs or _stale(lib, objs):
         cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs
         r = subprocess.run(cmd, capture_output=True, text=True)
@@ -70,7 +78,7 @@ def build(force: bool = False, verbose: bool = True, lab: bool = False) -> str:
             raise RuntimeError(f"link failed:\n{r.stderr}")
         if verbose:
             print(f"[wavjepa_amd.build] linked {lib}", file=sys.stderr)
-    if not lab:
+    if not lab and not dropout:
         build_io(force=force, verbose=verbose)
     return lib
 
@@ -78,6 +86,7 @@ def build(force: bool = False, verbose: bool = True, lab: bool = False) -> str:
 def build_all(force: bool = False, verbose: bool = True) -> None:
     """Release + laboratory libraries (what __graft_entry__.build() and the test suite need)."""
     build(force=force, verbose=verbose)
+    build(force=force, verbose=verbose, dropout=True)
     build(force=force, verbose=verbose, lab=True)
 
 

@@ -65,3 +65,12 @@
 
 // argument structs of the header that no stream entry takes
 #define WJ_OTHER_STRUCTS(S) S(wj_rccl_init_args)
+
+// libwavjepa_hip_dropout.so (include/wavjepa_hip_dropout.h, csrc/dropout_abi.hip): the same two row forms
+#define WJ_DROPOUT_ENTRIES(E, W)                                                       \
+    E(wj_dropout_rows, wj_dropout_rows_args)                                           \
+    E(wj_layernorm_fwd_drop, wj_ln_fwd_drop_args)                                      \
+    W(wj_layernorm_bwd_drop, wj_ln_bwd_drop_args, wj_ln_bwd_drop_ws_bytes)             \
+    E(wj_attn_stream_fwd_drop, wj_attn_fwd_drop_args)                                  \
+    W(wj_attn_stream_bwd_drop, wj_attn_bwd_drop_args, wj_attn_bwd_drop_ws_bytes)
+#define WJ_DROPOUT_OTHER_STRUCTS(S) S(wj_dropout_args)

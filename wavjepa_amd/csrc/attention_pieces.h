@@ -198,6 +198,27 @@ __device__ __forceinline__ void stats_rows(const SeqView<HG>& sv, const float* l
 
 __device__ __forceinline__ f32x4 splat4(float v) { return f32x4{v, v, v, v}; }
 
+// What a tile pair does to dP under dropout of the probabilities.  NoDrop (every parent kernel): nothing, and nothing is compiled.
+// DropBits (attention_stream.hip's _drop kernels): dP <- dP o m * scale, bit 4 u + r = accumulator row r of tile u of the pair is kept.
+struct NoDrop {
+    static constexpr bool ON = false;
+};
+struct DropBits {
+    static constexpr bool ON = true;
+    uint32_t bits;
+    float scale;
+    __device__ __forceinline__ void mask_dp(int u, f32x4& dp) const {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dp[r] = (bits >> (4 * u + r)) & 1u ? dp[r] * scale : 0.f;
+    }
+    // the bf16 probabilities of the pair as pack_tiles lays them out (element e = tile e / 4, row e % 4): P o m
+    __device__ __forceinline__ bf16x8 mask_p(bf16x8 pf) const {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) pf[e] = (bits >> e) & 1u ? pf[e] : f2bf(0.f);
+        return pf;
+    }
+};
+
 // S and dP of one 16 x 16 tile: image rows [t*16, t*16+16) against the wave's own-tile fragments (k = head dim).
 template <int HD>
 __device__ __forceinline__ void s_dp_tile(const char* img0, const char* img1, int t, const bf16x8 (&f0)[HD / 32], const bf16x8 (&f1)[HD / 32],
@@ -225,10 +246,10 @@ __device__ __forceinline__ void p_ds_tile(f32x4 s, f32x4 dp, f32x4 kv, f32x4 lse
 
 // Phase A, one 32-key chunk c of the K (img0) / V (img1) images against the wave's 16 queries (queries on the lane, keys on the
 // accumulator rows): S^T and dP^T -> dS^T as the bf16 B operand of the dQ MFMAs.  kvalid: the image's rows.
-template <int HD, class F>
+template <int HD, class F, class DM = NoDrop>
 __device__ __forceinline__ bf16x8 phase_a_pair(const char* img0, const char* img1, int c, int nt, const bf16x8 (&qf)[HD / 32],
                                                const bf16x8 (&dof)[HD / 32], const float* kvalid, float my_lse, float my_delta, float scale,
-                                               float scale2, int lane) {
+                                               float scale2, int lane, const DM& dm = DM()) {
     f32x4 ds2[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -237,6 +258,7 @@ __device__ __forceinline__ bf16x8 phase_a_pair(const char* img0, const char* img
         if (!F::GUARD || kt < nt) {
             f32x4 s, dp, p, kv = splat4(0.f);
             s_dp_tile<HD>(img0, img1, kt, qf, dof, lane, s, dp);
+            if constexpr (DM::ON) dm.mask_dp(u, dp);
             if constexpr (F::MASKED) kv = *reinterpret_cast<const f32x4*>(kvalid + kt * 16 + 4 * (lane >> 4));
             p_ds_tile<F>(s, dp, kv, splat4(my_lse), splat4(my_delta), scale, scale2, p, ds2[u]);
         }
@@ -245,10 +267,10 @@ __device__ __forceinline__ bf16x8 phase_a_pair(const char* img0, const char* img
 }
 // Phase B, one 32-query chunk c of the Q (img0) / dO (img1) images against the wave's 16 keys (keys on the lane, queries on the
 // accumulator rows): S and dP -> P and dS as the bf16 B operands of the dV / dK MFMAs.  lse_s, delta: the image's rows.
-template <int HD, class F>
+template <int HD, class F, class DM = NoDrop>
 __device__ __forceinline__ void phase_b_pair(const char* img0, const char* img1, int c, int nt, const bf16x8 (&kf)[HD / 32],
                                              const bf16x8 (&vf)[HD / 32], const float* lse_s, const float* delta, float my_kv, float scale,
-                                             float scale2, int lane, bf16x8& pf, bf16x8& dsf) {
+                                             float scale2, int lane, bf16x8& pf, bf16x8& dsf, const DM& dm = DM()) {
     f32x4 p2[2], ds2[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -257,6 +279,7 @@ __device__ __forceinline__ void phase_b_pair(const char* img0, const char* img1,
         if (!F::GUARD || qt < nt) {
             f32x4 s, dp;
             s_dp_tile<HD>(img0, img1, qt, kf, vf, lane, s, dp);
+            if constexpr (DM::ON) dm.mask_dp(u, dp);
             const f32x4 l4 = *reinterpret_cast<const f32x4*>(lse_s + qt * 16 + 4 * (lane >> 4));
             const f32x4 d4 = *reinterpret_cast<const f32x4*>(delta + qt * 16 + 4 * (lane >> 4));
             p_ds_tile<F>(s, dp, splat4(my_kv), l4, d4, scale, scale2, p2[u], ds2[u]);

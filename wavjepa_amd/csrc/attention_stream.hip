@@ -18,7 +18,11 @@
 // workgroups per CU; a block is four 32-row chunks = 8 score tiles = 32 fp32 registers per lane, which pass 1 holds at once to take one
 // maximum and one rescale per block; 64 rows would double the barriers per key, 256 would leave one workgroup per CU.
 // The next block's rows are fetched into registers while the current one is computed on (BlockRegs), as RowRegs does in attention.hip.
+// The _drop entries (dropout on the probabilities) are the same kernels with the DROP flag: the mask of (sequence, head, query, key) comes
+// from csrc/dropout_pieces.h, whose grouping of eight is the eight probabilities a lane holds for one query and one 32-key chunk.
+#include <type_traits>
 #include "attention_pieces.h"
+#include "dropout_host.h"
 
 namespace {
 
@@ -67,8 +71,8 @@ __device__ __forceinline__ void block_scores(f32x4 (&s)[KB / 16], const char* ki
 }
 
 // ------------------------------------------------------------------------------------------------ forward
-template <int HD>
-__global__ __launch_bounds__(NW * 64, 2) void attn_stream_fwd_kernel(wj_attn_fwd_args a, int nqc) {
+template <int HD, bool DROP>
+__device__ __forceinline__ void attn_stream_fwd_body(const wj_attn_fwd_args& a, int nqc, const DropParams& d) {
     constexpr int RS = Img<HD>::RS, KS = HD / 32, DT = HD / 16;
     __shared__ __attribute__((aligned(16))) char kimg[KB * RS];
     __shared__ __attribute__((aligned(16))) char vimg[KB * RS];
@@ -141,22 +145,38 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_stream_fwd_kernel(wj_attn_fwd
 #pragma unroll
                 for (int r = 0; r < 4; ++r) s[2 * c + u][r] = __builtin_amdgcn_exp2f(fmaf(s[2 * c + u][r], scale2, -m2)) * inv;
             // probabilities are normalised BEFORE the bf16 rounding (as a materialised softmax would be)
-            const bf16x8 pf = pack_tiles(s[2 * c], s[2 * c + 1]);
+            bf16x8 pf = pack_tiles(s[2 * c], s[2 * c + 1]);
+            // dropout: the dropped elements of the rounded P are zeroed; the survivors' scale goes once onto O below
+            if constexpr (DROP)
+                pf = DropBits{drop_keep_bits(d, drop_attn_group((uint64_t)sv.b * sv.H + sv.h, qt * 16 + i, kb * (KB / 32) + c, g)), d.scale}.mask_p(pf);
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt)
                 o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tr_frag<HD>(vimg, c, dt * 16, lane), pf, o[dt], 0, 0, 0);
         }
     }
+    if constexpr (DROP) {
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) o[dt] *= d.scale;
+    }
     store_out_lse<HD>(sv, a, qt * 16 + i, o, sum, msafe, scale, g);
+}
+template <int HD>
+__global__ __launch_bounds__(NW * 64, 2) void attn_stream_fwd_kernel(wj_attn_fwd_args a, int nqc) {
+    attn_stream_fwd_body<HD, false>(a, nqc, DropParams{});
+}
+template <int HD>
+__global__ __launch_bounds__(NW * 64, 2) void attn_stream_fwd_drop_kernel(wj_attn_fwd_args a, int nqc, DropParams d) {
+    attn_stream_fwd_body<HD, true>(a, nqc, d);
 }
 
 // ------------------------------------------------------------------------------------------------ backward
 // p = exp(s * scale - lse) is recomputed per block from the stored lse; masked and padding keys carry kvalid = -inf INTO the exponent and
 // padding query rows carry lse = +inf, so no product of 0 with an overflowed exp can arise (see the note in attention_pieces.h).
-template <int HD>
-__global__ __launch_bounds__(NW * 64, 2) void attn_stream_bwd_kernel(wj_attn_bwd_args a) {
+template <int HD, bool DROP>
+__device__ __forceinline__ void attn_stream_bwd_body(const wj_attn_bwd_args& a, const DropParams& d) {
     constexpr int RS = Img<HD>::RS, KS = HD / 32, DT = HD / 16;
     using Form = BwdForm<true, true, false>;
+    using DM = std::conditional_t<DROP, DropBits, NoDrop>;
     __shared__ __attribute__((aligned(16))) char img0[KB * RS];   // phase A: K block      phase B: Q block
     __shared__ __attribute__((aligned(16))) char img1[KB * RS];   // phase A: V block      phase B: dO block
     __shared__ __attribute__((aligned(16))) float lse_s[T_MAX];   // lse * log2 e (+inf for rows >= T)
@@ -170,6 +190,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_stream_bwd_kernel(wj_attn_bwd
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
     const long ld = sv.ld;
     const bf16_t *qkv = sv.qkv, *dO = sv.dO;
+    const uint64_t bh = (uint64_t)sv.b * sv.H + sv.h;            // (DROP: the mask's sequence and head)
 
     BlockRegs<HD> nxt;
     nxt.template load<true>(qkv + D, ld, qkv + 2 * D, ld, 0, T);
@@ -201,7 +222,10 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_stream_bwd_kernel(wj_attn_bwd
             const float my_lse = lse_s[qt * 16 + i], my_delta = delta[qt * 16 + i];
 #pragma unroll
             for (int c = 0; c < KB / 32; ++c) {
-                const bf16x8 dsf = phase_a_pair<HD, Form>(img0, img1, c, KB / 16, qf, dof, kvalid + kb * KB, my_lse, my_delta, scale, scale2, lane);
+                DM dm;
+                // queries on the lane, the pair's eight keys on the accumulator rows: the forward's group, one generator call
+                if constexpr (DROP) dm = DropBits{drop_keep_bits(d, drop_attn_group(bh, qt * 16 + i, kb * (KB / 32) + c, g)), d.scale};
+                const bf16x8 dsf = phase_a_pair<HD, Form, DM>(img0, img1, c, KB / 16, qf, dof, kvalid + kb * KB, my_lse, my_delta, scale, scale2, lane, dm);
 #pragma unroll
                 for (int dt = 0; dt < DT; ++dt)
                     dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tr_frag<HD>(img0, c, dt * 16, lane), dsf, dq[dt], 0, 0, 0);
@@ -237,13 +261,30 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_stream_bwd_kernel(wj_attn_bwd
 #pragma unroll
             for (int c = 0; c < KB / 32; ++c) {
                 bf16x8 pf, dsf;
-                phase_b_pair<HD, Form>(img0, img1, c, KB / 16, kf, vf, lse_s + qb * KB, delta + qb * KB, my_kv, scale, scale2, lane, pf, dsf);
+                DM dm;
+                if constexpr (DROP) {
+                    // keys on the lane, the pair's eight QUERIES on the accumulator rows: eight groups, one draw of each (the key's)
+                    const int k = kt * 16 + i, kg_c = k >> 5, kg_g = (k & 15) >> 2, j = drop_attn_draw(k);
+                    uint32_t bits = 0;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const int q = qb * KB + c * 32 + (e >> 2) * 16 + 4 * g + (e & 3);
+                        bits |= (uint32_t)(drop_draw(drop_draws(d, drop_attn_group(bh, q, kg_c, kg_g)), j) >= d.thr) << e;
+                    }
+                    dm = DropBits{bits, d.scale};
+                }
+                phase_b_pair<HD, Form, DM>(img0, img1, c, KB / 16, kf, vf, lse_s + qb * KB, delta + qb * KB, my_kv, scale, scale2, lane, pf, dsf, dm);
+                if constexpr (DROP) pf = dm.mask_p(pf);      // dV += (P o m)^T dO; the scale goes once onto dV below
 #pragma unroll
                 for (int dt = 0; dt < DT; ++dt) {
                     dv[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tr_frag<HD>(img1, c, dt * 16, lane), pf, dv[dt], 0, 0, 0);
                     dk[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tr_frag<HD>(img0, c, dt * 16, lane), dsf, dk[dt], 0, 0, 0);
                 }
             }
+        }
+        if constexpr (DROP) {
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) dv[dt] *= d.scale;
         }
         store_tile<false>(sv.dqkv + D, ld, kt * 16 + i, T, dk, csk, g);
         store_tile<false>(sv.dqkv + 2 * D, ld, kt * 16 + i, T, dv, csv, g);
@@ -255,6 +296,14 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_stream_bwd_kernel(wj_attn_bwd
         // the (b, h) slice of this sequence's partial row, the waves added in wave order in both modes
         dbias_store<HD, HD, NW, true>(bsum, a.dbias_ws, sv, NW * 64);
     }
+}
+template <int HD>
+__global__ __launch_bounds__(NW * 64, 2) void attn_stream_bwd_kernel(wj_attn_bwd_args a) {
+    attn_stream_bwd_body<HD, false>(a, DropParams{});
+}
+template <int HD>
+__global__ __launch_bounds__(NW * 64, 2) void attn_stream_bwd_drop_kernel(wj_attn_bwd_args a, DropParams d) {
+    attn_stream_bwd_body<HD, true>(a, d);
 }
 
 }  // namespace
@@ -286,3 +335,43 @@ extern "C" int wj_attn_stream_bwd(const wj_attn_bwd_args* a, void* stream) {
     WJ_CHECK_LAUNCH();
     return WJ_OK;
 }
+
+#ifdef WJ_DROPOUT_LIB
+extern "C" WJ_DROPOUT_EXPORT int wj_attn_stream_fwd_drop(const wj_attn_fwd_drop_args* ad, void* stream) {
+    WJ_CLEAR_STALE_ERROR();
+    if (!ad) return WJ_ERR_ARG;
+    const wj_attn_fwd_args* a = &ad->attn;
+    const int rc = attn_check_args(a, AttnLimits{T_MAX, 0});
+    if (rc != WJ_OK) return rc;
+    DropParams d;
+    if (!drop_params(ad->drop, d)) return WJ_ERR_ARG;
+    const int nqc = (a->T + QC - 1) / QC;
+    if ((long)a->B * a->H * nqc > 0x7fffffffL) return WJ_ERR_ARG;
+    dim3 grid(a->B * a->H * nqc);
+    hipStream_t st = (hipStream_t)stream;
+    if (a->hd == 64) hipLaunchKernelGGL(attn_stream_fwd_drop_kernel<64>, grid, dim3(NW * 64), 0, st, *a, nqc, d);
+    else hipLaunchKernelGGL(attn_stream_fwd_drop_kernel<32>, grid, dim3(NW * 64), 0, st, *a, nqc, d);
+    WJ_CHECK_LAUNCH();
+    return WJ_OK;
+}
+
+int64_t wj_attn_bwd_drop_ws_bytes(const wj_attn_bwd_drop_args* a) { return a->attn.B * attn_dbias_row(&a->attn) * 4; }
+
+extern "C" WJ_DROPOUT_EXPORT int wj_attn_stream_bwd_drop(const wj_attn_bwd_drop_args* ad, void* stream) {
+    WJ_CLEAR_STALE_ERROR();
+    if (!ad) return WJ_ERR_ARG;
+    const wj_attn_bwd_args* a = &ad->attn;
+    int rc = attn_check_args(a, AttnLimits{T_MAX, 0});
+    if (rc != WJ_OK) return rc;
+    DropParams d;
+    if (!drop_params(ad->drop, d)) return WJ_ERR_ARG;
+    dim3 grid(a->B * a->H);
+    hipStream_t st = (hipStream_t)stream;
+    if (a->hd == 64) hipLaunchKernelGGL(attn_stream_bwd_drop_kernel<64>, grid, dim3(NW * 64), 0, st, *a, d);
+    else hipLaunchKernelGGL(attn_stream_bwd_drop_kernel<32>, grid, dim3(NW * 64), 0, st, *a, d);
+    rc = attn_fold_dbias(a, stream);
+    if (rc != WJ_OK) return rc;
+    WJ_CHECK_LAUNCH();
+    return WJ_OK;
+}
+#endif

@@ -4,6 +4,7 @@
 // workgroup.  Every piece of arithmetic below exists once; the kernels differ in which operands they read and write.
 #include "common.h"
 #include "../../include/wavjepa_hip.h"
+#include "dropout_host.h"
 
 namespace {
 
@@ -32,6 +33,22 @@ __device__ __forceinline__ f32x4 load4_sum(const void* x, long xr, bool x_is_bf1
     f32x4 s = load4(x, xr, D, col, x_is_bf16);
     if (r) s += load4(r, m, D, col, true);
     return s;
+}
+
+// the four keep bits of chunk (m, col) of a [M][D] tensor under dropout: group m * D / 8 + col / 8, draws col % 8 .. + 3 (the two
+// chunks of a group are held by neighbouring lanes, each of which runs the generator: 60 VALU operations against a 16-byte row access)
+__device__ __forceinline__ uint32_t drop_bits4(const DropParams& d, long m, int D, int col) {
+    return (drop_keep_bits(d, (uint64_t)(m * (D >> 3) + (col >> 3))) >> (col & 4)) & 15u;
+}
+// v o m * scale
+__device__ __forceinline__ f32x4 drop4(f32x4 v, uint32_t keep, float scale) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = (keep >> e) & 1u ? v[e] * scale : 0.f;
+    return v;
+}
+// x (f32 or bf16, row xr) + the bf16 addend r (row m) under dropout
+__device__ __forceinline__ f32x4 load4_sum_drop(const void* x, long xr, bool x_is_bf16, const void* r, long m, int D, int col, const DropParams& d) {
+    return load4(x, xr, D, col, x_is_bf16) + drop4(load4(r, m, D, col, true), drop_bits4(d, m, D, col), d.scale);
 }
 
 __device__ __forceinline__ bf16x4 round4(f32x4 v) { return bf16x4{f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])}; }
@@ -149,8 +166,9 @@ __device__ __forceinline__ f32x4 normalise4(f32x4 s, float mean, float rstd, f32
     return y;
 }
 
-template <int V, int LPR>
-__global__ __launch_bounds__(256) void ln_fwd_kernel(wj_ln_fwd_args a) {
+// DROP: the addend r goes through dropout (wj_layernorm_fwd_drop; no fp8 output there)
+template <int V, int LPR, bool DROP>
+__device__ __forceinline__ void ln_fwd_body(const wj_ln_fwd_args& a, const DropParams& d) {
     const Lanes<V, LPR> L(a.D);
     const int D = a.D;
     f32x4 gam[V], bet[V];
@@ -164,7 +182,8 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(wj_ln_fwd_args a) {
         float sum = 0.f;
         L.zero(s);
         LN_FOR_CHUNKS(L, j, col) {
-            s[j] = load4_sum(a.x, xr, a.x_is_bf16, a.r, m, D, col);
+            if constexpr (DROP) s[j] = load4_sum_drop(a.x, xr, a.x_is_bf16, a.r, m, D, col, d);
+            else s[j] = load4_sum(a.x, xr, a.x_is_bf16, a.r, m, D, col);
             sum += s[j][0] + s[j][1] + s[j][2] + s[j][3];
         }
         float mean, rstd;
@@ -179,7 +198,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(wj_ln_fwd_args a) {
             }
             const bf16x4 o = round4(y);
             store4(a.y_f32, m, a.y_bf16, m, D, col, y, o);
-            if (a.y_fp8) {
+            if (!DROP && a.y_fp8) {
                 // MX fp8 of bf16(y), as wj_quantize_mxfp8 defines it: a 32-column block = 8 consecutive lanes of this chunk, the
                 // four block scales of a 128-column K tile = 32 lanes -> one dword [kt][row] (D % 128 == 0: every lane of a
                 // block / K tile is live together, so the shuffles below are uniform)
@@ -212,6 +231,14 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(wj_ln_fwd_args a) {
         add_row_to_group(gs1, gs2, r1, r2);
     }
     if (a.group_stats) store_group_stats(a.group_stats, gs1, gs2);
+}
+template <int V, int LPR>
+__global__ __launch_bounds__(256) void ln_fwd_kernel(wj_ln_fwd_args a) {
+    ln_fwd_body<V, LPR, false>(a, DropParams{});
+}
+template <int V, int LPR>
+__global__ __launch_bounds__(256) void ln_fwd_drop_kernel(wj_ln_fwd_args a, DropParams d) {
+    ln_fwd_body<V, LPR, true>(a, d);
 }
 
 // The LEAN form (wj_ln_fwd_args.workgroups > 0): the same pieces in the same order -- bit-identical outputs -- from a kernel that fits
@@ -351,7 +378,9 @@ __device__ __forceinline__ void ln_bwd_body(const Ops& ops) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) ds[e] = rstd[u] * (dy[u][j][e] * gam[j][e] - k1 - xh[u][j][e] * k2);
                 if constexpr (Ops::adds_residual) ds = ops.residual(m, col) + ds;
-                const bf16x4 dsb = round4(ds);
+                bf16x4 dsb;
+                if constexpr (Ops::masks_out) dsb = round4(ops.mask_out(m, col, ds));     // (ds_f32 stays the residual's gradient)
+                else dsb = round4(ds);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     dg[j][e] += dy[u][j][e] * xh[u][j][e];
@@ -400,7 +429,7 @@ __device__ __forceinline__ void ln_bwd_body(const Ops& ops) {
 
 // post-norm: x-hat from x (+ r) through the input row remap, dy (+ dy2), ds_bf16 through the output row remap
 struct PostNormBwd {
-    static constexpr bool adds_residual = false;
+    static constexpr bool adds_residual = false, masks_out = false;
     const wj_ln_bwd_args a;
     __device__ __forceinline__ long src_row(int m) const {
         return remap_row(m, a.in_seg, a.in_valid, a.chan, a.chan > 1 ? a.M / (a.chan * a.in_valid) : 0);
@@ -419,12 +448,32 @@ __global__ __launch_bounds__(BWD_THREADS) void ln_bwd_kernel(wj_ln_bwd_args a) {
     ln_bwd_body<V, LPR>(PostNormBwd{a});
 }
 
+// post-norm under dropout of the addend r (wj_layernorm_bwd_drop): x-hat from x + r o m * scale; ds_bf16 = bf16(ds o m * scale) is the
+// gradient of r.  The mask is regenerated in the load and in the store phase: held across the reductions it would cost registers.
+struct PostNormDropBwd {
+    static constexpr bool adds_residual = false, masks_out = true;
+    const wj_ln_bwd_args a;
+    const DropParams d;
+    __device__ __forceinline__ long src_row(int m) const { return PostNormBwd{a}.src_row(m); }
+    __device__ __forceinline__ long out_row(int m) const { return PostNormBwd{a}.out_row(m); }
+    __device__ __forceinline__ void load(int m, long xr, int col, f32x4& x, f32x4& dy) const {
+        x = load4_sum_drop(a.x, xr, a.x_is_bf16, a.r, m, a.D, col, d);
+        dy = load4(a.dy, m, a.D, col, false);
+        if (a.dy2) dy += load4(a.dy2, m, a.D, col, a.dy2_is_bf16);
+    }
+    __device__ __forceinline__ f32x4 mask_out(int m, int col, f32x4 ds) const { return drop4(ds, drop_bits4(d, m, a.D, col), d.scale); }
+};
+template <int V, int LPR>
+__global__ __launch_bounds__(BWD_THREADS) void ln_bwd_drop_kernel(wj_ln_bwd_args a, DropParams d) {
+    ln_bwd_body<V, LPR>(PostNormDropBwd{a, d});
+}
+
 // pre-norm: ds = (dres) + LN-backward(dy; s, gamma, mean, rstd).  dres is the gradient that bypasses the norm on the residual path (NULL
 // behind a stack's final norm), dy the grad_input of the branch's first Linear (bf16 under autocast) or an f32 gradient.  One operand
 // fewer than post-norm (the stream s was stored, there is no r to add back).  ds_bf16 = bf16(ds) is the dY of the PREVIOUS branch's last
 // Linear and dbias its bias gradient.
 struct PreNormBwd {
-    static constexpr bool adds_residual = true;
+    static constexpr bool adds_residual = true, masks_out = false;
     const wj_ln_pre_bwd_args a;
     __device__ __forceinline__ long src_row(int m) const { return m; }
     __device__ __forceinline__ long out_row(int m) const { return m; }
@@ -643,14 +692,26 @@ int64_t wj_colsum_bf16_ws_bytes(const wj_colsum_args* a) {
     return (int64_t)gy * a->N * 4;
 }
 
-extern "C" int wj_layernorm_fwd(const wj_ln_fwd_args* a, void* stream) {
-    WJ_CLEAR_STALE_ERROR();
-    if (!a || !a->x || !a->gamma || !a->beta) return WJ_ERR_ARG;
+static int ln_fwd_check(const wj_ln_fwd_args* a) {
+    if (!a->x || !a->gamma || !a->beta) return WJ_ERR_ARG;
     if (a->M <= 0 || a->D <= 0 || (a->D & 3) || a->D > 256 * MAXV) return WJ_ERR_ARG;
     if (a->in_seg > 0 && a->in_valid <= 0) return WJ_ERR_ARG;
     if (a->in_chan > 1 && (a->in_seg <= 0 || a->M % (a->in_chan * a->in_valid))) return WJ_ERR_ARG;
     if (a->group_stats && a->group_rows <= 0) return WJ_ERR_ARG;
     if (a->y_fp8 && (!a->y_fp8_scales || (a->D % 128) || a->ld_fp8_scale < a->M)) return WJ_ERR_ARG;
+    return WJ_OK;
+}
+static int ln_bwd_check(const wj_ln_bwd_args* a) {
+    if (!a->dy || !a->x || !a->gamma || !a->mean || !a->rstd) return WJ_ERR_ARG;
+    if (a->M <= 0 || a->D <= 0 || (a->D & 3) || a->D > 256 * MAXV) return WJ_ERR_ARG;
+    if ((a->in_seg > 0 && a->in_valid <= 0) || (a->out_seg > 0 && a->out_valid <= 0)) return WJ_ERR_ARG;
+    if (a->chan > 1 && ((a->in_seg > 0 && a->M % (a->chan * a->in_valid)) || (a->out_seg > 0 && a->M % (a->chan * a->out_valid)))) return WJ_ERR_ARG;
+    return WJ_OK;
+}
+
+extern "C" int wj_layernorm_fwd(const wj_ln_fwd_args* a, void* stream) {
+    WJ_CLEAR_STALE_ERROR();
+    if (!a || ln_fwd_check(a) != WJ_OK) return WJ_ERR_ARG;
     const int grid = ln_fwd_grid(a->M, a->D, a->group_stats != nullptr, a->group_rows);
     hipStream_t s = (hipStream_t)stream;
     // the lean form on a capped grid (see ln_fwd_lean_kernel): same bits, a kernel that shares a CU with a persistent GEMM
@@ -664,6 +725,24 @@ extern "C" int wj_layernorm_fwd(const wj_ln_fwd_args* a, void* stream) {
     return WJ_OK;
 }
 
+#ifdef WJ_DROPOUT_LIB
+extern "C" WJ_DROPOUT_EXPORT int wj_layernorm_fwd_drop(const wj_ln_fwd_drop_args* ad, void* stream) {
+    WJ_CLEAR_STALE_ERROR();
+    if (!ad) return WJ_ERR_ARG;
+    const wj_ln_fwd_args* a = &ad->ln;
+    DropParams d;
+    if (ln_fwd_check(a) != WJ_OK || !a->r || (a->D & 7) || a->y_fp8 || !drop_params(ad->drop, d)) return WJ_ERR_ARG;
+    const int grid = ln_fwd_grid(a->M, a->D, a->group_stats != nullptr, a->group_rows);
+    hipStream_t s = (hipStream_t)stream;
+    ln_dispatch(a->D, [&](auto shape) {
+        using S = decltype(shape);
+        hipLaunchKernelGGL((ln_fwd_drop_kernel<S::V, S::LPR>), dim3(grid), dim3(256), 0, s, *a, d);
+    });
+    WJ_CHECK_LAUNCH();
+    return WJ_OK;
+}
+#endif
+
 extern "C" int wj_ln_bwd_partial_rows(int M, int D) {
     if (M <= 0 || D <= 0) return -1;
     return ln_bwd_grid(M, D);
@@ -672,6 +751,9 @@ extern "C" int wj_ln_bwd_partial_rows(int M, int D) {
 static int64_t ln_bwd_ws_bytes(int D) { return (int64_t)LN_BWD_MAX_PARTIAL_ROWS * 3 * D * 4; }
 int64_t wj_ln_bwd_ws_bytes(const wj_ln_bwd_args* a) { return ln_bwd_ws_bytes(a->D); }
 int64_t wj_ln_pre_bwd_ws_bytes(const wj_ln_pre_bwd_args* a) { return ln_bwd_ws_bytes(a->D); }
+#ifdef WJ_DROPOUT_LIB
+int64_t wj_ln_bwd_drop_ws_bytes(const wj_ln_bwd_drop_args* a) { return ln_bwd_ws_bytes(a->ln.D); }
+#endif
 
 extern "C" int wj_colsum_f32_group(const wj_colsum_group_args* a, void* stream) {
     WJ_CLEAR_STALE_ERROR();
@@ -688,10 +770,7 @@ extern "C" int wj_colsum_f32_group(const wj_colsum_group_args* a, void* stream) 
 
 extern "C" int wj_layernorm_bwd(const wj_ln_bwd_args* a, void* stream) {
     WJ_CLEAR_STALE_ERROR();
-    if (!a || !a->dy || !a->x || !a->gamma || !a->mean || !a->rstd) return WJ_ERR_ARG;
-    if (a->M <= 0 || a->D <= 0 || (a->D & 3) || a->D > 256 * MAXV) return WJ_ERR_ARG;
-    if ((a->in_seg > 0 && a->in_valid <= 0) || (a->out_seg > 0 && a->out_valid <= 0)) return WJ_ERR_ARG;
-    if (a->chan > 1 && ((a->in_seg > 0 && a->M % (a->chan * a->in_valid)) || (a->out_seg > 0 && a->M % (a->chan * a->out_valid)))) return WJ_ERR_ARG;
+    if (!a || ln_bwd_check(a) != WJ_OK) return WJ_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     ln_bwd_launch(a, s, [&](auto shape, dim3 g, dim3 b) {
         using S = decltype(shape);
@@ -700,6 +779,23 @@ extern "C" int wj_layernorm_bwd(const wj_ln_bwd_args* a, void* stream) {
     WJ_CHECK_LAUNCH();
     return WJ_OK;
 }
+
+#ifdef WJ_DROPOUT_LIB
+extern "C" WJ_DROPOUT_EXPORT int wj_layernorm_bwd_drop(const wj_ln_bwd_drop_args* ad, void* stream) {
+    WJ_CLEAR_STALE_ERROR();
+    if (!ad) return WJ_ERR_ARG;
+    const wj_ln_bwd_args* a = &ad->ln;
+    DropParams d;
+    if (ln_bwd_check(a) != WJ_OK || !a->r || (a->D & 7) || !drop_params(ad->drop, d)) return WJ_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    ln_bwd_launch(a, s, [&](auto shape, dim3 g, dim3 b) {
+        using S = decltype(shape);
+        hipLaunchKernelGGL((ln_bwd_drop_kernel<S::V, S::LPR>), g, b, 0, s, *a, d);
+    });
+    WJ_CHECK_LAUNCH();
+    return WJ_OK;
+}
+#endif
 
 extern "C" int wj_layernorm_pre_fwd(const wj_ln_pre_fwd_args* a, void* stream) {
     if (!a || !a->x || !a->gamma || !a->beta) return WJ_ERR_ARG;

@@ -123,6 +123,9 @@ class Denoiser(_ModuleBase):
             enc_c.update(num_layers=24)
         self.n_encoder_heads = enc_l["nhead"]
         self.encoder_embedding_dim = enc_l["d_model"]
+        if enc_l.get("dropout", 0.0):
+            raise NotImplementedError(f"dropout={enc_l.get('dropout')} in the Denoiser stage: its engine issues no dropout launches "
+                                      "(dropout is a JEPA pre-training option)")
         if enc_l.get("norm_first", False):
             raise NotImplementedError("the Denoiser stage runs post-norm stacks only (norm_first=False); pre-norm is a JEPA pre-training option")
         self.encoder = TransformerStack(enc_l, enc_c["num_layers"])

@@ -45,6 +45,8 @@ class EngineConfig:
     loss_kind: str = "mse"         # per-element loss of the masked objective: "mse" | "l1" | "smooth_l1" | "huber" (ops.masked_loss)
     loss_beta: float = 1.0         # smooth-L1's beta / Huber's delta
     recompute: bool = False        # activation recomputation in the student and the predictor (JEPA use_gradient_checkpointing; _alloc_ring)
+    dropout_enc: float = 0.0       # dropout rate of the student's layers in a training-mode forward (never the teacher's); JepaEngine._drop
+    dropout_dec: float = 0.0       # ... of the predictor's
 
 
 @dataclass
@@ -287,6 +289,20 @@ class JepaEngine:
                 if layers > 0 and hd not in (32, 64):
                     raise NotImplementedError(f"{self.T} tokens per clip with {hd}-wide {what} heads: attention beyond "
                                               f"{ops.ATTN_WHOLE_T_MAX} tokens (wj_attn_stream_fwd / _bwd) takes head widths 32 and 64")
+        # dropout (nn.TransformerEncoderLayer's four sites) in the student / predictor of a training-mode forward: the _drop entries,
+        # whose masks are a function of (drop_seed, drop_call, stack, layer, site, element) -- nothing is stored, the backward and the
+        # second forward of recompute mode pass the same tail again.  The attention of such a stack runs the streamed family at any length.
+        for what, p, pre, hd, layers in (("encoder", cfg.dropout_enc, cfg.norm_first_enc, cfg.d_enc // cfg.h_enc, cfg.l_enc),
+                                         ("decoder", cfg.dropout_dec, cfg.norm_first_dec, cfg.d_dec // cfg.h_dec, cfg.l_dec)):
+            if not (0.0 <= float(p) < 1.0):
+                raise ValueError(f"{what} dropout must lie in [0, 1), not {p}")
+            if p > 0 and pre:
+                raise NotImplementedError(f"{what}: dropout={p} with norm_first=True: the dropout kernels cover post-norm layers only")
+            if p > 0 and layers > 0 and hd not in (32, 64):
+                raise NotImplementedError(f"{what}: dropout={p} with {hd}-wide heads: attention dropout runs in the streamed kernels "
+                                          "(wj_attn_stream_fwd_drop / _bwd_drop), which take head widths 32 and 64")
+        self.drop_seed, self.drop_call = 0, 0
+        self._drop_now: Dict[str, float] = {}          # stack -> rate, for the forward being run and its backward ({}: no dropout)
         self.N = 0
         self.G = 0              # target groups per clip of the arena (taken from the mask plan)
         # second HIP stream: work that is off the critical path (teacher forward; all weight-gradient GEMMs of the
@@ -463,6 +479,9 @@ class JepaEngine:
                      if self._row_form_pays(M, n_out) or (pairs and self._pair_pays(M, n_out, k_in)))
 
     def _check_fp8(self) -> None:
+        if self.fp8 and (self.cfg.dropout_enc > 0 or self.cfg.dropout_dec > 0):
+            raise RuntimeError("fp8 mode (WJ_FP8=1 / engine.fp8) is not combined with dropout > 0: the fp8 producers (LayerNorm and GELU "
+                               "epilogues that emit the next GEMM's operand) have no dropout forms")
         if self.fp8 and self.recompute:
             # the fp8 forward hands a layer's output to the next layer in the stack's fp8 scratch as well; a second forward that starts
             # from a kept bf16 output would quantise it in another launch order, and nothing pins that to the first pass's bits
@@ -685,11 +704,22 @@ class JepaEngine:
 
     # ------------------------------------------------------------------------------------------------ building blocks
     # ---- pieces of a layer that the post-norm and the pre-norm layout share
+    def _drop(self, stack: str, layer: int, site: int):
+        """The dropout tail (ops.drop_args) of one site of one layer, or None when the stack runs without dropout in this forward."""
+        p = self._drop_now.get(stack, 0.0)
+        if not p:
+            return None
+        return ops.drop_args(self.drop_seed, self.drop_call, p, site=site, layer=layer, stack=ops.DROP_STACK[stack])
+
     def _attn_fwd(self, a: _Acts, D: int, H: int, B: int, mask: Optional[torch.Tensor], seq: Optional[Tuple[torch.Tensor, int]],
-                  save: bool) -> None:
-        """a.o = attention(a.qkv): packed sequences (`seq`) or T tokens per sequence under a key mask; `save` keeps the softmax statistics."""
+                  save: bool, drop=None) -> None:
+        """a.o = attention(a.qkv): packed sequences (`seq`) or T tokens per sequence under a key mask; `save` keeps the softmax statistics.
+        drop: dropout on the probabilities (the streamed family, at any length)."""
         lse = a.lse if save else None
-        if seq is not None:
+        if drop is not None:
+            kw = dict(T=seq[1], seq_off=seq[0]) if seq is not None else dict(T=self.T, key_mask=mask)
+            ops.attn_stream_fwd_drop(a.qkv, a.o, B=B, H=H, hd=D // H, lse=lse, drop=drop, **kw)
+        elif seq is not None:
             fwd = getattr(ops, ops.attn_entries(seq[1])[0][3:])      # by the length bound of THIS call: a short ragged stack keeps the whole-image kernels
             fwd(a.qkv, a.o, B=B, T=seq[1], H=H, hd=D // H, seq_off=seq[0], lse=lse)
         else:
@@ -703,13 +733,17 @@ class JepaEngine:
         ops.mask_gather_rows(x, rows, self.tail_x, n_rows=M, D=D, elem_bytes=4)
         return self.tail_o, self.tail_x, M
 
-    def _mlp_fwd(self, stack: str, w: _Layer, a: _Acts, xb: torch.Tensor, M: int, D: int, save: bool, out: bool = True) -> None:
+    def _mlp_fwd(self, stack: str, w: _Layer, a: _Acts, xb: torch.Tensor, M: int, D: int, save: bool, out: bool = True, drop=None) -> None:
         """a.f = linear2(gelu(linear1(xb))) in bf16; `save` also keeps gelu'(linear1 output) in a.h for the backward.
-        out=False: linear1 only (a.g and a.h), for a second forward whose a.f was kept from the first."""
+        out=False: linear1 only (a.g and a.h), for a second forward whose a.f was kept from the first.
+        drop: dropout behind the GELU, one pass over a.g and a.h with the same mask -- linear2's weight gradient (reads a.g) and the
+        MUL_GELU_GRAD dgrad epilogue (reads a.h) are then correct as they stand."""
         if save:
             self._linear_fwd(stack, xb, w.w1, a.h, M=M, N=4 * D, K=D, bias=w.b1, epilogue=ops.EPI_BIAS_GELU2, C2=a.g)
         else:
             self._linear_fwd(stack, xb, w.w1, a.g, M=M, N=4 * D, K=D, bias=w.b1, epilogue=ops.EPI_BIAS_GELU)
+        if drop is not None:
+            ops.dropout_rows(a.g, a.h if save else None, M=M, N=4 * D, drop=drop)
         if out:
             self._linear_fwd(stack, a.g, w.w2, a.f, M=M, N=D, K=4 * D, bias=w.b2)
 
@@ -717,7 +751,7 @@ class JepaEngine:
                    mask: Optional[torch.Tensor], seq: Optional[Tuple[torch.Tensor, int]] = None, save: bool = True,
                    x2_out: Optional[torch.Tensor] = None, x2_stats: Optional[torch.Tensor] = None,
                    sub: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None, stack: str = "enc", xq_ready: bool = False,
-                   redo: bool = False) -> bool:
+                   redo: bool = False, li: int = 0) -> bool:
         """Post-norm layer: x1 = LN1(x + out_proj(attn(in_proj(x)))); x2 = LN2(x1 + linear2(gelu(linear1(x1)))).
         `seq` = (offsets int32 [B+1], longest sequence) selects the ragged form: M packed rows, no key mask.
         save=False (teacher / inference): nothing is kept for a backward (no gelu' output, no softmax statistics).
@@ -725,8 +759,11 @@ class JepaEngine:
         context rows are keys / values there and nothing reads their outputs).
         xq_ready / return value (fp8 mode): the stack's small fp8 buffer already / now holds this layer's input / output.
         redo (recompute mode, in front of the layer's backward): the same launches once more; x2 / x2b were kept from the first pass --
-        the side stream may be reading x2b -- so norm2 writes its row statistics only."""
+        the side stream may be reading x2b -- so norm2 writes its row statistics only.
+        li: the layer's index in its stack (the dropout masks' layer field)."""
         eps = self.cfg.ln_eps
+        if self._drop_now.get(stack):
+            return self._layer_fwd_drop(w, a, x_in, xb_in, M, D, H, B, mask, seq, sub, stack, redo, li)
         # fp8 mode with an eligible width (K = D a multiple of 256): the GEMM inputs are produced directly in the MX fp8 operand
         # format by their producers -- LayerNorm (x1 for linear1, x2 for the next layer's in_proj) and linear1's GELU epilogue
         # (for linear2); only the attention output and the very first layer input go through wj_quantize_mxfp8
@@ -768,6 +805,25 @@ class JepaEngine:
                           mean=a.m2, rstd=a.r2, group_stats=x2_stats, group_rows=self.T if x2_stats is not None else 0,
                           workgroups=lean if x2_stats is None else 0, **f8_out)
         return f8 and sub is None              # the small fp8 buffer now holds x2 for the next layer of this stack
+
+    def _layer_fwd_drop(self, w: _Layer, a: _Acts, x_in, xb_in, M: int, D: int, H: int, B: int, mask, seq, sub, stack: str, redo: bool,
+                        li: int) -> bool:
+        """_layer_fwd of a student / predictor layer under dropout (always saving, never fp8): the same GEMMs; the attention and the two
+        residual LayerNorms in their _drop forms, and one pass over linear1's outputs."""
+        eps = self.cfg.ln_eps
+        self._linear_fwd(stack, xb_in, w.wqkv, a.qkv, M=M, N=3 * D, K=D, bias=w.bqkv)
+        self._attn_fwd(a, D, H, B, mask, seq, True, drop=self._drop(stack, li, ops.DROP_SITE_ATTN))
+        o_in = a.o
+        if sub is not None:
+            o_in, x_in, M = self._tail_gather(a, x_in, sub, D)
+        self._linear_fwd(stack, o_in, w.wo, a.p, M=M, N=D, K=D, bias=w.bo)
+        ops.layernorm_fwd_drop(x_in, w.g1, w.be1, M=M, D=D, eps=eps, r=a.p, y_f32=a.x1, y_bf16=a.x1b, mean=a.m1, rstd=a.r1,
+                               drop=self._drop(stack, li, ops.DROP_SITE_RES1))
+        self._mlp_fwd(stack, w, a, a.x1b, M, D, True, drop=self._drop(stack, li, ops.DROP_SITE_FFN))
+        y2 = (None, None) if redo else (a.x2, a.x2b)
+        ops.layernorm_fwd_drop(a.x1, w.g2, w.be2, M=M, D=D, eps=eps, r=a.f, y_f32=y2[0], y_bf16=y2[1], mean=a.m2, rstd=a.r2,
+                               drop=self._drop(stack, li, ops.DROP_SITE_RES2))
+        return False
 
     def _layer_fwd_pre(self, w: _Layer, a: _Acts, x_in, r_in, M: int, D: int, H: int, B: int, mask: Optional[torch.Tensor],
                        seq: Optional[Tuple[torch.Tensor, int]] = None, save: bool = True, s_out: Optional[torch.Tensor] = None,
@@ -933,16 +989,19 @@ class JepaEngine:
             self._fold_now(ws, N, rows, N, o0, o1, o2, n_each)
 
     def _ln_bwd(self, dy, x, gamma, mean, rstd, *, M: int, D: int, dgamma=None, dbeta=None, dbias=None, defer: bool = True,
-                workspace=None, **kw) -> None:
+                workspace=None, drop=None, **kw) -> None:
         """wj_layernorm_bwd; its dgamma / dbeta / dbias partials are folded later, together with the neighbours' (see _flush_folds), or
         in deterministic mode at once -- never by the kernel's own atomics then.  workspace: what an undeferred caller hands the
         kernel's own reduction (a deferring one: red_ws)."""
         form, ws = self._fold_form(3 * D, bool(dgamma or dbeta or dbias), defer)
+        ln_bwd = ops.layernorm_bwd
+        if drop is not None:         # the addend r went through dropout: wj_layernorm_bwd_drop, the same partial rows
+            ln_bwd, kw = ops.layernorm_bwd_drop, dict(kw, drop=drop)
         if form == "own":
-            ops.layernorm_bwd(dy, x, gamma, mean, rstd, M=M, D=D, dgamma=dgamma, dbeta=dbeta, dbias=dbias,
-                              workspace=self.red_ws if defer else workspace, **kw)
+            ln_bwd(dy, x, gamma, mean, rstd, M=M, D=D, dgamma=dgamma, dbeta=dbeta, dbias=dbias,
+                   workspace=self.red_ws if defer else workspace, **kw)
         else:
-            ops.layernorm_bwd(dy, x, gamma, mean, rstd, M=M, D=D, workspace=ws, **kw)
+            ln_bwd(dy, x, gamma, mean, rstd, M=M, D=D, workspace=ws, **kw)
             self._fold(form, ws, 3 * D, ops.ln_bwd_partial_rows(M, D), dgamma, dbeta, dbias, D)
 
     def _ln_bwd_direct(self, dy, x, gamma, mean, rstd, *, M: int, D: int, workspace=None, **kw) -> None:
@@ -960,11 +1019,13 @@ class JepaEngine:
             ops.layernorm_pre_bwd(dy, s, gamma, mean, rstd, M=M, D=D, workspace=ws, **kw)
             self._fold(form, ws, 3 * D, ops.ln_pre_bwd_partial_rows(M, D), dgamma, dbeta, dbias, D)
 
-    def _attn_bwd(self, qkv, out, dout, lse, dqkv, *, B: int, H: int, hd: int, dbias, **kw) -> None:
+    def _attn_bwd(self, qkv, out, dout, lse, dqkv, *, B: int, H: int, hd: int, dbias, drop=None, **kw) -> None:
         """wj_attn_bwd (wj_attn_stream_bwd above 416 tokens, the same arguments and the same [B][3D] partial rows): the in_proj bias partials
         go to a slot, or the kernel folds them itself out of red_ws (in order when deterministic)."""
         D3 = 3 * H * hd
         attn_bwd = getattr(ops, ops.attn_entries(kw["T"])[1][3:])
+        if drop is not None:         # dropout on the probabilities: the streamed family at any length
+            attn_bwd, kw = ops.attn_stream_bwd_drop, dict(kw, drop=drop)
         if self.deterministic:
             kw = dict(kw, deterministic=True)
         form, ws = self._fold_form(D3, bool(dbias))
@@ -1038,7 +1099,7 @@ class JepaEngine:
 
     def _attn_block_bwd(self, w: _Layer, a: _Acts, xb: torch.Tensor, bw: dict, parity: int, M: int, D: int, H: int, B: int,
                         mask: Optional[torch.Tensor], seq: Optional[Tuple[torch.Tensor, int]],
-                        sub: Optional[Tuple[torch.Tensor, torch.Tensor, int]]) -> torch.Tensor:
+                        sub: Optional[Tuple[torch.Tensor, torch.Tensor, int]], drop=None) -> torch.Tensor:
         """d(out_proj output) (bf16, bw["dsb1"][parity]; with `sub`: on the sub-rows) -> d(qkv) over all M rows (bw["dqkv"][parity]);
         xb: the bf16 operand in_proj read.  Returns the fp32 residual gradient over all M rows: bw["ds"], with `sub` scattered into
         bw["dx1"].  The two weight gradients are queued (_wgrads)."""
@@ -1052,9 +1113,9 @@ class JepaEngine:
             ops.unmask_rows_f32(self.tail_do, sub[1], do, M=M, D=D, dst_is_bf16=True)
             ops.unmask_rows_f32(ds, sub[1], dx1, M=M, D=D, src_is_f32=True)       # dx1 is free again: residual gradient
         if seq is not None:
-            self._attn_bwd(a.qkv, a.o, do, a.lse, dqkv, B=B, T=seq[1], H=H, hd=D // H, seq_off=seq[0], dbias=w.gbqkv)
+            self._attn_bwd(a.qkv, a.o, do, a.lse, dqkv, B=B, T=seq[1], H=H, hd=D // H, seq_off=seq[0], dbias=w.gbqkv, drop=drop)
         else:
-            self._attn_bwd(a.qkv, a.o, do, a.lse, dqkv, B=B, T=self.T, H=H, hd=D // H, key_mask=mask, dbias=w.gbqkv)
+            self._attn_bwd(a.qkv, a.o, do, a.lse, dqkv, B=B, T=self.T, H=H, hd=D // H, key_mask=mask, dbias=w.gbqkv, drop=drop)
         bw["pending"] += [(dsb1, o_in, w.gwo, D, D, Ms), (dqkv, xb, w.gwqkv, 3 * D, D, M)]
         return ds_all
 
@@ -1083,7 +1144,8 @@ class JepaEngine:
     def _layer_bwd(self, w: _Layer, a: _Acts, x_in: torch.Tensor, xb_in: torch.Tensor, dy: torch.Tensor, dyb: Optional[torch.Tensor],
                    dx_out: torch.Tensor, M: int, D: int, H: int, B: int, mask: Optional[torch.Tensor], bw: dict, parity: int,
                    seq: Optional[Tuple[torch.Tensor, int]] = None,
-                   sub: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None, flush: bool = True, bottom: bool = False):
+                   sub: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None, flush: bool = True, bottom: bool = False,
+                   stack: str = "enc", li: int = 0):
         """d(x2) = dy (fp32) + dyb (bf16 or None) -> d(x_in), returned as (fp32 part, bf16 part or None, flushed); parameter gradients
         accumulated into the flat gradient buffer.
         The grad_input of linear1 and in_proj is what a bf16 linear returns under autocast -- a bf16 tensor (`dgb` / `dxb`) -- and the
@@ -1091,7 +1153,9 @@ class JepaEngine:
         instead of the 4 + 4 of a read-modify-write fp32 GEMM epilogue.  Only the `bottom` layer of a stack folds the two into one
         fp32 tensor (dx_out), for the consumers below the stack.
         Returns flushed = True when the weight-gradient queue went out (_wgrads: the queued layers' gradients are then final in
-        side-stream order)."""
+        side-stream order).
+        stack, li: which layer this is -- under dropout the two LayerNorm backwards and the attention backward regenerate the forward's
+        masks from them (the FFN site needs nothing: a.g and a.h were stored masked)."""
         ds, dxb, dqkv = bw["ds"], bw["dxb"], bw["dqkv"][parity]
         if not self.recompute:             # (recompute mode: _redo_layer waited for the slot before it wrote the activations)
             self._slot_wait(bw, parity)
@@ -1099,11 +1163,11 @@ class JepaEngine:
         if sub is not None:              # dy holds the sub-rows only; everything up to the attention works on them
             Ms, x_ln1 = sub[2], self.tail_x
         self._ln_bwd(dy, a.x1, w.g2, a.m2, a.r2, M=Ms, D=D, r=a.f, dy2=dyb, dy2_is_bf16=dyb is not None, ds_f32=ds, ds_bf16=bw["dsb2"][parity],
-                     dgamma=w.gg2, dbeta=w.gbe2, dbias=w.gb2)
+                     dgamma=w.gg2, dbeta=w.gbe2, dbias=w.gb2, drop=self._drop(stack, li, ops.DROP_SITE_RES2))
         self._mlp_bwd(w, a, a.x1b, bw, parity, Ms, D)
         self._ln_bwd(ds, x_ln1, w.g1, a.m1, a.r1, M=Ms, D=D, r=a.p, dy2=bw["dgb"], dy2_is_bf16=True, ds_f32=ds, ds_bf16=bw["dsb1"][parity],
-                     dgamma=w.gg1, dbeta=w.gbe1, dbias=w.gbo)      # ds updated in place
-        ds_all = self._attn_block_bwd(w, a, xb_in, bw, parity, M, D, H, B, mask, seq, sub)
+                     dgamma=w.gg1, dbeta=w.gbe1, dbias=w.gbo, drop=self._drop(stack, li, ops.DROP_SITE_RES1))      # ds updated in place
+        ds_all = self._attn_block_bwd(w, a, xb_in, bw, parity, M, D, H, B, mask, seq, sub, drop=self._drop(stack, li, ops.DROP_SITE_ATTN))
         self._wgrads(bw, parity, flush)
         if bottom:
             self._dgrad(dqkv, w, "wqkv", dx_out, M=M, N=D, K=3 * D, epilogue=ops.EPI_ADD_F32, aux=ds_all)
@@ -1173,7 +1237,8 @@ class JepaEngine:
         xq = False
         for i, w in enumerate(layers):
             a = acts[i] if save else self.scratch
-            xq = self._layer_fwd(w, a, x, xb, M, D, H, B, mask, seq, save=save, sub=sub if i == top else None, stack=stack, xq_ready=xq)
+            xq = self._layer_fwd(w, a, x, xb, M, D, H, B, mask, seq, save=save, sub=sub if i == top else None, stack=stack, xq_ready=xq,
+                                 li=i)
             x, xb = a.x2, a.x2b
         ops.layernorm_fwd(x, gamma, beta, M=Mo, D=D, eps=c.norm_eps,
                           workgroups=self.ln_lean_wgs if (lean and self._lean_now and stack in self.ln_lean) else 0, **out)
@@ -1195,7 +1260,7 @@ class JepaEngine:
                 self._layer_fwd_pre(layers[i], acts[i], x, r, M, D, H, B, mask, seq, save=True, sub=sub, stack=stack, redo=True)
             else:
                 x, xb = (x0, xb0) if i == 0 else (acts[i - 1].x2, acts[i - 1].x2b)
-                self._layer_fwd(layers[i], acts[i], x, xb, M, D, H, B, mask, seq, save=True, sub=sub, stack=stack, redo=True)
+                self._layer_fwd(layers[i], acts[i], x, xb, M, D, H, B, mask, seq, save=True, sub=sub, stack=stack, redo=True, li=i)
         finally:
             self._lean_now = lean_was
 
@@ -1232,7 +1297,7 @@ class JepaEngine:
             else:
                 x_in, xb_in = (x0, xb0) if i == 0 else (acts[i - 1].x2, acts[i - 1].x2b)
                 dy, dyb, done = self._layer_bwd(w, a, x_in, xb_in, dy, dyb, bw["dy"], M, D, H, B, mask, bw, i % nbuf, seq, sub=sub_i,
-                                                flush=flush, bottom=i == 0)
+                                                flush=flush, bottom=i == 0, stack=stack, li=i)
             if done and flushed is not None:
                 flushed(i)
         return dy
@@ -1260,9 +1325,18 @@ class JepaEngine:
         ops.add_pos(src, self.pos_enc, M=M, T=T, D=c.d_enc, y_f32=self.lf, y_bf16=self.lf_b)
 
     # ------------------------------------------------------------------------------------------------ forward
-    def forward(self, audio: torch.Tensor, plan: MaskPlan) -> None:
-        """Training forward.  Results: self.loss[0], self.preds, self.targets, self.cf[:n_ctx], self.lf."""
+    def forward(self, audio: torch.Tensor, plan: MaskPlan, train: bool = True, drop_call: Optional[int] = None) -> None:
+        """Training forward.  Results: self.loss[0], self.preds, self.targets, self.cf[:n_ctx], self.lf.
+        train (module.training): with it, a stack whose EngineConfig rate is > 0 runs under dropout, its masks drawn from
+        (self.drop_seed, drop_call); the backward of this forward uses the same.  Without it, or with both rates 0, the launches are
+        exactly those of an engine without dropout."""
         N = audio.shape[0]
+        self._drop_now = {}
+        if train and (self.cfg.dropout_enc > 0 or self.cfg.dropout_dec > 0):
+            self._check_fp8()
+            self._drop_now = {k: float(p) for k, p in (("enc", self.cfg.dropout_enc), ("dec", self.cfg.dropout_dec)) if p > 0}
+            if drop_call is not None:
+                self.drop_call = int(drop_call)
         if plan.N != N or plan.T != self.T or plan.G < 1:
             raise ValueError(f"mask plan is for {plan.N} clips x {plan.G} groups x {plan.T} tokens; the batch has {N} clips of {self.T} tokens")
         rag = self.ragged and plan.ragged_ok
@@ -1542,6 +1616,7 @@ class JepaEngine:
         if N != self.N:
             self.alloc(N, train=False)
         self.wait_optimizer()
+        self._drop_now = {}             # inference runs without dropout
         self._frontend(audio)
         self._stack_fwd("enc", self.lf, self.lf_b, self.M, N, key_mask_u8, y_f32=self.enc_out)
         return self.enc_out.view(N, self.T, c.d_enc)

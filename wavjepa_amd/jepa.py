@@ -49,7 +49,7 @@ class _SelfAttention(nn.Module):
 
 
 class _PostNormLayer(nn.Module):
-    def __init__(self, d_model: int, nhead: int, dim_feedforward: int, layer_norm_eps: float, **unused):
+    def __init__(self, d_model: int, nhead: int, dim_feedforward: int, layer_norm_eps: float, **unused):     # (dropout: TransformerStack.dropout)
         super().__init__()
         self.self_attn = _SelfAttention(d_model)
         self.linear1 = nn.Linear(d_model, dim_feedforward)
@@ -71,8 +71,16 @@ class TransformerStack(nn.Module):
     def __init__(self, layer_cfg: Dict[str, Any], num_layers: int):
         super().__init__()
         self.norm_first = bool(layer_cfg.get("norm_first", False))
-        if layer_cfg.get("dropout", 0.0) != 0.0:
-            raise NotImplementedError("dropout is 0 on the WavJEPA path")
+        # dropout: the rate of this stack's layers in a training-mode forward (engine: the _drop kernels; 0 = the launches without it)
+        self.dropout = float(layer_cfg.get("dropout", 0.0) or 0.0)
+        if not (0.0 <= self.dropout < 1.0):
+            raise ValueError(f"dropout must lie in [0, 1), not {layer_cfg.get('dropout')}")
+        if self.dropout > 0 and self.norm_first:
+            raise NotImplementedError(f"dropout={self.dropout} with norm_first=True: the dropout kernels cover post-norm layers only")
+        if self.dropout > 0 and int(layer_cfg["d_model"]) // int(layer_cfg["nhead"]) not in (32, 64):
+            raise NotImplementedError(f"dropout={self.dropout} with {int(layer_cfg['d_model']) // int(layer_cfg['nhead'])}-wide heads "
+                                      f"(d_model={layer_cfg['d_model']}, nhead={layer_cfg['nhead']}): attention dropout runs in the "
+                                      "streamed kernels, which take head widths 32 and 64")
         if int(layer_cfg["dim_feedforward"]) != 4 * int(layer_cfg["d_model"]):
             raise NotImplementedError("feed-forward width must be 4 * d_model")
         first = (_PreNormLayer if self.norm_first else _PostNormLayer)(**layer_cfg)
@@ -353,6 +361,15 @@ class JEPA(_ModuleBase):
             self.hparams["norm_first_encoder"] = True
         if self.decoder.norm_first:
             self.hparams["norm_first_decoder"] = True
+        # Dropout in the student and the predictor of a training-mode forward; the TEACHER runs without it (differences
+        # by design).  The masks are a function of (dropout_seed, dropout_call or global_step, stack, layer, site, element): nothing is
+        # stored, a resumed run continues the same mask sequence.  Recorded only when some rate is set (the rule of norm_first_*).
+        self._dropout_seed = int(torch.initial_seed())
+        self.dropout_call: Optional[int] = None       # None: int(global_step)
+        if self.encoder.dropout > 0 or self.decoder.dropout > 0:
+            self.hparams["dropout_encoder"] = self.encoder.dropout
+            self.hparams["dropout_decoder"] = self.decoder.dropout
+            self.hparams["dropout_seed"] = self._dropout_seed
         self.decoder_to_encoder_mapper = nn.Linear(self.decoder_embedding_dim, self.encoder_embedding_dim, bias=True)
         self.encoder_to_decoder_mapper = nn.Linear(self.encoder_embedding_dim, self.decoder_embedding_dim)
         self.mask_token = nn.Parameter(torch.zeros(1, 1, self.decoder_embedding_dim))
@@ -464,7 +481,8 @@ class JEPA(_ModuleBase):
                            top_k=int(self.hparams.average_top_k_layers), ln_eps=self.encoder.layer_norm_eps,
                            norm_first_enc=self.encoder.norm_first, norm_first_dec=self.decoder.norm_first,
                            conv_mode=getattr(ext, "mode", "default"), conv_bias=bool(getattr(ext, "conv_bias", False)),
-                           loss_kind=self.loss_kind, loss_beta=self.loss_beta, recompute=self.use_gradient_checkpointing)
+                           loss_kind=self.loss_kind, loss_beta=self.loss_beta, recompute=self.use_gradient_checkpointing,
+                           dropout_enc=self.encoder.dropout, dropout_dec=self.decoder.dropout)
         self._engine = JepaEngine(cfg, self._flat, self.pos_encoding_encoder.data, self.pos_encoding_decoder.data)
         self._anchor = torch.zeros(1, device=self.device, requires_grad=True)
         self._student_bf16_fresh = False
@@ -542,7 +560,8 @@ class JEPA(_ModuleBase):
             raise ValueError(f"expected {self.extract_audio.in_channels} audio channel(s), got {audio.shape[1]}")
         plan = ctx_masks if isinstance(ctx_masks, MaskPlan) else make_mask_plan(ctx_masks, target_indices, ctx_and_target_masks, self.device)
         self._prepare_weights()
-        eng.forward(audio, plan)
+        eng.drop_seed = self._dropout_key()
+        eng.forward(audio, plan, train=self.training, drop_call=int(self.global_step) if self.dropout_call is None else int(self.dropout_call))
         N, T = audio.shape[0], eng.T
         if torch.is_grad_enabled():
             loss = _EngineLoss.apply(self._anchor, self)
@@ -550,6 +569,23 @@ class JEPA(_ModuleBase):
             loss = eng.loss[0].clone()
         return _StepOutputs(eng, local_features=eng.lf.view(N, T, -1), contextual_features=eng.cf[:plan.n_ctx], loss=loss,
                             targets=eng.targets.view(N, T, -1))
+
+    @property
+    def dropout_seed(self) -> int:
+        return self._dropout_seed
+
+    @dropout_seed.setter
+    def dropout_seed(self, seed: int) -> None:       # (the checkpoint's hyper-parameters follow: a resumed run reads the seed there)
+        self._dropout_seed = int(seed)
+        if "dropout_seed" in self.hparams:
+            self.hparams["dropout_seed"] = int(seed)
+
+    def _dropout_key(self) -> int:
+        """The generator's 64-bit key: dropout_seed with the data-parallel rank mixed in (every rank draws its own masks)."""
+        rank = 0
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            rank = torch.distributed.get_rank()
+        return (int(self.dropout_seed) ^ (rank * 0x9E3779B97F4A7C15)) & 0xFFFFFFFFFFFFFFFF
 
     @torch.no_grad()
     def get_audio_representation(self, audio: torch.Tensor, padding_mask: Optional[torch.Tensor]) -> torch.Tensor:

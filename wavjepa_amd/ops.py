@@ -86,6 +86,7 @@ class TimingEvent:
 
 # the argument struct class of every stream entry, from the headers' prototypes
 _ENTRY_STRUCT = {fn: {**STRUCTS, **_abi.LAB_STRUCTS}[name] for fn, name in _abi.ENTRY_ARGS.items()}
+_ENTRY_STRUCT.update({fn: _abi.DROPOUT_STRUCTS[name] for fn, name in _abi.DROPOUT_ENTRY_ARGS.items()})    # libwavjepa_hip_dropout.so
 
 
 def _call(fn: str, a, stream: Optional[int], fields) -> None:
@@ -642,3 +643,9 @@ def noise_prepare(noise: Ptr, out: Ptr, workspace: Ptr, *, offsets, lengths, cut
          offsets=host[0].ctypes.data, lengths=host[1].ctypes.data, cut_start=host[2].ctypes.data, place_start=host[3].ctypes.data,
          clips=host[4].ctypes.data, noise_elems=noise_elems, workspace_bytes=workspace_bytes, B=B, n_clips=int(host[4].size),
          max_len=max_len, out_len=out_len, fade_len=fade_len)
+
+
+# ---------------------------------------------------------------------------------------------------------- dropout
+# the wrappers of libwavjepa_hip_dropout.so (include/wavjepa_hip_dropout.h) live in wavjepa_amd/dropout_ops.py and belong to this namespace
+from .dropout_ops import (DROP_SITE_ATTN, DROP_SITE_FFN, DROP_SITE_RES1, DROP_SITE_RES2, DROP_STACK, attn_stream_bwd_drop,  # noqa: E402,F401
+                          attn_stream_fwd_drop, drop_args, dropout_rows, layernorm_bwd_drop, layernorm_fwd_drop)

@@ -173,6 +173,10 @@ class Trainer:
             ck = torch.load(ckpt_path, map_location="cpu", weights_only=False)
             model.load_state_dict(ck["state_dict"])
             model.global_step = int(ck.get("global_step", 0))
+            # dropout masks are a function of (dropout_seed, global_step): a resumed run continues the saved run's mask sequence
+            seed = (ck.get("hyper_parameters") or {}).get("dropout_seed")
+            if seed is not None and hasattr(model, "dropout_seed"):
+                model.dropout_seed = int(seed)
             if "optimizer" in ck:
                 runner.optimizer.load_state_dict(ck["optimizer"])
             if "lr_scheduler" in ck:
