@@ -96,8 +96,20 @@ class ComponentFactory:
             raise RuntimeError(f"Failed to create network instance: {str(e)}")
 
 
+def monitor_settings(cfg) -> tuple:
+    """(monitor_every, min_pred_var, min_target_var): trainer.monitor_every steps between two collapse monitors (0 = off, the default),
+    trainer.min_pred_var / trainer.min_target_var the thresholds below which the run stops (0 = no check; data2vec 2.0: 0.01 / 0.1).
+    A threshold without monitor_every monitors the steps the trainer logs."""
+    every = int(cfg.trainer.get("monitor_every", 0))
+    min_pred, min_target = float(cfg.trainer.get("min_pred_var", 0.0)), float(cfg.trainer.get("min_target_var", 0.0))
+    if every == 0 and (min_pred > 0 or min_target > 0):
+        every = int(cfg.trainer.get("log_every_n_steps", 50))
+    return every, min_pred, min_target
+
+
 def setup_trainer(cfg) -> Trainer:
-    return Trainer(accelerator=cfg.trainer.accelerator, max_epochs=cfg.trainer.epochs, max_steps=cfg.trainer.steps,
+    _, min_pred, min_target = monitor_settings(cfg)
+    return Trainer(min_pred_var=min_pred, min_target_var=min_target, accelerator=cfg.trainer.accelerator, max_epochs=cfg.trainer.epochs, max_steps=cfg.trainer.steps,
                    precision=cfg.trainer.precision, devices=int(cfg.trainer.num_gpus), gradient_clip_val=5,
                    gradient_clip_algorithm="norm", strategy="ddp" if int(cfg.trainer.num_gpus) > 1 else "auto",
                    log_every_n_steps=cfg.trainer.get("log_every_n_steps", 50),
@@ -109,6 +121,8 @@ def setup_trainer(cfg) -> Trainer:
 def build_model(cfg):
     extractor = ComponentFactory.create_extractor(cfg)
     network = ComponentFactory.create_network(cfg, extractor)
+    if hasattr(network, "monitor_every"):
+        network.monitor_every = monitor_settings(cfg)[0]
     return network, extractor.total_patches(int(cfg.data.sr * cfg.data.process_seconds))
 
 

@@ -105,9 +105,38 @@ STRUCTS, LAB_STRUCTS = _HEADER.struct_types, _LAB.struct_types
 _DROP = Header(DROPOUT_HEADER, known=_HEADER)
 DROPOUT_STRUCTS, DROPOUT_FUNCTIONS, DROPOUT_ENTRY_ARGS = _DROP.struct_types, list(_DROP.functions), dict(_DROP.entry_args)
 
+# libwavjepa_hip_monitor.so (wj_masked_moments, the collapse monitor): likewise a header, a function list and an entry map of its own
+MONITOR_HEADER = os.path.join(os.path.dirname(HERE), "include", "wavjepa_hip_monitor.h")
+MONITOR_LIB_PATH = os.path.join(HERE, "lib", "libwavjepa_hip_monitor.so")
+_MON = Header(MONITOR_HEADER, known=_HEADER)
+MONITOR_STRUCTS, MONITOR_FUNCTIONS, MONITOR_ENTRY_ARGS, MONITOR_DEFINES = _MON.struct_types, list(_MON.functions), dict(_MON.entry_args), _MON.defines
+
 _lib = None
 _lab_lib = None
 _dropout_lib = None
+_monitor_lib = None
+
+
+def load_monitor():
+    """libwavjepa_hip_monitor.so (once), its struct sizes cross-checked against its own wj_monitor_struct_size.  Loaded behind the release
+    library, as load_dropout() does."""
+    global _monitor_lib
+    if _monitor_lib is None:
+        load()
+        if not os.path.exists(MONITOR_LIB_PATH):
+            raise WavJepaHipError(f"{MONITOR_LIB_PATH} is missing: run `python -m wavjepa_amd.build` (or __graft_entry__.build())")
+        lib = ctypes.CDLL(MONITOR_LIB_PATH)
+        for fn in MONITOR_FUNCTIONS:
+            if not hasattr(lib, fn):
+                raise WavJepaHipError(f"{MONITOR_LIB_PATH} does not export {fn} (declared in include/wavjepa_hip_monitor.h); rebuild it")
+            f = getattr(lib, fn)
+            f.restype, f.argtypes = _MON.functions[fn]
+        for name, cls in MONITOR_STRUCTS.items():
+            want = lib.wj_monitor_struct_size(name.encode())
+            if want != ctypes.sizeof(cls):
+                raise WavJepaHipError(f"struct {name}: header mirror is {ctypes.sizeof(cls)} bytes, library says {want}")
+        _monitor_lib = lib
+    return _monitor_lib
 
 
 def load_dropout():
@@ -186,6 +215,8 @@ def workspace_bytes(fn_name: str, args_struct) -> int:
     """Scratch bytes the call `fn_name(args_struct)` needs (pointers in the struct are ignored)."""
     if fn_name in DROPOUT_ENTRY_ARGS:
         n = int(load_dropout().wj_dropout_workspace_bytes(fn_name.encode(), ctypes.byref(args_struct)))
+    elif fn_name in MONITOR_ENTRY_ARGS:
+        n = int(load_monitor().wj_monitor_workspace_bytes(fn_name.encode(), ctypes.byref(args_struct)))
     else:
         n = int(load().wj_workspace_bytes(fn_name.encode(), ctypes.byref(args_struct)))
     if n < 0:
@@ -197,7 +228,7 @@ _ERR = {-1: "invalid argument", -2: "kernel launch failed", -3: "unsupported con
 
 
 def call(fn_name: str, args_struct, stream: int, lab: bool = False) -> None:
-    lib = load_dropout() if fn_name in DROPOUT_ENTRY_ARGS else (load_lab() if lab else load())
+    lib = load_dropout() if fn_name in DROPOUT_ENTRY_ARGS else (load_monitor() if fn_name in MONITOR_ENTRY_ARGS else (load_lab() if lab else load()))
     rc = getattr(lib, fn_name)(ctypes.byref(args_struct), stream)
     if rc != 0:
         raise WavJepaHipError(f"{fn_name} failed: {_ERR.get(rc, rc)}")

@@ -21,6 +21,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-val
 DROPOUT_LIB = os.path.join(LIBDIR, "libwavjepa_hip_dropout.so")
 DROPOUT_SOURCES = ["dropout.hip", "norm.hip", "attention_stream.hip", "dropout_abi.hip"]
 DROPOUT_FLAGS = ["-DWJ_DROPOUT_LIB", "-fvisibility=hidden"]
+# libwavjepa_hip_monitor.so (include/wavjepa_hip_monitor.h): wj_masked_moments, the collapse monitor, and its two query entries
+MONITOR_LIB = os.path.join(LIBDIR, "libwavjepa_hip_monitor.so")
+MONITOR_SOURCES = ["monitor.hip"]
+MONITOR_FLAGS = ["-fvisibility=hidden"]
 
 
 def _hipcc() -> str:
@@ -37,19 +41,19 @@ def _stale(target: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force: bool = False, verbose: bool = True, lab: bool = False, dropout: bool = False) -> str:
+def build(force: bool = False, verbose: bool = True, lab: bool = False, dropout: bool = False, monitor: bool = False) -> str:
     """The release library (compute + query entries, production-safe switches only), or with lab=True the laboratory variant
     (libwavjepa_hip_lab.so: -DWJ_LAB, the extra entries of include/wavjepa_hip_lab.h and every A/B / diagnostic environment switch),
-    or with dropout=True libwavjepa_hip_dropout.so."""
+    or with dropout=True libwavjepa_hip_dropout.so, or with monitor=True libwavjepa_hip_monitor.so."""
     hipcc = _hipcc()
     os.makedirs(LIBDIR, exist_ok=True)
-    objdir = os.path.join(LIBDIR, "obj_dropout" if dropout else ("obj_lab" if lab else "obj"))
+    objdir = os.path.join(LIBDIR, "obj_monitor" if monitor else ("obj_dropout" if dropout else ("obj_lab" if lab else "obj")))
     os.makedirs(objdir, exist_ok=True)
     inc = os.path.join(os.path.dirname(HERE), "include")
     headers = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(inc, "*.h"))
-    flags = FLAGS + (DROPOUT_FLAGS if dropout else (["-DWJ_LAB"] if lab else []))
-    lib = DROPOUT_LIB if dropout else (LAB_LIB if lab else LIB)
-    sources = DROPOUT_SOURCES if dropout else SOURCES
+    flags = FLAGS + (MONITOR_FLAGS if monitor else (DROPOUT_FLAGS if dropout else (["-DWJ_LAB"] if lab else [])))
+    lib = MONITOR_LIB if monitor else (DROPOUT_LIB if dropout else (LAB_LIB if lab else LIB))
+    sources = MONITOR_SOURCES if monitor else (DROPOUT_SOURCES if dropout else SOURCES)
     jobs = []
     for src in sources:
         s = os.path.join(CSRC, src)
@@ -78,7 +82,7 @@ def build(force: bool = False, verbose: bool = True, lab: bool = False, dropout:
             raise RuntimeError(f"link failed:\n{r.stderr}")
         if verbose:
             print(f"[wavjepa_amd.build] linked {lib}", file=sys.stderr)
-    if not lab and not dropout:
+    if not lab and not dropout and not monitor:
         build_io(force=force, verbose=verbose)
     return lib
 
@@ -87,6 +91,7 @@ def build_all(force: bool = False, verbose: bool = True) -> None:
     """Release + laboratory libraries (what __graft_entry__.build() and the test suite need)."""
     build(force=force, verbose=verbose)
     build(force=force, verbose=verbose, dropout=True)
+    build(force=force, verbose=verbose, monitor=True)
     build(force=force, verbose=verbose, lab=True)
 
 

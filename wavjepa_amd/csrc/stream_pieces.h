@@ -1,5 +1,6 @@
 // The pieces the streaming kernels are made of, one copy each: csrc/misc.hip (token plumbing, targets, masked loss, optimiser pass),
-// denoise.hip, scene.hip, fp8.hip, noise_prep.hip and audio_prep.hip include this header.
+// denoise.hip, scene.hip, fp8.hip, noise_prep.hip, audio_prep.hip and monitor.hip (the collapse monitor, a library of its own)
+// include this header.
 //   conversions: to_f32x4 / to_bf16x4 -- four bf16 <-> four fp32 (f2bf: RNE)
 //   walkers    : for_each_flat (the 256-thread grid-stride loop), for_each_row_col (the same over [rows][per_row])
 //   bodies     : fill_token (one predictor-input piece: context feature or mask token, plus position), gelu_bwd8

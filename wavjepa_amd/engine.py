@@ -327,6 +327,8 @@ class JepaEngine:
         self.fuse_conv_gelu_bwd = _os.environ.get("WJ_FUSE_CONV_GELU_BWD", "1") != "0"
         # last predictor layer: after its attention only the target rows go on (WJ_TRIM_TAIL=0: every visible row)
         self.trim_tail = _os.environ.get("WJ_TRIM_TAIL", "1") != "0"
+        self._monitor_now = False
+        self.moments = self.moments_col = self.moments_ws = None      # collapse monitor (forward(monitor=True)): made on first use
         self.tail = None
         # MX fp8 forward GEMMs (BASELINE config 5; build-defined numerics, WJ_FP8=1 or engine.fp8 = True): every transformer forward
         # linear whose K is a multiple of 256 runs on block-scaled e4m3 operands (wj_gemm_mxfp8, 2x the bf16 MFMA rate); weights are
@@ -1325,12 +1327,16 @@ class JepaEngine:
         ops.add_pos(src, self.pos_enc, M=M, T=T, D=c.d_enc, y_f32=self.lf, y_bf16=self.lf_b)
 
     # ------------------------------------------------------------------------------------------------ forward
-    def forward(self, audio: torch.Tensor, plan: MaskPlan, train: bool = True, drop_call: Optional[int] = None) -> None:
+    def forward(self, audio: torch.Tensor, plan: MaskPlan, train: bool = True, drop_call: Optional[int] = None, monitor: bool = False) -> None:
         """Training forward.  Results: self.loss[0], self.preds, self.targets, self.cf[:n_ctx], self.lf.
         train (module.training): with it, a stack whose EngineConfig rate is > 0 runs under dropout, its masks drawn from
         (self.drop_seed, drop_call); the backward of this forward uses the same.  Without it, or with both rates 0, the launches are
-        exactly those of an engine without dropout."""
+        exactly those of an engine without dropout.
+        monitor: one wj_masked_moments right behind the loss, over the rows the loss uses; self.moments = (pred_var, target_var, n, 0)
+        and self.moments_col (per-column mean and M2, what a data-parallel run merges).  Without it no launch, allocation or pointer
+        of the step differs: the monitor's buffers are made by the first forward that asks for it."""
         N = audio.shape[0]
+        self._monitor_now = bool(monitor)
         self._drop_now = {}
         if train and (self.cfg.dropout_enc > 0 or self.cfg.dropout_dec > 0):
             self._check_fp8()
@@ -1405,13 +1411,31 @@ class JepaEngine:
                  ldc=De, bias=f.ptr32("decoder_to_encoder_mapper.bias"))
         self._join_side()               # teacher targets (side stream) are needed by the loss
         self._mse(None, None)
+        if self._monitor_now:
+            self._moments()
+
+    def _loss_rows(self) -> dict:
+        """The row list of self.preds for the loss and the monitor: the target rows (trimmed tail), the visible rows (ragged), none (dense)."""
+        plan = self.plan
+        if self.ragged_step and self.tail is not None:
+            return dict(rows=plan.tgt_dense, n_rows=plan.n_tgt)          # preds hold the target rows only
+        return dict(rows=plan.dec_rows, n_rows=plan.n_dec) if self.ragged_step else {}
+
+    def _moments(self) -> None:
+        """Collapse monitor: reads self.preds / self.targets only, behind the loss on the same stream, no host synchronisation."""
+        N, G, T, De = self.N, self.G, self.T, self.cfg.d_enc
+        need = ops.workspace_bytes("wj_masked_moments", B=N, G=G, T=T, D=De) // 8
+        if self.moments is None or self.moments_col.shape[-1] != De:
+            self.moments = torch.zeros(4, dtype=torch.float32, device=self.dev)
+            self.moments_col = torch.zeros(2, 2, De, dtype=torch.float64, device=self.dev)
+        if self.moments_ws is None or self.moments_ws.numel() < need:
+            self.moments_ws = torch.empty(max(need, 1), dtype=torch.float64, device=self.dev)
+        ops.masked_moments(self.preds, self.targets, self.plan.tgt_u8, self.moments, self.moments_ws, B=N, G=G, T=T, D=De,
+                           col=self.moments_col, **self._loss_rows())
 
     def _mse(self, dpreds, gscale_ptr) -> None:
         c, plan = self.cfg, self.plan
-        if self.ragged_step and self.tail is not None:
-            rows = dict(rows=plan.tgt_dense, n_rows=plan.n_tgt)          # preds hold the target rows only
-        else:
-            rows = dict(rows=plan.dec_rows, n_rows=plan.n_dec) if self.ragged_step else {}
+        rows = self._loss_rows()
         if c.loss_kind == "mse":
             ops.masked_mse(self.preds, self.targets, plan.tgt_u8, self.loss, self.mse_ws, B=self.N, G=self.G, T=self.T, D=c.d_enc,
                            dpreds=dpreds, gscale_ptr=gscale_ptr, **rows)

@@ -370,6 +370,10 @@ class JEPA(_ModuleBase):
             self.hparams["dropout_encoder"] = self.encoder.dropout
             self.hparams["dropout_decoder"] = self.decoder.dropout
             self.hparams["dropout_seed"] = self._dropout_seed
+        # Collapse monitor (an attribute, no constructor argument: signature and hyper-parameters are what they were).  A training-mode
+        # forward at a step with global_step % monitor_every == 0 returns pred_var / target_var (device scalars: the mean over
+        # features of sqrt(variance over the loss's rows + 1e-6)) and training_step logs them; 0 = never, the step as it always was.
+        self.monitor_every: int = 0
         self.decoder_to_encoder_mapper = nn.Linear(self.decoder_embedding_dim, self.encoder_embedding_dim, bias=True)
         self.encoder_to_decoder_mapper = nn.Linear(self.encoder_embedding_dim, self.decoder_embedding_dim)
         self.mask_token = nn.Parameter(torch.zeros(1, 1, self.decoder_embedding_dim))
@@ -546,6 +550,8 @@ class JEPA(_ModuleBase):
         audio_input, ctx_masks, target_indices, ctx_and_target_masks = batch
         out = self(audio_input, ctx_masks, target_indices, ctx_and_target_masks)
         self.log_dict({"train/loss": out["loss"], "ema": self._get_ema_decay()}, prog_bar=True, sync_dist=True)
+        if "pred_var" in out:          # a monitored step (monitor_every)
+            self.log_dict({"train/pred_var": out["pred_var"], "train/target_var": out["target_var"]}, prog_bar=False, sync_dist=True)
         self._step_teacher()           # EMA with the pre-update student, before backward (reference jepa.py:330-331)
         return out
 
@@ -561,14 +567,24 @@ class JEPA(_ModuleBase):
         plan = ctx_masks if isinstance(ctx_masks, MaskPlan) else make_mask_plan(ctx_masks, target_indices, ctx_and_target_masks, self.device)
         self._prepare_weights()
         eng.drop_seed = self._dropout_key()
-        eng.forward(audio, plan, train=self.training, drop_call=int(self.global_step) if self.dropout_call is None else int(self.dropout_call))
+        every = int(self.monitor_every)
+        monitor = self.training and every > 0 and int(self.global_step) % every == 0
+        drop_call = int(self.global_step) if self.dropout_call is None else int(self.dropout_call)
+        if monitor:
+            eng.forward(audio, plan, train=self.training, drop_call=drop_call, monitor=True)
+        else:
+            eng.forward(audio, plan, train=self.training, drop_call=drop_call)
         N, T = audio.shape[0], eng.T
         if torch.is_grad_enabled():
             loss = _EngineLoss.apply(self._anchor, self)
         else:
             loss = eng.loss[0].clone()
-        return _StepOutputs(eng, local_features=eng.lf.view(N, T, -1), contextual_features=eng.cf[:plan.n_ctx], loss=loss,
-                            targets=eng.targets.view(N, T, -1))
+        out = _StepOutputs(eng, local_features=eng.lf.view(N, T, -1), contextual_features=eng.cf[:plan.n_ctx], loss=loss,
+                           targets=eng.targets.view(N, T, -1))
+        if monitor:                    # copies: the engine's buffer is overwritten by the next monitored step
+            stats = eng.moments.clone()
+            out["pred_var"], out["target_var"] = stats[0], stats[1]
+        return out
 
     @property
     def dropout_seed(self) -> int:

@@ -119,11 +119,15 @@ class StepRunner:
         return out
 
 
+class CollapseError(RuntimeError):
+    """A collapse monitor fell below its threshold (Trainer(min_pred_var=..., min_target_var=...))."""
+
+
 class Trainer:
     def __init__(self, accelerator: str = "gpu", max_steps: int = 375000, max_epochs: int = -1, precision: str = "bf16-mixed",
                  devices: int = 1, gradient_clip_val: float = 5.0, gradient_clip_algorithm: str = "norm", strategy: str = "auto",
                  log_every_n_steps: int = 50, default_root_dir: Optional[str] = None, checkpoint_every_n_steps: int = 25000,
-                 deterministic: bool = False, **unused):
+                 deterministic: bool = False, min_pred_var: float = 0.0, min_target_var: float = 0.0, **unused):
         if accelerator not in ("gpu", "cuda", "auto"):
             raise ValueError("wavjepa_amd trains on MI355X GPUs only (accelerator='gpu'); there is no CPU path")
         if precision not in ("bf16-mixed", "bf16"):
@@ -139,11 +143,39 @@ class Trainer:
         # True: the engine's deterministic mode (bit-reproducible gradients and updates on one build and GPU model; the WJ_DETERMINISTIC
         # environment variable switches it on as well).  One GPU: the order of a multi-GPU gradient reduction is RCCL's.
         self.deterministic = bool(deterministic)
+        # Collapse thresholds (data2vec 2.0: 0.01 / 0.1; 0 = no check) on the statistics of a monitored step (model.monitor_every):
+        # checked at log steps, the one place this loop synchronises.
+        self.min_pred_var, self.min_target_var = float(min_pred_var), float(min_target_var)
         self.rank, self.local_rank, self.world = init_distributed()
         self.logged: Dict[str, Any] = {}
 
     def log_dict(self, data: Dict[str, Any], **kw) -> None:
         self.logged = data          # kept on the device: no per-step host sync / scalar all-reduce
+
+    def check_collapse(self, step: int, pred_var: float, target_var: float) -> None:
+        """Raise CollapseError when a statistic of the monitored step `step` lies below its threshold."""
+        for name, value, floor in (("pred_var", pred_var, self.min_pred_var), ("target_var", target_var, self.min_target_var)):
+            if floor > 0.0 and not value >= floor:          # (a NaN statistic is a collapse too)
+                raise CollapseError(f"{name} = {value:.6g} is below min_{name} = {floor:.6g} at step {step}: the run has collapsed "
+                                    f"(pred_var {pred_var:.6g}, target_var {target_var:.6g})")
+
+    def _monitor_values(self, model, seen) -> tuple:
+        """(step, pred_var, target_var) of the last monitored step as host floats.  One rank: the step's own scalars.  Several: every
+        rank's row count and per-column moments are gathered and merged (merge_moments), so all ranks hold the statistic of the
+        global batch and raise together."""
+        step, pv, tv = seen
+        if not (dist.is_initialized() and self.world > 1):
+            return step, float(pv), float(tv)
+        from .ops import merge_moments
+        eng = model._engine
+        mine = torch.cat([eng.moments[2:3].double(), eng.moments_col.reshape(-1)])
+        every = [torch.empty_like(mine) for _ in range(self.world)]
+        dist.all_gather(every, mine)
+        host = torch.stack(every).cpu().numpy()
+        D = (host.shape[1] - 1) // 4
+        stat = [merge_moments([(h[0], h[1 + 2 * q * D:1 + (2 * q + 1) * D], h[1 + (2 * q + 1) * D:1 + (2 * q + 2) * D]) for h in host])
+                for q in (0, 1)]
+        return step, stat[0], stat[1]
 
     def save_checkpoint(self, model, runner: StepRunner, path: str, versioned: bool = False) -> None:
         """`versioned`: never overwrite (Lightning's enable_version_counter): last.ckpt, last-v1.ckpt, ... -- the run directory is
@@ -183,22 +215,31 @@ class Trainer:
                 runner.scheduler.load_state_dict(ck["lr_scheduler"])
         loader = train_dataloaders if train_dataloaders is not None else datamodule.train_dataloader()
         t0 = time.time()
+        seen = None         # (step, pred_var, target_var) of the last monitored step since the last log step, still on the device
         for batch in loader:
             if model.global_step >= self.max_steps:
                 break
             out = runner.step(batch, model.global_step)
             gs = model.global_step
+            if "pred_var" in out:
+                seen = (gs - 1, out["pred_var"].detach(), out["target_var"].detach())
+            mon = None
             if self.log_every_n_steps and gs % self.log_every_n_steps == 0:
                 lt = out["loss"].detach().float().clone()
                 if dist.is_initialized() and self.world > 1:
                     dist.all_reduce(lt, op=dist.ReduceOp.AVG)   # the reference logs with sync_dist=True (jepa.py:328): the rank mean
+                if seen is not None:
+                    mon, seen = self._monitor_values(model, seen), None
             if self.log_every_n_steps and gs % self.log_every_n_steps == 0 and self.rank == 0:
                 loss = float(lt)                      # the only host sync, every n steps
                 dt = time.time() - t0
                 ema = f"  ema {model._get_ema_decay():.6f}" if hasattr(model, "_get_ema_decay") else ""
-                print(f"step {gs}  loss {loss:.5f}  lr {runner.scheduler.get_last_lr()[0]:.3e}{ema}  "
+                var = f"  pred_var {mon[1]:.5f}  target_var {mon[2]:.5f} (step {mon[0]})" if mon is not None else ""
+                print(f"step {gs}  loss {loss:.5f}  lr {runner.scheduler.get_last_lr()[0]:.3e}{ema}{var}  "
                       f"{dt / self.log_every_n_steps * 1000:.1f} ms/step", flush=True)
                 t0 = time.time()
+            if mon is not None:
+                self.check_collapse(*mon)
             if self.root and self.ckpt_every and gs % self.ckpt_every == 0:
                 self.save_checkpoint(model, runner, os.path.join(self.root, f"step={gs}.ckpt"), versioned=ckpt_path is None)
         if self.root:
