@@ -46,6 +46,8 @@ def setup_trainer(cfg) -> Trainer:
                    precision=cfg.trainer.precision, devices=int(cfg.trainer.num_gpus), gradient_clip_val=1.0, gradient_clip_algorithm="norm",
                    log_every_n_steps=cfg.trainer.get("log_every_n_steps", 1),
                    deterministic=bool(cfg.trainer.get("deterministic", False)),
+                   # (passed on so that a value above 1 is refused by Trainer.fit: accumulation covers the JEPA stage only)
+                   accumulate_grad_batches=cfg.trainer.get("accumulate_grad_batches", 1),
                    default_root_dir=checkpoint_dir(cfg, "saved_models_jepa_denoised", get_identity_from_cfg_denoise(cfg)),
                    checkpoint_every_n_steps=2500)
 

@@ -114,6 +114,8 @@ def setup_trainer(cfg) -> Trainer:
                    gradient_clip_algorithm="norm", strategy="ddp" if int(cfg.trainer.num_gpus) > 1 else "auto",
                    log_every_n_steps=cfg.trainer.get("log_every_n_steps", 50),
                    deterministic=bool(cfg.trainer.get("deterministic", False)),     # the reference passes deterministic=False (train.py:170)
+                   # trainer.accumulate_grad_batches: loader batches per optimiser step (pl.Trainer's argument; default 1)
+                   accumulate_grad_batches=cfg.trainer.get("accumulate_grad_batches", 1),
                    checkpoint_every_n_steps=25000,      # ModelCheckpoint(every_n_train_steps=25000, save_last=True), reference train.py:146-153
                    default_root_dir=checkpoint_dir(cfg, "saved_models_jepa_new_masking", get_identity_from_cfg(cfg)))
 
@@ -164,7 +166,8 @@ def main(argv=None):
         else:
             source = create_data_source(cfg, patches, device, trainer.rank)
         if trainer.rank == 0:
-            print(f"Effective Batch Size is: {cfg.trainer.batch_size * cfg.data.samples_per_audio * cfg.trainer.num_gpus}")
+            print(f"Effective Batch Size is: "
+                  f"{cfg.trainer.batch_size * cfg.data.samples_per_audio * cfg.trainer.num_gpus * trainer.accumulate_grad_batches}")
         trainer.fit(model, train_dataloaders=source)
     except Exception as e:
         print(f"Training failed with error: {str(e)}")

@@ -1518,8 +1518,9 @@ class JepaEngine:
             self.targets.copy_(x)
 
     # ------------------------------------------------------------------------------------------------ backward
-    def backward(self, gscale_ptr: int = 0, on_grads_ready=None) -> None:
-        """Gradients of self.loss[0] w.r.t. every trainable parameter -> flat.g32 (overwritten).
+    def backward(self, gscale_ptr: int = 0, on_grads_ready=None, accumulate: bool = False) -> None:
+        """Gradients of self.loss[0] w.r.t. every trainable parameter -> flat.g32 (overwritten; accumulate=True: added to what the
+        buffer holds -- every parameter-gradient output of this backward adds into it, so the one difference is the clear below).
 
         `on_grads_ready(tag)` is called (host side, stream-ordered) as sections of the flat gradient buffer become
         final: "dec" (predictor + both mappers), "enc:<i>" after encoder layer i, "front" at the end -- the hook the
@@ -1542,7 +1543,7 @@ class JepaEngine:
         c, f, plan = self.cfg, self.flat, self.plan
         N, M, Mp, T, G = self.N, self.M, self.Mp, self.T, self.G
         De, Dd = c.d_enc, c.d_dec
-        if not getattr(f, "g_clean", False):      # (FusedAdamW.fuse_zero_grad: the last update left the buffer clear)
+        if not accumulate and not getattr(f, "g_clean", False):      # (FusedAdamW.fuse_zero_grad: the last update left the buffer clear)
             f.g32.zero_()
         f.g_clean = False
         if self.deterministic:

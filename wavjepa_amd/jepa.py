@@ -128,7 +128,10 @@ class _EngineLoss(torch.autograd.Function):
     def backward(ctx, grad_out: torch.Tensor):
         m = ctx.module
         g = grad_out.contiguous().float()
-        m._engine.backward(gscale_ptr=g.data_ptr(), on_grads_ready=m._grads_ready_hook)
+        if m.accumulate_grads:           # torch's contract: backward adds, FusedAdamW.zero_grad() clears
+            m._engine.backward(gscale_ptr=g.data_ptr(), on_grads_ready=m._grads_ready_hook, accumulate=True)
+        else:
+            m._engine.backward(gscale_ptr=g.data_ptr(), on_grads_ready=m._grads_ready_hook)
         m._flat.attach_grads()
         return torch.zeros_like(m._anchor), None
 
@@ -212,6 +215,15 @@ class FusedAdamW(torch.optim.Optimizer):
         return self._sumsq.sqrt() if self._sumsq is not None else torch.zeros(1)
 
     def zero_grad(self, set_to_none: bool = True) -> None:  # the engine overwrites the flat gradient buffer each backward
+        m = self._module
+        if not m.accumulate_grads or m._flat is None or m._engine is None:
+            return None
+        # JEPA.accumulate_grads: backward adds into the flat buffer, so this call is the clear (the views stay attached whatever
+        # set_to_none says: the buffer IS the gradients).  Nothing to do behind an update that cleared it itself (fuse_zero_grad).
+        if not getattr(m._flat, "g_clean", False):
+            m._engine.wait_optimizer()       # an update overlapped on the side stream may still read the buffer
+            m._flat.g32.zero_()
+            m._flat.g_clean = True
         return None
 
     def state_dict(self):
@@ -242,6 +254,32 @@ def cosine_schedule_with_warmup(optimizer, num_warmup_steps: int, num_training_s
         return max(0.0, 0.5 * (1.0 + math.cos(math.pi * progress)))
 
     return torch.optim.lr_scheduler.LambdaLR(optimizer, lr_lambda)
+
+
+def accumulate_window(module) -> int:
+    """k = accumulate_grad_batches of the trainer `module` is attached to (Lightning's attribute name); 1 where there is none."""
+    try:
+        k = getattr(module.trainer, "accumulate_grad_batches", 1)
+    except (RuntimeError, AttributeError):       # Lightning: not attached to a Trainer yet
+        k = 1
+    return 1 if k is None else int(k)
+
+
+def dropout_call_of(global_step: int, k: int = 1, micro: int = 0, explicit: Optional[int] = None) -> int:
+    """The dropout generator's call counter of a training forward: an explicit model.dropout_call, else global_step * k + micro for
+    micro-batch `micro` of a window of k (k = 1: global_step), so that the micro-batches of one optimiser step draw different masks.
+    The counter is 32 bits wide in the kernels (wj_dropout_args.call): a product beyond that would wrap onto an earlier step's masks."""
+    if explicit is not None:
+        return int(explicit)
+    if k == 1:
+        return int(global_step)
+    if not 0 <= micro < k:
+        raise ValueError(f"micro-batch index {micro} outside a window of {k}")
+    call = int(global_step) * int(k) + int(micro)
+    if call >= 1 << 32:
+        raise OverflowError(f"dropout call counter global_step * accumulate_grad_batches + micro = {global_step} * {k} + {micro} does not "
+                            "fit the generator's 32-bit counter")
+    return call
 
 
 class _NullTrainer:
@@ -365,7 +403,7 @@ class JEPA(_ModuleBase):
         # by design).  The masks are a function of (dropout_seed, dropout_call or global_step, stack, layer, site, element): nothing is
         # stored, a resumed run continues the same mask sequence.  Recorded only when some rate is set (the rule of norm_first_*).
         self._dropout_seed = int(torch.initial_seed())
-        self.dropout_call: Optional[int] = None       # None: int(global_step)
+        self.dropout_call: Optional[int] = None       # None: int(global_step) (under accumulation: dropout_call_of)
         if self.encoder.dropout > 0 or self.decoder.dropout > 0:
             self.hparams["dropout_encoder"] = self.encoder.dropout
             self.hparams["dropout_decoder"] = self.decoder.dropout
@@ -374,6 +412,12 @@ class JEPA(_ModuleBase):
         # forward at a step with global_step % monitor_every == 0 returns pred_var / target_var (device scalars: the mean over
         # features of sqrt(variance over the loss's rows + 1e-6)) and training_step logs them; 0 = never, the step as it always was.
         self.monitor_every: int = 0
+        # Gradient accumulation (attributes as well).  accumulate_grads: loss.backward() ADDS into the flat gradient buffer and
+        # FusedAdamW.zero_grad() clears it -- torch's contract, what a loop of k backwards per optimiser step needs; off, every backward
+        # starts from a clear buffer and zero_grad() is a no-op, as always.  _micro = (i, k): the micro-batch index inside a window of
+        # trainer.accumulate_grad_batches = k, set by training_step for the forward it issues ((0, 1) anywhere else).
+        self.accumulate_grads: bool = False
+        self._micro: Tuple[int, int] = (0, 1)
         self.decoder_to_encoder_mapper = nn.Linear(self.decoder_embedding_dim, self.encoder_embedding_dim, bias=True)
         self.encoder_to_decoder_mapper = nn.Linear(self.encoder_embedding_dim, self.decoder_embedding_dim)
         self.mask_token = nn.Parameter(torch.zeros(1, 1, self.decoder_embedding_dim))
@@ -548,7 +592,15 @@ class JEPA(_ModuleBase):
     # ------------------------------------------------------------------------------------------------ step
     def training_step(self, batch, batch_idx: int) -> ForwardReturn:
         audio_input, ctx_masks, target_indices, ctx_and_target_masks = batch
-        out = self(audio_input, ctx_masks, target_indices, ctx_and_target_masks)
+        k = accumulate_window(self)
+        if k > 1:                      # micro-batch batch_idx % k of its window: dropout counter and monitor (forward)
+            self._micro = (int(batch_idx) % k, k)
+            try:
+                out = self(audio_input, ctx_masks, target_indices, ctx_and_target_masks)
+            finally:
+                self._micro = (0, 1)
+        else:
+            out = self(audio_input, ctx_masks, target_indices, ctx_and_target_masks)
         self.log_dict({"train/loss": out["loss"], "ema": self._get_ema_decay()}, prog_bar=True, sync_dist=True)
         if "pred_var" in out:          # a monitored step (monitor_every)
             self.log_dict({"train/pred_var": out["pred_var"], "train/target_var": out["target_var"]}, prog_bar=False, sync_dist=True)
@@ -568,8 +620,10 @@ class JEPA(_ModuleBase):
         self._prepare_weights()
         eng.drop_seed = self._dropout_key()
         every = int(self.monitor_every)
-        monitor = self.training and every > 0 and int(self.global_step) % every == 0
-        drop_call = int(self.global_step) if self.dropout_call is None else int(self.dropout_call)
+        i, k = self._micro
+        # (a window of k micro-batches: the one that closes it is the monitored forward of its optimiser step)
+        monitor = self.training and every > 0 and int(self.global_step) % every == 0 and i == k - 1
+        drop_call = dropout_call_of(int(self.global_step), k, i, self.dropout_call)
         if monitor:
             eng.forward(audio, plan, train=self.training, drop_call=drop_call, monitor=True)
         else:
