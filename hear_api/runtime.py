@@ -63,14 +63,18 @@ class WindowPlan:
 class RuntimeJEPA(torch.nn.Module):
     def __init__(self, in_channels, weights, is_spectrogram, process_seconds, extractor, model_size, sr, **kwargs) -> None:
         """norm_first=True (keyword, default False; RuntimeNatJEPA passes it on): the checkpoint is of a pre-norm model -- its
-        `hyper_parameters` carry norm_first_encoder.  Taken from **kwargs so that the positional surface stays the reference's."""
+        `hyper_parameters` carry norm_first_encoder.  Taken from **kwargs so that the positional surface stays the reference's.
+        activation= (keyword, default None = GELU; a module, function or kind as TransformerLayerCFG takes it) likewise: the checkpoint's
+        `hyper_parameters` carry activation_encoder, and a model trained with ReLU embeds with ReLU."""
         super().__init__()
         norm_first = bool(kwargs.pop("norm_first", False))
+        activation = kwargs.pop("activation", None)
         self.sample_rate = sr
         self.in_channels = int(in_channels)
-        layer, stack = TransformerLayerCFG.create, TransformerEncoderCFG.create
-        self.model = JEPA(feature_extractor=extractor, transformer_encoder_cfg=stack(), transformer_encoder_layers_cfg=layer(norm_first=norm_first),
-                          transformer_decoder_cfg=stack(), transformer_decoder_layers_cfg=layer(d_model=384, norm_first=norm_first),
+        stack = TransformerEncoderCFG.create
+        layer = lambda **kw: dict(TransformerLayerCFG.create(norm_first=norm_first, **kw), activation=activation)   # noqa: E731
+        self.model = JEPA(feature_extractor=extractor, transformer_encoder_cfg=stack(), transformer_encoder_layers_cfg=layer(),
+                          transformer_decoder_cfg=stack(), transformer_decoder_layers_cfg=layer(d_model=384),
                           resample_sr=sr, size=model_size, process_audio_seconds=process_seconds)
         if weights is not None:
             self.model.load_state_dict(strip_compile_prefixes(weights["state_dict"]), strict=False)

@@ -1,0 +1,321 @@
+"""Whole steps with another feed-forward activation through the HIP engine against the oracle (GPU only).
+
+The oracle gets the activation by replacing its layer function (tests/act_reference.py, pinned to torch.nn.TransformerEncoderLayer by
+tests/test_activation_cpu.py).  The SMALL model, 4 clips of 2.01 s, the golden AudioSet masks; the yardstick forms and constants of
+tests/parity_yardstick.py unchanged: loss within 1e-3 relative of the oracle's bf16 flow, activations 1.1 / 2e-4, gradient groups
+1.25 / 5e-4.  Every test prints its figures before it asserts.  (A model built with activation=nn.ReLU() computed GELU before the
+activation reached the engine: the relu cases fail there.)"""
+import os
+import subprocess
+import sys
+
+import pytest
+import torch
+from torch import nn
+
+import synth
+from oracle import jepa_oracle as J
+from tests import act_reference as R
+from tests import launch
+from tests import parity_yardstick as Y
+from tests.test_jepa_gpu import SMALL, build, dev, group_of, masks, oracle_kw, rel
+from tests.test_prenorm_gpu import assert_activation_yardstick, clips
+from tests.test_recompute_gpu import DEEP, bits
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MODULES = {"gelu": None, "relu": nn.ReLU(), "gelu_tanh": nn.GELU(approximate="tanh"), "silu": nn.SiLU()}
+# the synthetic weight draw: the one of seeds 7-12 whose ReLU and GELU oracle losses lie furthest apart on the golden masks (1.4 %, checked
+# on the CPU; seed 7 gives 0.25 %; asserted in test_activation_step_parity)
+WEIGHT_SEED = 8
+
+
+def build_act(cfg, enc, dec, pre_norm=False, **kw):
+    """tests.test_jepa_gpu.build with the activation (and norm_first) set in the layer configs it creates"""
+    from wavjepa_amd import types as WT
+    saved, orig = WT.TransformerLayerCFG.__dict__["create"], WT.TransformerLayerCFG.create
+
+    def create(**k):
+        kind = enc if k.get("d_model", 768) != cfg["d_dec"] else dec
+        return orig(**dict(k, norm_first=pre_norm, activation=MODULES[kind]))
+    WT.TransformerLayerCFG.create = staticmethod(create)
+    try:
+        m, P = build(cfg, **dict(dict(seed=WEIGHT_SEED), **kw))
+    finally:
+        WT.TransformerLayerCFG.create = saved
+    assert (m.encoder.activation, m.teacher_encoder.activation, m.decoder.activation) == (enc, enc, dec)
+    return m, P
+
+
+def patch_oracle(monkeypatch, enc, dec, pre_norm=False):
+    monkeypatch.setattr(J, "post_norm_layer", R.stack_layers(enc, dec, pre_norm))
+
+
+def sign_disagreements(P, audio, dm, cfg, enc, dec, pre_norm):
+    """ReLU's derivative is a discrete event under bf16 noise: the count of linear1 outputs whose sign differs between the oracle's
+    bf16 and fp32 flows (reported beside a gradient group that misses its factor)."""
+    seen = {}
+    real = J._lin
+
+    def run(mode):
+        signs = []
+
+        def lin(x, w, b, m):
+            y = real(x, w, b, m)
+            if w.shape[0] == 4 * w.shape[1]:
+                signs.append(y.detach().float() > 0)
+            return y
+        J._lin = lin
+        try:
+            with torch.no_grad():
+                J.jepa_forward({k: v.detach() for k, v in P.items()}, audio if mode == "bf16" else audio.float(), *dm, mode=mode, **oracle_kw(cfg))
+        finally:
+            J._lin = real
+        return signs
+    a, b = run("bf16"), run("fp32")
+    seen["flipped"] = sum(int((x != y).sum()) for x, y in zip(a, b))
+    seen["of"] = sum(x.numel() for x in a)
+    return seen
+
+
+CASES = [("relu", "relu", False, True), ("relu", "relu", False, False), ("gelu_tanh", "gelu_tanh", False, True), ("silu", "silu", False, True),
+         ("silu", "silu", True, True), ("relu", "gelu", False, True)]
+
+
+@pytest.mark.parametrize("enc,dec,pre_norm,ragged", CASES)
+def test_activation_step_parity(golden_dir, monkeypatch, enc, dec, pre_norm, ragged):
+    """test_forward_backward_parity with another activation: loss, activations and parameter gradients in the yardstick forms; for the
+    mixed model, which entry each stack's linear1 took."""
+    from wavjepa_amd import ops
+    m, P = build_act(SMALL, enc, dec, pre_norm)
+    m._ensure_engine().ragged = ragged
+    ctx, tgt, vis = masks(golden_dir, 4)
+    audio = clips(4)
+    dm = [t.to(dev()) for t in (ctx, tgt, vis)]
+    tag = f"{enc}/{dec} {'pre' if pre_norm else 'post'}-norm {'ragged' if ragged else 'dense'}"
+    with torch.no_grad():
+        gelu = float(J.jepa_forward(P, audio, *dm, mode="bf16", **oracle_kw(SMALL))["loss"]) if not pre_norm else None
+    patch_oracle(monkeypatch, enc, dec, pre_norm)
+    prev, ops.PROFILE = ops.PROFILE, []
+    try:
+        out = m(audio, ctx, tgt, vis)
+        calls = [(fn, f) for fn, f, _, _ in ops.PROFILE]
+    finally:
+        ops.PROFILE = prev
+    assert m._engine.ragged_step == ragged
+    names = J.trainable_names(P)
+    for k in names:
+        P[k].requires_grad_(True)
+    ref = J.jepa_forward(P, audio, *dm, mode="bf16", **oracle_kw(SMALL))
+    ref32 = J.jepa_forward({k: v.detach() for k, v in P.items()}, audio.float(), *dm, mode="fp32", **oracle_kw(SMALL))
+    seen = (tgt if ragged else ~vis).reshape(-1, vis.shape[-1]).to(dev())
+    lo, lr_, l32 = float(out["loss"].detach()), float(ref["loss"].detach()), float(ref32["loss"])
+    print(tag, "loss hip/oracle-bf16/oracle-fp32/GELU oracle:", lo, lr_, l32, gelu, flush=True)
+    if (enc, dec) == ("relu", "relu"):
+        # the case that fails where the activation is swallowed: on this draw the two oracles are more than ten bounds apart
+        assert abs(lr_ - gelu) > 10 * 1e-3 * abs(lr_), (lr_, gelu)
+    assert_activation_yardstick(out, ref, ref32, seen, tag)
+    assert abs(lo - lr_) < 1e-3 * abs(lr_), (lo, lr_)
+    out["loss"].backward()
+    ref["loss"].backward()
+    got = {k: p.grad for k, p in m.named_parameters() if p.grad is not None}
+    gbf = {k: P[k].grad for k in names}
+    assert set(names) <= set(got)
+    _, g32 = Y.oracle_fp32_grads(J, P, audio, *dm, names, **oracle_kw(SMALL))
+    table = Y.grad_yardstick(got, gbf, g32, names, group_of)
+    print(tag, "grad yardstick (d_hip, d_orc, pair, ratio):", {g: tuple(round(v, 5) for v in r.values()) for g, r in table.items()}, flush=True)
+    if "relu" in (enc, dec) and not all(Y.grad_bound_ok(g, r) for g, r in table.items()):
+        print(tag, "linear1 sign disagreements, oracle bf16 against fp32:", sign_disagreements(P, audio, dm, SMALL, enc, dec, pre_norm), flush=True)
+    Y.assert_grad_yardstick(table)
+    # which entry each stack's linear1 took (linear1: N = 4 K, one of the two forward GELU forms)
+    gelu_epis = (ops.EPI_BIAS_GELU2, ops.EPI_BIAS_GELU)
+    act_calls = [f for fn, f in calls if fn == "wj_gemm_bf16_act"]
+    plain = [f for fn, f in calls if fn == "wj_gemm_bf16" and f["epilogue"] in gelu_epis and f["N"] == 4 * f["K"]]
+    want = {SMALL["d_enc"]: enc, SMALL["d_dec"]: dec}
+    assert {f["gemm"].K for f in act_calls} == {d for d, k in want.items() if k != "gelu"}
+    assert {f["K"] for f in plain} == {d for d, k in want.items() if k == "gelu"}
+    assert all(f["act"] == ops.ACT[want[f["gemm"].K]] for f in act_calls)
+    if enc != "gelu":        # the saving student and the teacher, which keeps nothing for a backward
+        assert {f["gemm"].epilogue for f in act_calls if f["gemm"].K == SMALL["d_enc"]} == set(gelu_epis)
+
+
+def test_activation_inference_representation(monkeypatch):
+    """get_audio_representation with relu on 3 clips, with a key-padding mask on one of them and with None, against the patched oracle."""
+    patch_oracle(monkeypatch, "relu", "relu")
+    m, P = build_act(SMALL, "relu", "relu")
+    audio = torch.from_numpy(synth.synth_audio(3, 1, 32159, seed=9)).to(dev())
+    pad = torch.zeros(3, 200, dtype=torch.bool)
+    pad[1, 150:] = True
+    kw = dict(spec=SMALL["conv_spec"], enc_heads=SMALL["h_enc"])
+    for mask in (pad.to(dev()), None):
+        rep = m.get_audio_representation(audio, mask)
+        ref = J.audio_representation(P, audio.to(torch.bfloat16), mask, mode="bf16", **kw)
+        ref32 = J.audio_representation(P, audio.to(torch.bfloat16).float(), mask, mode="fp32", **kw)
+        valid = ~pad.to(dev()) if mask is not None else torch.ones(3, 200, dtype=torch.bool, device=dev())
+        d_hip, d_orc, pair = rel(rep[valid], ref32[valid]), rel(ref[valid], ref32[valid]), rel(rep[valid], ref[valid])
+        print("relu inference, mask" if mask is not None else "relu inference, no mask", d_hip, d_orc, pair, flush=True)
+        assert d_hip < Y.ACT_FACTOR * d_orc + Y.ACT_EPS, (d_hip, d_orc)
+        assert pair < Y.PAIR_FACTOR * d_orc + Y.ACT_EPS, (pair, d_orc)
+
+
+def _one_step(golden_dir, enc, dec, cfg=SMALL, deterministic=True, **kw):
+    m, _ = build_act(cfg, enc, dec, **kw)
+    m._ensure_engine().deterministic = deterministic
+    ctx, tgt, vis = masks(golden_dir, 4)
+    out = m(clips(4), ctx, tgt, vis)
+    out["loss"].backward()
+    torch.cuda.synchronize()
+    return bits(out["loss"].detach().float().reshape(1)), m._flat.g32.clone()
+
+
+def test_deterministic_mode_and_recompute(golden_dir):
+    """Two fresh silu models in deterministic mode: loss and flat.g32 bit for bit.  gelu_tanh with activation recomputation against
+    without it (deterministic mode, the deep model of the recompute tests): the second forward goes through the same call."""
+    a, b = _one_step(golden_dir, "silu", "silu"), _one_step(golden_dir, "silu", "silu")
+    assert torch.equal(a[0], b[0]) and torch.equal(bits(a[1]), bits(b[1]))
+    assert float(a[1].abs().max()) > 0
+    off = _one_step(golden_dir, "gelu_tanh", "gelu_tanh", cfg=DEEP)
+    on = _one_step(golden_dir, "gelu_tanh", "gelu_tanh", cfg=DEEP, use_gradient_checkpointing=True)
+    assert torch.equal(off[0], on[0]) and torch.equal(bits(off[1]), bits(on[1]))
+
+
+def test_relu_training_trajectory_vs_oracle(golden_dir, monkeypatch):
+    """Three optimisation steps with relu against J.train_step under the monkeypatch, with the constants of
+    test_training_trajectory_vs_oracle: every loss within 2e-3 relative, gradient norms within 3e-2, final parameters within 2e-3."""
+    patch_oracle(monkeypatch, "relu", "relu")
+    m, P = build_act(SMALL, "relu", "relu", warmup_steps=3)
+    P = {k: v.detach().clone() for k, v in P.items()}
+    m.hparams["ema_decay"], m.hparams["ema_end_decay"], m.ema_end_step = 0.9, 0.99, 10
+    from wavjepa_amd.trainer import StepRunner
+    m.trainer.max_steps = 20
+    run = StepRunner(m)
+    ctx, tgt, vis = masks(golden_dir, 6)
+    state, worst = {}, 0.0
+    for i in range(3):
+        sl = slice(2 * (i % 3), 2 * (i % 3) + 2)
+        audio = clips(2, seed=100 + i % 3)
+        m.global_step = i
+        out = m.training_step((audio, ctx[sl], tgt[sl], vis[sl]), i)
+        out["loss"].backward()
+        run.reducer.wait()
+        run.optimizer.step()
+        run.scheduler.step()
+        r = J.train_step(P, state, i, (audio, ctx[sl].to(dev()), tgt[sl].to(dev()), vis[sl].to(dev())), mode="bf16", warmup=3,
+                         total_steps=20, ema=(0.9, 0.99, 10), **oracle_kw(SMALL))
+        lo = float(out["loss"])
+        worst = max(worst, abs(lo - r["loss"]) / abs(r["loss"]))
+        gn = float(run.optimizer.grad_norm())
+        print("relu trajectory step", i, "loss", lo, r["loss"], "grad norm", gn, r["grad_norm"], flush=True)
+        assert abs(gn - r["grad_norm"]) < 3e-2 * r["grad_norm"], (i, gn, r["grad_norm"])
+    assert worst < 2e-3, worst
+    sd = m.state_dict()
+    for k in ("encoder.layers.1.linear1.weight", "teacher_encoder.layers.1.linear1.weight", "decoder.layers.0.linear1.bias", "decoder.norm.bias"):
+        assert rel(sd[k], P[k]) < 2e-3, (k, rel(sd[k], P[k]))
+
+
+class _ReluF:
+    """torch.nn.functional with gelu <- relu: what tests/dropout_reference.py::dropout_layer calls for its activation"""
+    def __getattr__(self, name):
+        import torch.nn.functional as F
+        return F.relu if name == "gelu" else getattr(F, name)
+
+
+def test_dropout_step_with_relu(golden_dir, monkeypatch):
+    """Dropout 0.1 with relu on the 7 + 5-layer model of the dropout tests, the oracle given the engine's masks rebuilt on the host
+    (tests/dropout_reference.py): wj_dropout_rows masks act and act' alike, whatever produced them."""
+    from tests import dropout_reference as DR
+    from tests import test_dropout_gpu as TD
+    from wavjepa_amd import types as WT
+    saved, orig = WT.TransformerLayerCFG.__dict__["create"], WT.TransformerLayerCFG.create
+    WT.TransformerLayerCFG.create = staticmethod(lambda **k: orig(**dict(k, activation=nn.ReLU())))
+    try:
+        m, P = TD.build_drop(TD.P_DROP, TD.P_DROP, seed=WEIGHT_SEED)
+    finally:
+        WT.TransformerLayerCFG.create = saved
+    assert m.encoder.activation == m.decoder.activation == "relu" and m.encoder.dropout == TD.P_DROP
+    eng = m._ensure_engine()
+    m.dropout_call = 5
+    audio, (ctx, tgt, vis) = TD.draw(golden_dir)
+    out = m(audio, ctx, tgt, vis)
+    assert eng.ragged_step and eng._drop_now == dict(enc=TD.P_DROP, dec=TD.P_DROP)
+    provider = DR.EngineMasks(m._dropout_key(), 5, dict(enc=TD.P_DROP, dec=TD.P_DROP), dev(), plan=eng.plan, tail=eng.tail is not None)
+    provider.n_layers = dict(enc=DEEP["l_enc"], dec=DEEP["l_dec"])
+    DR.install(monkeypatch, provider)
+    monkeypatch.setattr(DR, "F", _ReluF())
+    names = J.trainable_names(P)
+    for k in names:
+        P[k].requires_grad_(True)
+    dm = [t.to(dev()) for t in (ctx, tgt, vis)]
+    ref = J.jepa_forward(P, audio, *dm, mode="bf16", **oracle_kw(DEEP))
+    ref32 = J.jepa_forward({k: v.detach() for k, v in P.items()}, audio.float(), *dm, mode="fp32", **oracle_kw(DEEP))
+    seen = tgt.reshape(-1, vis.shape[-1]).to(dev())
+    lo, lr_ = float(out["loss"].detach()), float(ref["loss"].detach())
+    print("relu + dropout loss hip/oracle-bf16:", lo, lr_, flush=True)
+    assert_activation_yardstick(out, ref, ref32, seen, "relu-dropout")
+    assert abs(lo - lr_) < 1e-3 * abs(lr_), (lo, lr_)
+    out["loss"].backward()
+    ref["loss"].backward()
+    got = {k: p.grad for k, p in m.named_parameters() if p.grad is not None}
+    _, g32 = Y.oracle_fp32_grads(J, P, audio, *dm, names, **oracle_kw(DEEP))
+    table = Y.grad_yardstick(got, {k: P[k].grad for k in names}, g32, names, group_of)
+    print("relu + dropout grad yardstick (d_hip, d_orc, pair, ratio):", {g: tuple(round(v, 5) for v in r.values()) for g, r in table.items()}, flush=True)
+    Y.assert_grad_yardstick(table)
+
+
+def _train(tmp_path, *overrides):
+    cmd = [sys.executable, os.path.join(ROOT, "train.py"), *overrides, "trainer.size=tiny", "trainer.batch_size=1", "data.samples_per_audio=4",
+           "trainer.steps=3", "trainer.warmup_steps=2", "trainer.log_every_n_steps=1", f"save_dir={tmp_path}"]
+    rc, out, err = launch.run(cmd, cwd=ROOT, timeout=300)
+    assert rc == 0, (out[-1500:], err[-4000:])
+    found = list(tmp_path.rglob("last.ckpt"))
+    assert len(found) == 1
+    return torch.load(found[0], map_location="cpu", weights_only=False)
+
+
+def test_launcher_writes_a_relu_checkpoint_the_hear_runtime_embeds_with(tmp_path, monkeypatch):
+    ck = _train(tmp_path / "relu", "trainer.activation=relu")
+    plain = _train(tmp_path / "plain")
+    hp = ck["hyper_parameters"]
+    assert ck["global_step"] == 3 and hp.get("activation_encoder") == "relu" and hp.get("activation_decoder") == "relu"
+    assert all(bool(torch.isfinite(v.float()).all()) for v in ck["state_dict"].values())
+    assert set(hp) - set(plain["hyper_parameters"]) == {"activation_encoder", "activation_decoder"}
+    assert not [k for k in plain["hyper_parameters"] if "activation" in k]
+    from hear_api.runtime import RuntimeJEPA
+    from wavjepa_amd.extractors import ConvFeatureExtractor
+    ext = ConvFeatureExtractor(conv_layers_spec=list(J.WAVJEPA_CONV_SPEC), in_channels=1)
+    rt = RuntimeJEPA(in_channels=1, weights=ck, is_spectrogram=False, process_seconds=2.01, extractor=ext, model_size="tiny", sr=16000,
+                     activation=hp["activation_encoder"])
+    assert rt.model.encoder.activation == "relu"
+    audio = torch.from_numpy(synth.synth_audio(2, 1, 32159, seed=31)).to(dev())
+    rep = rt.model.get_audio_representation(audio, None)
+    patch_oracle(monkeypatch, "relu", "relu")
+    P = {k: v.to(dev()) for k, v in ck["state_dict"].items()}
+    ref = J.audio_representation(P, audio.to(torch.bfloat16), None, mode="bf16", spec=list(J.WAVJEPA_CONV_SPEC), enc_heads=4)
+    print("relu checkpoint through the hear runtime against the patched oracle:", rel(rep, ref), flush=True)
+    assert rel(rep, ref) < 2e-2, rel(rep, ref)
+
+
+TRACE_CASES = ["post ragged", "post dense", "post inference", "post WJ_DETERMINISTIC=1", "both ragged"]
+# the hashes `python tools/launch_trace.py --summary <TRACE_CASES>` prints in the parent of the commit that added the activations
+PARENT_TRACE = {
+    "post ragged": "e9e6a95fdadc208f73f289d8fe9a1b61b5f8ab94c2180365cfe5e35edd26f567",
+    "post dense": "e4ad82211b6ef7b39e0eac6bfced54125a807b8cdbad1ff57f3deed03958de8f",
+    "both ragged": "b32f5b414a7e6b0f356eafeb1540dc04907d49e85b7de4cbf6deafb123ae9faa",
+    "post WJ_DETERMINISTIC=1": "241d629caafeb74f0995feabf941e79d470b206cc58376067406ca4e6ef88da6",
+    "post inference": "f3b986448aa9db3821defcab3089c2b84fcd7a9c106d845ddd20e59b7f9478bc",
+}
+
+
+def test_default_model_issues_the_parents_launches_and_never_loads_the_library():
+    """A fresh process: the default cases of tools/launch_trace.py hash to what the tree without the feature hashed to, and the
+    process that ran them has not loaded libwavjepa_hip_act.so."""
+    code = ("import runpy, sys; sys.argv = ['launch_trace.py', '--summary'] + %r; " % (TRACE_CASES,) + ""
+            f"runpy.run_path({os.path.join(ROOT, 'tools', 'launch_trace.py')!r}, run_name='__main__'); "
+            "from wavjepa_amd import _abi; print('ACT_LOADED', _abi.act_loaded()); "
+            "print('ACT_MAPPED', 'libwavjepa_hip_act' in open('/proc/self/maps').read())")
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    got = {ln.split(":")[0][3:]: ln.split("sha256 ")[1].split()[0].rstrip(";") for ln in r.stdout.splitlines() if ln.startswith("== ")}
+    print(got, flush=True)
+    assert "ACT_LOADED False" in r.stdout and "ACT_MAPPED False" in r.stdout
+    assert PARENT_TRACE and got == PARENT_TRACE

@@ -79,11 +79,20 @@ class ComponentFactory:
                   "huber": lambda: torch.nn.HuberLoss(reduction="none", delta=beta)}
         if loss not in losses:
             raise ValueError(f"Unknown trainer.loss: {loss}. Available losses: {list(losses)}")
+        # trainer.activation: the feed-forward activation of every stack (gelu | gelu_tanh | relu | silu); trainer.activation_decoder: the
+        # predictor's own (default: the same)
+        act = str(cfg.trainer.get("activation", "gelu"))
+        act_dec = str(cfg.trainer.get("activation_decoder", act))
+        acts = {"gelu": lambda: None, "gelu_tanh": lambda: torch.nn.GELU(approximate="tanh"), "relu": torch.nn.ReLU, "silu": torch.nn.SiLU}
+        for key, a in (("trainer.activation", act), ("trainer.activation_decoder", act_dec)):
+            if a not in acts:
+                raise ValueError(f"Unknown {key}: {a}. Available activations: {list(acts)}")
         try:
             return cls(feature_extractor=extractor, transformer_encoder_cfg=TransformerEncoderCFG.create(),
-                       transformer_encoder_layers_cfg=TransformerLayerCFG.create(norm_first=norm_first, dropout=drop_enc),
+                       transformer_encoder_layers_cfg=TransformerLayerCFG.create(norm_first=norm_first, dropout=drop_enc, activation=acts[act]()),
                        transformer_decoder_cfg=TransformerEncoderCFG.create(),
-                       transformer_decoder_layers_cfg=TransformerLayerCFG.create(d_model=384, norm_first=norm_first_dec, dropout=drop_dec),
+                       transformer_decoder_layers_cfg=TransformerLayerCFG.create(d_model=384, norm_first=norm_first_dec, dropout=drop_dec,
+                                                                                 activation=acts[act_dec]()),
                        lr=cfg.optimizer.lr,
                        adam_betas=(cfg.optimizer.b1, cfg.optimizer.b2), adam_weight_decay=cfg.optimizer.weight_decay,
                        resample_sr=cfg.data.sr, process_audio_seconds=cfg.data.process_seconds,

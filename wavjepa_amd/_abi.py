@@ -111,10 +111,44 @@ MONITOR_LIB_PATH = os.path.join(HERE, "lib", "libwavjepa_hip_monitor.so")
 _MON = Header(MONITOR_HEADER, known=_HEADER)
 MONITOR_STRUCTS, MONITOR_FUNCTIONS, MONITOR_ENTRY_ARGS, MONITOR_DEFINES = _MON.struct_types, list(_MON.functions), dict(_MON.entry_args), _MON.defines
 
+# libwavjepa_hip_act.so (wj_gemm_bf16_act: linear1's forward GEMM with the activation chosen per call): likewise
+ACT_HEADER = os.path.join(os.path.dirname(HERE), "include", "wavjepa_hip_act.h")
+ACT_LIB_PATH = os.path.join(HERE, "lib", "libwavjepa_hip_act.so")
+_ACT = Header(ACT_HEADER, known=_HEADER)
+ACT_STRUCTS, ACT_FUNCTIONS, ACT_ENTRY_ARGS, ACT_ENUMS = _ACT.struct_types, list(_ACT.functions), dict(_ACT.entry_args), _ACT.enums
+
 _lib = None
 _lab_lib = None
 _dropout_lib = None
 _monitor_lib = None
+_act_lib = None
+
+
+def act_loaded() -> bool:
+    """True once libwavjepa_hip_act.so is in the process (a model whose stacks all run GELU never loads it)."""
+    return _act_lib is not None
+
+
+def load_act():
+    """libwavjepa_hip_act.so (once), its struct sizes cross-checked against its own wj_act_struct_size.  Loaded behind the release
+    library, as load_dropout() does."""
+    global _act_lib
+    if _act_lib is None:
+        load()
+        if not os.path.exists(ACT_LIB_PATH):
+            raise WavJepaHipError(f"{ACT_LIB_PATH} is missing: run `python -m wavjepa_amd.build` (or __graft_entry__.build())")
+        lib = ctypes.CDLL(ACT_LIB_PATH)
+        for fn in ACT_FUNCTIONS:
+            if not hasattr(lib, fn):
+                raise WavJepaHipError(f"{ACT_LIB_PATH} does not export {fn} (declared in include/wavjepa_hip_act.h); rebuild it")
+            f = getattr(lib, fn)
+            f.restype, f.argtypes = _ACT.functions[fn]
+        for name, cls in ACT_STRUCTS.items():
+            want = lib.wj_act_struct_size(name.encode())
+            if want != ctypes.sizeof(cls):
+                raise WavJepaHipError(f"struct {name}: header mirror is {ctypes.sizeof(cls)} bytes, library says {want}")
+        _act_lib = lib
+    return _act_lib
 
 
 def load_monitor():
@@ -217,6 +251,8 @@ def workspace_bytes(fn_name: str, args_struct) -> int:
         n = int(load_dropout().wj_dropout_workspace_bytes(fn_name.encode(), ctypes.byref(args_struct)))
     elif fn_name in MONITOR_ENTRY_ARGS:
         n = int(load_monitor().wj_monitor_workspace_bytes(fn_name.encode(), ctypes.byref(args_struct)))
+    elif fn_name in ACT_ENTRY_ARGS:
+        n = int(load_act().wj_act_workspace_bytes(fn_name.encode(), ctypes.byref(args_struct)))
     else:
         n = int(load().wj_workspace_bytes(fn_name.encode(), ctypes.byref(args_struct)))
     if n < 0:
@@ -228,7 +264,10 @@ _ERR = {-1: "invalid argument", -2: "kernel launch failed", -3: "unsupported con
 
 
 def call(fn_name: str, args_struct, stream: int, lab: bool = False) -> None:
-    lib = load_dropout() if fn_name in DROPOUT_ENTRY_ARGS else (load_monitor() if fn_name in MONITOR_ENTRY_ARGS else (load_lab() if lab else load()))
+    if fn_name in ACT_ENTRY_ARGS:
+        lib = load_act()
+    else:
+        lib = load_dropout() if fn_name in DROPOUT_ENTRY_ARGS else (load_monitor() if fn_name in MONITOR_ENTRY_ARGS else (load_lab() if lab else load()))
     rc = getattr(lib, fn_name)(ctypes.byref(args_struct), stream)
     if rc != 0:
         raise WavJepaHipError(f"{fn_name} failed: {_ERR.get(rc, rc)}")

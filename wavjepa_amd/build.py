@@ -25,6 +25,11 @@ DROPOUT_FLAGS = ["-DWJ_DROPOUT_LIB", "-fvisibility=hidden"]
 MONITOR_LIB = os.path.join(LIBDIR, "libwavjepa_hip_monitor.so")
 MONITOR_SOURCES = ["monitor.hip"]
 MONITOR_FLAGS = ["-fvisibility=hidden"]
+# libwavjepa_hip_act.so (include/wavjepa_hip_act.h): wj_gemm_bf16_act, linear1's forward GEMM with the activation chosen per call, from
+# the SAME GEMM sources with -DWJ_ACT_LIB (the one-tile and the persistent kernels; the activation is a template argument there)
+ACT_LIB = os.path.join(LIBDIR, "libwavjepa_hip_act.so")
+ACT_SOURCES = ["gemm.hip", "gemm_persist.hip", "act_abi.hip"]
+ACT_FLAGS = ["-DWJ_ACT_LIB", "-fvisibility=hidden"]
 
 
 def _hipcc() -> str:
@@ -41,19 +46,19 @@ def _stale(target: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force: bool = False, verbose: bool = True, lab: bool = False, dropout: bool = False, monitor: bool = False) -> str:
+def build(force: bool = False, verbose: bool = True, lab: bool = False, dropout: bool = False, monitor: bool = False, act: bool = False) -> str:
     """The release library (compute + query entries, production-safe switches only), or with lab=True the laboratory variant
     (libwavjepa_hip_lab.so: -DWJ_LAB, the extra entries of include/wavjepa_hip_lab.h and every A/B / diagnostic environment switch),
-    or with dropout=True libwavjepa_hip_dropout.so, or with monitor=True libwavjepa_hip_monitor.so."""
+    or with dropout=True libwavjepa_hip_dropout.so, or with monitor=True libwavjepa_hip_monitor.so, or with act=True libwavjepa_hip_act.so."""
     hipcc = _hipcc()
     os.makedirs(LIBDIR, exist_ok=True)
-    objdir = os.path.join(LIBDIR, "obj_monitor" if monitor else ("obj_dropout" if dropout else ("obj_lab" if lab else "obj")))
+    objdir = os.path.join(LIBDIR, "obj_act" if act else ("obj_monitor" if monitor else ("obj_dropout" if dropout else ("obj_lab" if lab else "obj"))))
     os.makedirs(objdir, exist_ok=True)
     inc = os.path.join(os.path.dirname(HERE), "include")
     headers = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(inc, "*.h"))
-    flags = FLAGS + (MONITOR_FLAGS if monitor else (DROPOUT_FLAGS if dropout else (["-DWJ_LAB"] if lab else [])))
-    lib = MONITOR_LIB if monitor else (DROPOUT_LIB if dropout else (LAB_LIB if lab else LIB))
-    sources = MONITOR_SOURCES if monitor else (DROPOUT_SOURCES if dropout else SOURCES)
+    flags = FLAGS + (ACT_FLAGS if act else (MONITOR_FLAGS if monitor else (DROPOUT_FLAGS if dropout else (["-DWJ_LAB"] if lab else []))))
+    lib = ACT_LIB if act else (MONITOR_LIB if monitor else (DROPOUT_LIB if dropout else (LAB_LIB if lab else LIB)))
+    sources = ACT_SOURCES if act else (MONITOR_SOURCES if monitor else (DROPOUT_SOURCES if dropout else SOURCES))
     jobs = []
     for src in sources:
         s = os.path.join(CSRC, src)
@@ -82,7 +87,7 @@ def build(force: bool = False, verbose: bool = True, lab: bool = False, dropout:
             raise RuntimeError(f"link failed:\n{r.stderr}")
         if verbose:
             print(f"[wavjepa_amd.build] linked {lib}", file=sys.stderr)
-    if not lab and not dropout and not monitor:
+    if not lab and not dropout and not monitor and not act:
         build_io(force=force, verbose=verbose)
     return lib
 
@@ -92,6 +97,7 @@ def build_all(force: bool = False, verbose: bool = True) -> None:
     build(force=force, verbose=verbose)
     build(force=force, verbose=verbose, dropout=True)
     build(force=force, verbose=verbose, monitor=True)
+    build(force=force, verbose=verbose, act=True)
     build(force=force, verbose=verbose, lab=True)
 
 

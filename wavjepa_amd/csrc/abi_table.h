@@ -75,6 +75,10 @@
     W(wj_attn_stream_bwd_drop, wj_attn_bwd_drop_args, wj_attn_bwd_drop_ws_bytes)
 #define WJ_DROPOUT_OTHER_STRUCTS(S) S(wj_dropout_args)
 
+// libwavjepa_hip_act.so (include/wavjepa_hip_act.h, csrc/act_abi.hip): the same two row forms (the forward GELU forms take no scratch)
+#define WJ_ACT_ENTRIES(E, W)                                                           \
+    E(wj_gemm_bf16_act, wj_gemm_act_args)
+
 // libwavjepa_hip_monitor.so (include/wavjepa_hip_monitor.h, csrc/monitor.hip): the same two row forms
 #define WJ_MONITOR_ENTRIES(E, W)                                                       \
     W(wj_masked_moments, wj_moments_args, wj_masked_moments_ws_bytes)

@@ -151,6 +151,94 @@ __device__ __forceinline__ void gelu_bf16x8(const bf16x8 h, bf16x8& g, bf16x8& g
     }
 }
 
+// The other feed-forward activations of linear1's epilogues (libwavjepa_hip_act.so, include/wavjepa_hip_act.h: the values of wj_act),
+// two elements at a time like gelu_pk: act(h) and act'(h) in fp32 from the bf16 h, as torch defines them on a bf16 tensor.
+// EVERY finite bf16 h gives finite outputs, and beyond saturation act' is exactly 1 / 0:
+//   relu       (h < 0) ? 0 : h and (h > 0) ? 1 : 0: two compares, two selects; -0 stays -0 and NaN passes, as torch.relu on a bf16
+//              tensor; act' = 0 at h == 0 (torch's threshold_backward).
+//   silu       s = 1 / (1 + exp(-h)) as v_rcp_f32(1 + v_exp_f32(-h log2 e)).  exp overflows to +inf (h < -88.7) -> s = +0 exactly,
+//              underflows to 0 (h > 104) -> s = 1 exactly; act = h s, act' = s + (h s)(1 - s) as one fma: with s in {0, 1} that is
+//              fma(-0, 1, 0) = 0 or fma(h, 0, 1) = 1, no 0 * inf anywhere (h s is finite: |h s| <= |h|).
+//   gelu_tanh  0.5 (1 + tanh(u)) = 1 / (1 + exp(-2u)) =: s, u = c (h + 0.044715 h^3): the same exp / rcp pair, no tanh.  act = h s,
+//              act' = s + s (1 - s) . 2c h (1 + 0.134145 h^2) (1 - tanh^2 = 4 s (1 - s)).  h^2, h^3 and the polynomial are taken of
+//              hc = med3(h, -16, 16): at |h| = 16 the exponent is -+459, far outside fp32, so s and s (1 - s) are exactly what they
+//              are for every larger |h|, and nothing but the exp ever leaves the finite range.  act = h s uses the unclamped h.
+// VALU instructions per 8 outputs of act' + act / of act alone, counted around act_bf16x8 in a stand-alone kernel (unpack and the
+// bf16 conversions included), and the VGPRs of the persistent BIAS_GELU2 kernel (tools/kernel_resources.py on the -DWJ_ACT_LIB build):
+// gelu_pk 98 / 86, 225;  relu 49 / 29, 222;  gelu_tanh 84 / 59, 226;  silu 53 / 41, 225.  The 256 x 128 and eight-phase kernels hold
+// 108 and 228 VGPRs for every kind.  ("Feed-forward activation".)
+constexpr int ACT_GELU = 0, ACT_RELU = 1, ACT_GELU_TANH = 2, ACT_SILU = 3;    // = wj_act (include/wavjepa_hip_act.h)
+constexpr int ACT_KINDS = 4;
+
+template <bool WANT_GRAD>
+__device__ __forceinline__ void relu_pk(const f32x2 x, f32x2& g, f32x2& gp) {
+    g.x = x.x < 0.f ? 0.f : x.x;
+    g.y = x.y < 0.f ? 0.f : x.y;
+    if constexpr (WANT_GRAD) {
+        gp.x = x.x > 0.f ? 1.f : 0.f;
+        gp.y = x.y > 0.f ? 1.f : 0.f;
+    }
+}
+template <bool WANT_GRAD>
+__device__ __forceinline__ void silu_pk(const f32x2 x, f32x2& g, f32x2& gp) {
+    const f32x2 u = x * (-1.44269504088896340736f);
+    f32x2 e, s;
+    e.x = __builtin_amdgcn_exp2f(u.x);
+    e.y = __builtin_amdgcn_exp2f(u.y);
+    const f32x2 d = e + 1.0f;
+    s.x = __builtin_amdgcn_rcpf(d.x);
+    s.y = __builtin_amdgcn_rcpf(d.y);
+    g = x * s;
+    if constexpr (WANT_GRAD) gp = __builtin_elementwise_fma(g, 1.0f - s, s);
+}
+template <bool WANT_GRAD>
+__device__ __forceinline__ void gelu_tanh_pk(const f32x2 x, f32x2& g, f32x2& gp) {
+    constexpr float C2 = 2.0f * 0.79788456080286535588f;                 // 2 sqrt(2 / pi)
+    constexpr float KE = -C2 * 1.44269504088896340736f;                  // exp(-2u) = exp2(KE hc (1 + 0.044715 hc^2))
+    f32x2 hc, e, s;
+    hc.x = __builtin_amdgcn_fmed3f(x.x, -16.0f, 16.0f);
+    hc.y = __builtin_amdgcn_fmed3f(x.y, -16.0f, 16.0f);
+    const f32x2 q = hc * hc;
+    const f32x2 a = hc * __builtin_elementwise_fma(q, f32x2{KE * 0.044715f, KE * 0.044715f}, f32x2{KE, KE});
+    e.x = __builtin_amdgcn_exp2f(a.x);
+    e.y = __builtin_amdgcn_exp2f(a.y);
+    const f32x2 d = e + 1.0f;
+    s.x = __builtin_amdgcn_rcpf(d.x);
+    s.y = __builtin_amdgcn_rcpf(d.y);
+    g = x * s;
+    if constexpr (WANT_GRAD) {
+        const f32x2 w = hc * __builtin_elementwise_fma(q, f32x2{C2 * 0.134145f, C2 * 0.134145f}, f32x2{C2, C2});
+        gp = __builtin_elementwise_fma(s * (1.0f - s), w, s);
+    }
+}
+template <int ACT, bool WANT_GRAD>
+__device__ __forceinline__ void act_pk(const f32x2 x, f32x2& g, f32x2& gp) {
+    static_assert(ACT >= 0 && ACT < ACT_KINDS, "activation kind");
+    if constexpr (ACT == ACT_RELU) relu_pk<WANT_GRAD>(x, g, gp);
+    else if constexpr (ACT == ACT_GELU_TANH) gelu_tanh_pk<WANT_GRAD>(x, g, gp);
+    else if constexpr (ACT == ACT_SILU) silu_pk<WANT_GRAD>(x, g, gp);
+    else gelu_pk<WANT_GRAD>(x, g, gp);
+}
+// 8 bf16 in, act (and act') as 8 bf16 out; ACT_GELU is gelu_bf16x8 itself
+template <int ACT, bool WANT_GRAD>
+__device__ __forceinline__ void act_bf16x8(const bf16x8 h, bf16x8& g, bf16x8& gp) {
+    if constexpr (ACT == ACT_GELU) {
+        gelu_bf16x8<WANT_GRAD>(h, g, gp);
+    } else {
+        typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_;
+        const u32x4_ w = __builtin_bit_cast(u32x4_, h);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            f32x2 x, a, b;
+            x.x = __uint_as_float(w[j] << 16);
+            x.y = __uint_as_float(w[j] & 0xffff0000u);
+            act_pk<ACT, WANT_GRAD>(x, a, b);
+            g[2 * j] = f2bf(a.x); g[2 * j + 1] = f2bf(a.y);
+            if constexpr (WANT_GRAD) { gp[2 * j] = f2bf(b.x); gp[2 * j + 1] = f2bf(b.y); }
+        }
+    }
+}
+
 // XCD-aware bijective remap of a linear workgroup id: blocks b and b+8 share an XCD (round-robin dispatch),
 // so give each XCD a contiguous chunk of the logical id space (neighbouring tiles then share that XCD's L2).
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {

@@ -519,7 +519,8 @@ __device__ __forceinline__ void pair_exchange(f32x4 (&acc)[8][4], const EpiArgs&
 // the list is padded with >= 256 readable entries).
 // The body of one workgroup: `bid` of `nwg` workgroups of ONE problem (the plain kernel passes blockIdx / gridDim; the grouped
 // kernel below passes the workgroup's position inside its problem of the group).
-template <bool AT, bool BT, int EPI, int BN, int SCHED, int GATHER = 0, int BMT = 256>
+// ACT: the activation of the forward GELU form (common.h: ACT_*; anything but ACT_GELU is launched by wj_gemm_bf16_act only).
+template <bool AT, bool BT, int EPI, int BN, int SCHED, int GATHER = 0, int BMT = 256, int ACT = ACT_GELU>
 __device__ __forceinline__ void gemm3_body(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, long lda, long ldb, int M, int N,
                                            int K, int tiles_n, int split_k, int k_per_split, const EpiArgs& e, int bid, int nwg,
                                            bool remapped = false) {
@@ -532,6 +533,7 @@ __device__ __forceinline__ void gemm3_body(const bf16_t* __restrict__ A, const b
     static_assert(GATHER == 0 || SCHED == 0, "gather forms use the plain schedule");
     static_assert(SCHED < 2 || (!AT && !BT), "eight-phase schedules: row-form operands");
     static_assert(SCHED != 3 || EPI == WJ_EPI_BF16 || EPI == WJ_EPI_BIAS_GELU2, "MX fp8 loop: forward epilogues");
+    static_assert(ACT == ACT_GELU || (EPI == WJ_EPI_BIAS_GELU2 && SCHED != 3 && GATHER == 0), "activations: the bf16 forward GELU form");
     static_assert(GATHER != 1 || (!AT && (EPI == WJ_EPI_BF16 || EPI == WJ_EPI_MUL_GELU_GRAD_Z)), "row gather: row-form A, bf16 output");
     static_assert(EPI != WJ_EPI_MUL_GELU_GRAD_Z || GATHER == 1, "gelu'(z) epilogue: built for the sparse conv dgrad");
     static_assert(GATHER != 2 || (AT && BT && BN == 256), "k gather: col-form A and B, 256-wide tiles");
@@ -873,8 +875,8 @@ __device__ __forceinline__ void gemm3_body(const bf16_t* __restrict__ A, const b
                     // WJ_EPI_BIAS_GELU (forward only, e.C2 == NULL): C = gelu(h) and nothing else.
                     bf16x8 gl, gp;
                     if (e.q_out) {                                // kernel-uniform: MX fp8 of gelu(h) for the next GEMM (config 5)
-                        if (e.C2) gelu_bf16x8<true>(v, gl, gp);
-                        else gelu_bf16x8<false>(v, gl, gp);
+                        if (e.C2) act_bf16x8<ACT, true>(v, gl, gp);
+                        else act_bf16x8<ACT, false>(v, gl, gp);
                         float f[8], amax = 0.f;
 #pragma unroll
                         for (int x = 0; x < 8; ++x) { f[x] = bf2f(gl[x]); amax = fmaxf(amax, fabsf(f[x])); }
@@ -906,11 +908,11 @@ __device__ __forceinline__ void gemm3_body(const bf16_t* __restrict__ A, const b
                             *reinterpret_cast<bf16x8*>((bf16_t*)e.C + off) = gl;
                         }
                     } else if (e.C2) {                            // kernel-uniform
-                        gelu_bf16x8<true>(v, gl, gp);
+                        act_bf16x8<ACT, true>(v, gl, gp);
                         *reinterpret_cast<bf16x8*>((bf16_t*)e.C + off) = gp;
                         *reinterpret_cast<bf16x8*>((bf16_t*)e.C2 + off) = gl;
                     } else {
-                        gelu_bf16x8<false>(v, gl, gp);
+                        act_bf16x8<ACT, false>(v, gl, gp);
                         *reinterpret_cast<bf16x8*>((bf16_t*)e.C + off) = gl;
                     }
                 } else if constexpr (EPI == WJ_EPI_MUL_GELU_GRAD) {
@@ -987,11 +989,11 @@ __device__ __forceinline__ void gemm3_body(const bf16_t* __restrict__ A, const b
     }
 }
 
-template <bool AT, bool BT, int EPI, int BN, int SCHED, int GATHER = 0>
+template <bool AT, bool BT, int EPI, int BN, int SCHED, int GATHER = 0, int ACT = ACT_GELU>
 __global__ __launch_bounds__(NT, BN == 256 ? 1 : 2) void gemm3_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B,
                                                                       long lda, long ldb, int M, int N, int K, int tiles_n,
                                                                       int split_k, int k_per_split, EpiArgs e) {
-    gemm3_body<AT, BT, EPI, BN, SCHED, GATHER>(A, B, lda, ldb, M, N, K, tiles_n, split_k, k_per_split, e, blockIdx.x, gridDim.x);
+    gemm3_body<AT, BT, EPI, BN, SCHED, GATHER, 256, ACT>(A, B, lda, ldb, M, N, K, tiles_n, split_k, k_per_split, e, blockIdx.x, gridDim.x);
 }
 
 // ---- grouped split-K weight gradients -----------------------------------------------------------------------------------------
@@ -1097,7 +1099,7 @@ bool pair_shape(const wj_gemm_args* a) {
     return tiles > 32 && tiles <= 128;            // 2 x tiles workgroups fit the chip in one round (<= 32 tiles would want a deeper split)
 }
 
-template <bool AT, bool BT, int EPI, int BN, int SCHED, int GATHER = 0>
+template <bool AT, bool BT, int EPI, int BN, int SCHED, int GATHER = 0, int ACT = ACT_GELU>
 int launch(const wj_gemm_args* a, hipStream_t s) {
     const int tiles_m = (a->M + BM - 1) / BM, tiles_n = (a->N + BN - 1) / BN;
     int split, kps;
@@ -1118,8 +1120,8 @@ int launch(const wj_gemm_args* a, hipStream_t s) {
     }
     // pairs: every XCD gets both roles of its run of tiles (ceil(tiles / 8) of each; spare workgroups leave at once)
     const int nwg = pair ? 16 * ((tiles_m * tiles_n + 7) / 8) : tiles_m * tiles_n * split;
-    return launch_with_lds<gemm3_kernel<AT, BT, EPI, BN, SCHED, GATHER>>(dim3(nwg), Cfg<BN>::LDS_BYTES, s, (const bf16_t*)a->A, (const bf16_t*)a->B,
-                                                                         (long)a->lda, (long)a->ldb, a->M, a->N, a->K, tiles_n, split, kps, e);
+    return launch_with_lds<gemm3_kernel<AT, BT, EPI, BN, SCHED, GATHER, ACT>>(dim3(nwg), Cfg<BN>::LDS_BYTES, s, (const bf16_t*)a->A, (const bf16_t*)a->B,
+                                                                              (long)a->lda, (long)a->ldb, a->M, a->N, a->K, tiles_n, split, kps, e);
 }
 
 // Deterministic form of the split-K weight gradient (col-form A and B; GATHER 2: the sparse conv wgrad over its row list): the K slices
@@ -1242,6 +1244,57 @@ int dispatch_epi(const wj_gemm_args* a, hipStream_t s) {
 }
 
 }  // namespace
+
+#ifdef WJ_ACT_LIB
+// ---- libwavjepa_hip_act.so (include/wavjepa_hip_act.h): the forward GELU form with the activation as a template argument ------------
+// Built from this file and csrc/gemm_persist.hip with -DWJ_ACT_LIB -fvisibility=hidden; the entries of libwavjepa_hip.so below are
+// not part of it.  The variant comes from pick_variant, so a call takes the schedule wj_gemm_bf16 would give it; the row-panel and
+// deferred-epilogue schedules are not in this library (never picked by themselves in a release build, refused here when forced).
+#include "../../include/wavjepa_hip_act.h"
+static_assert(WJ_ACT_GELU == ACT_GELU && WJ_ACT_RELU == ACT_RELU && WJ_ACT_GELU_TANH == ACT_GELU_TANH && WJ_ACT_SILU == ACT_SILU &&
+              WJ_ACT_SILU + 1 == ACT_KINDS, "wj_act and common.h's ACT_* are one list");
+bool wj_gemm_pde_eligible(const wj_gemm_args*) { return false; }
+bool wj_gemm_panel_eligible(const wj_gemm_args*) { return false; }
+
+namespace {
+template <int ACT>
+int launch_act(const wj_gemm_args* a, hipStream_t s) {
+    int v = pick_variant(a);
+    if (v == 4) {
+        const int rc = wj_gemm_persist_launch_act(a, ACT, s);
+        if (rc != WJ_ERR_UNSUPPORTED) return rc;
+        v = 3;                                   // no scheduling slot for this stream: the one-tile-per-workgroup form
+    }
+    if (v == 3) return launch<false, false, WJ_EPI_BIAS_GELU2, 256, 2, 0, ACT>(a, s);   // one instantiation, C2 == NULL selects the single output
+    return launch<false, false, WJ_EPI_BIAS_GELU2, 128, 0, 0, ACT>(a, s);
+}
+}  // namespace
+
+extern "C" __attribute__((visibility("default"))) int wj_gemm_bf16_act(const wj_gemm_act_args* aa, void* stream) {
+    WJ_CLEAR_STALE_ERROR();
+    if (!aa) return WJ_ERR_ARG;
+    const wj_gemm_args* a = &aa->gemm;
+    if (aa->act < 0 || aa->act >= ACT_KINDS) return WJ_ERR_ARG;
+    if (a->epilogue != WJ_EPI_BIAS_GELU2 && a->epilogue != WJ_EPI_BIAS_GELU) return WJ_ERR_ARG;
+    // the checks of wj_gemm_bf16 that bear on the forward GELU forms
+    if (!a->A || !a->B || !a->C) return WJ_ERR_ARG;
+    if (a->M <= 0 || a->N <= 0 || a->K <= 0) return WJ_ERR_ARG;
+    if ((a->N & 7) || (a->K & 7) || (a->lda & 7) || (a->ldb & 7) || (a->ldc & 7)) return WJ_ERR_ARG;
+    if (((uintptr_t)a->A | (uintptr_t)a->B | (uintptr_t)a->C) & 15) return WJ_ERR_ARG;
+    if (a->epilogue == WJ_EPI_BIAS_GELU2 && !a->C2) return WJ_ERR_ARG;
+    if (a->split_k > 1 || a->colsum || a->rowmap) return WJ_ERR_ARG;
+    if (a->schedule < 0 || a->schedule > 7 || a->persist_cus < 0 || a->persist_cus > 32) return WJ_ERR_ARG;
+    if (a->a_trans || a->b_trans) return WJ_ERR_UNSUPPORTED;
+    if (a->schedule == 2 || a->schedule == 3 || a->schedule == 6 || a->schedule == 7) return WJ_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    switch (aa->act) {
+        case WJ_ACT_RELU: return launch_act<ACT_RELU>(a, s);
+        case WJ_ACT_GELU_TANH: return launch_act<ACT_GELU_TANH>(a, s);
+        case WJ_ACT_SILU: return launch_act<ACT_SILU>(a, s);
+        default: return launch_act<ACT_GELU>(a, s);
+    }
+}
+#else
 
 template <int EPI>
 int launch_fp8(const wj_gemm_fp8_args* a, hipStream_t s) {
@@ -1440,3 +1493,4 @@ extern "C" int wj_gemm_bf16(const wj_gemm_args* a, void* stream) {
     if (a->a_trans && a->b_trans) return dispatch_epi<true, true>(a, s);
     return dispatch_epi<true, false>(a, s);
 }
+#endif   // !WJ_ACT_LIB

@@ -10,6 +10,8 @@
 bool wj_gemm_persist_eligible(const wj_gemm_args* a);
 // WJ_OK, or WJ_ERR_UNSUPPORTED (not eligible / no scheduling slot left for this stream: the caller takes another variant)
 int wj_gemm_persist_launch(const wj_gemm_args* a, hipStream_t s);
+// libwavjepa_hip_act.so (-DWJ_ACT_LIB) in its place: the two forward GELU forms with activation `act` (common.h: ACT_*)
+int wj_gemm_persist_launch_act(const wj_gemm_args* a, int act, hipStream_t s);
 
 // the stream's set of 8 tile counters (zero between launches), or NULL when no set is free; *dev_out = the current device
 unsigned* wj_gemm_persist_counters(hipStream_t s, int* dev_out);

@@ -225,7 +225,8 @@ __device__ __forceinline__ u32x4 mul_bf16x8(const u32x4& v, const u32x4& g, floa
 // transposed across the lane groups with seven shuffles (each lane ends with ONE column) and added with one 256-B atomic per wave.
 // skip_rows: the first rows of a tile that was shifted inwards at the M edge belong to its neighbour as well -- stored twice with the
 // same bits, but counted once.
-template <int EPI, bool HALF>
+// ACT: the activation of BIAS_GELU / BIAS_GELU2 (common.h: ACT_*; anything but ACT_GELU is launched by wj_gemm_bf16_act only).
+template <int EPI, bool HALF, int ACT = ACT_GELU>
 __device__ __forceinline__ void epilogue_regs(f32x4 (&acc)[8][4], char* smem, const PArgs& a, int m0, int n0, int skip_rows, int wave,
                                               int lane) {
     constexpr int NI = HALF ? 2 : 4;
@@ -329,8 +330,8 @@ __device__ __forceinline__ void epilogue_regs(f32x4 (&acc)[8][4], char* smem, co
                 h[1] = f32x2{bf2f(f2bf(v[2])), bf2f(f2bf(v[3]))};
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
-                    if constexpr (EPI == WJ_EPI_BIAS_GELU2) gelu_pk<true>(h[q], gl[q], gp[q]);
-                    else gelu_pk<false>(h[q], gl[q], gp[q]);
+                    if constexpr (EPI == WJ_EPI_BIAS_GELU2) act_pk<ACT, true>(h[q], gl[q], gp[q]);
+                    else act_pk<ACT, false>(h[q], gl[q], gp[q]);
                 }
                 if constexpr (EPI == WJ_EPI_CONV_GELU) {
 #pragma unroll
@@ -357,8 +358,9 @@ __device__ __forceinline__ void epilogue_regs(f32x4 (&acc)[8][4], char* smem, co
     }
 }
 
-template <int EPI>
+template <int EPI, int ACT = ACT_GELU>
 __global__ __launch_bounds__(GEMM_NT, 1) void gemm_persist_kernel(PArgs a) {
+    static_assert(ACT == ACT_GELU || EPI == WJ_EPI_BIAS_GELU2 || EPI == WJ_EPI_BIAS_GELU, "activations: the forward GELU forms");
     constexpr int LAGF = StoreCount<EPI, false>::N + TopDmaCount<EPI>::N;   // + the DMAs of the block that precedes an output item's first K tile
     constexpr int LAGH = StoreCount<EPI, true>::N + TopDmaCount<EPI>::N;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -548,8 +550,8 @@ __global__ __launch_bounds__(GEMM_NT, 1) void gemm_persist_kernel(PArgs a) {
         // 0-3 here and one for waves 4-7 behind the epilogue keep the lag and put both epilogues side by side.
         if (wm == 0) __builtin_amdgcn_s_barrier();
         asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");     // MFMA results of the last phase -> VALU readers behind the loop branch
-        if (half0) epilogue_regs<EPI, true>(acc, smem, a, m0, n0, skip0, wave, lane);
-        else epilogue_regs<EPI, false>(acc, smem, a, m0, n0, skip0, wave, lane);
+        if (half0) epilogue_regs<EPI, true, ACT>(acc, smem, a, m0, n0, skip0, wave, lane);
+        else epilogue_regs<EPI, false, ACT>(acc, smem, a, m0, n0, skip0, wave, lane);
         __builtin_amdgcn_sched_barrier(0);
         if (wm == 1) __builtin_amdgcn_s_barrier();
         stamp();
@@ -618,7 +620,7 @@ int persist_stagger(const wj_gemm_args* a) {
     return us * 100;
 }
 
-template <int EPI>
+template <int EPI, int ACT = ACT_GELU>
 int launch_persist(const wj_gemm_args* a, hipStream_t s, unsigned* ctr) {
     PArgs p;
     p.set(a);
@@ -661,7 +663,7 @@ int launch_persist(const wj_gemm_args* a, hipStream_t s, unsigned* ctr) {
 #endif
         }
     }
-    const int rc = launch_with_lds<gemm_persist_kernel<EPI>>(dim3(8 * p.wpx), LDS_TOTAL, s, p);
+    const int rc = launch_with_lds<gemm_persist_kernel<EPI, ACT>>(dim3(8 * p.wpx), LDS_TOTAL, s, p);
     if (rc != WJ_OK) return rc;
     if (p.active < 32) (void)hipMemsetAsync(ctr, 0, 8 * CTR_STRIDE * sizeof(unsigned), s);   // diagnostic: idle workgroups made no pulls, the counters did not wrap
     return WJ_OK;
@@ -767,6 +769,27 @@ unsigned* wj_gemm_persist_counters(hipStream_t s, int* dev_out) {
     return T.base[dev] + (size_t)slot * 8 * CTR_STRIDE;
 }
 
+#ifdef WJ_ACT_LIB
+// libwavjepa_hip_act.so: the two forward GELU forms per activation, and nothing else of this file's launches
+template <int ACT>
+static int launch_persist_act(const wj_gemm_args* a, hipStream_t s, unsigned* ctr) {
+    if (a->epilogue == WJ_EPI_BIAS_GELU2) return launch_persist<WJ_EPI_BIAS_GELU2, ACT>(a, s, ctr);
+    if (a->epilogue == WJ_EPI_BIAS_GELU) return launch_persist<WJ_EPI_BIAS_GELU, ACT>(a, s, ctr);
+    return WJ_ERR_UNSUPPORTED;
+}
+int wj_gemm_persist_launch_act(const wj_gemm_args* a, int act, hipStream_t s) {
+    if (!wj_gemm_persist_eligible(a)) return WJ_ERR_UNSUPPORTED;
+    unsigned* ctr = wj_gemm_persist_counters(s, nullptr);
+    if (!ctr) return WJ_ERR_UNSUPPORTED;
+    switch (act) {
+        case ACT_GELU: return launch_persist_act<ACT_GELU>(a, s, ctr);
+        case ACT_RELU: return launch_persist_act<ACT_RELU>(a, s, ctr);
+        case ACT_GELU_TANH: return launch_persist_act<ACT_GELU_TANH>(a, s, ctr);
+        case ACT_SILU: return launch_persist_act<ACT_SILU>(a, s, ctr);
+        default: return WJ_ERR_UNSUPPORTED;
+    }
+}
+#else
 int wj_gemm_persist_launch(const wj_gemm_args* a, hipStream_t s) {
     if (!wj_gemm_persist_eligible(a)) return WJ_ERR_UNSUPPORTED;
     unsigned* ctr = wj_gemm_persist_counters(s, nullptr);
@@ -780,3 +803,4 @@ int wj_gemm_persist_launch(const wj_gemm_args* a, hipStream_t s) {
         default: return WJ_ERR_UNSUPPORTED;
     }
 }
+#endif   // !WJ_ACT_LIB

@@ -129,6 +129,9 @@ class Denoiser(_ModuleBase):
         if enc_l.get("norm_first", False):
             raise NotImplementedError("the Denoiser stage runs post-norm stacks only (norm_first=False); pre-norm is a JEPA pre-training option")
         self.encoder = TransformerStack(enc_l, enc_c["num_layers"])
+        if self.encoder.activation != "gelu":
+            raise NotImplementedError(f"activation={self.encoder.activation!r} in the Denoiser stage: its engine runs nn.GELU() (gelu) only; "
+                                      "relu, gelu_tanh and silu are JEPA pre-training options")
         c_feat = feature_extractor.embedding_dim
         self.post_extraction_mapper = nn.Linear(c_feat, self.encoder_embedding_dim) if c_feat != self.encoder_embedding_dim else None
         tab = get_1d_sincos_pos_embed_from_grid(self.encoder_embedding_dim, np.arange(self.total_patches, dtype=np.float64))

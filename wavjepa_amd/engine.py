@@ -47,6 +47,8 @@ class EngineConfig:
     recompute: bool = False        # activation recomputation in the student and the predictor (JEPA use_gradient_checkpointing; _alloc_ring)
     dropout_enc: float = 0.0       # dropout rate of the student's layers in a training-mode forward (never the teacher's); JepaEngine._drop
     dropout_dec: float = 0.0       # ... of the predictor's
+    act_enc: str = "gelu"          # feed-forward activation of the student AND the teacher: "gelu" | "relu" | "gelu_tanh" | "silu" (ops.gemm_act)
+    act_dec: str = "gelu"          # ... of the predictor
 
 
 @dataclass
@@ -481,6 +483,9 @@ class JepaEngine:
                      if self._row_form_pays(M, n_out) or (pairs and self._pair_pays(M, n_out, k_in)))
 
     def _check_fp8(self) -> None:
+        if self.fp8 and (self.cfg.act_enc != "gelu" or self.cfg.act_dec != "gelu"):
+            raise RuntimeError(f"fp8 mode (WJ_FP8=1 / engine.fp8) is not combined with activation={self.cfg.act_enc!r} (encoder) / "
+                               f"{self.cfg.act_dec!r} (decoder): the MX fp8 forward GEMM (wj_gemm_mxfp8) has the erf-GELU epilogue only")
         if self.fp8 and (self.cfg.dropout_enc > 0 or self.cfg.dropout_dec > 0):
             raise RuntimeError("fp8 mode (WJ_FP8=1 / engine.fp8) is not combined with dropout > 0: the fp8 producers (LayerNorm and GELU "
                                "epilogues that emit the next GEMM's operand) have no dropout forms")
@@ -508,8 +513,13 @@ class JepaEngine:
         for ptr, (q, sc, n, k) in self._w8.items():
             ops.quantize_mxfp8(ptr, q, sc, M=n, K=k, ldx=k, ldq=k, ld_scale=n)
 
-    def _linear_fwd(self, stack: str, x, w_ptr: int, out, *, M: int, N: int, K: int, bias, epilogue: int = ops.EPI_BF16, C2=None) -> None:
-        """out[M, N] = x[M, K] . W^T (+ bias, epilogue): the bf16 GEMM, or in fp8 mode (eligible K) quantise x and run the MX fp8 GEMM."""
+    def _linear_fwd(self, stack: str, x, w_ptr: int, out, *, M: int, N: int, K: int, bias, epilogue: int = ops.EPI_BF16, C2=None,
+                    act: str = "gelu") -> None:
+        """out[M, N] = x[M, K] . W^T (+ bias, epilogue): the bf16 GEMM, or in fp8 mode (eligible K) quantise x and run the MX fp8 GEMM.
+        act (linear1's two calls): another activation than GELU in the epilogue's place -- ops.gemm_act, never in fp8 mode (_check_fp8)."""
+        if act != "gelu":
+            ops.gemm_act(x, w_ptr, out, act=act, C2=C2, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, bias=bias, epilogue=epilogue)
+            return
         w8 = self._w8.get(w_ptr) if self.fp8 else None
         if w8 is None:
             ops.gemm(x, w_ptr, out, C2=C2, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, bias=bias, epilogue=epilogue,
@@ -740,10 +750,11 @@ class JepaEngine:
         out=False: linear1 only (a.g and a.h), for a second forward whose a.f was kept from the first.
         drop: dropout behind the GELU, one pass over a.g and a.h with the same mask -- linear2's weight gradient (reads a.g) and the
         MUL_GELU_GRAD dgrad epilogue (reads a.h) are then correct as they stand."""
+        act = self.cfg.act_dec if stack == "dec" else self.cfg.act_enc          # (the teacher's stack runs the encoder's activation)
         if save:
-            self._linear_fwd(stack, xb, w.w1, a.h, M=M, N=4 * D, K=D, bias=w.b1, epilogue=ops.EPI_BIAS_GELU2, C2=a.g)
+            self._linear_fwd(stack, xb, w.w1, a.h, M=M, N=4 * D, K=D, bias=w.b1, epilogue=ops.EPI_BIAS_GELU2, C2=a.g, act=act)
         else:
-            self._linear_fwd(stack, xb, w.w1, a.g, M=M, N=4 * D, K=D, bias=w.b1, epilogue=ops.EPI_BIAS_GELU)
+            self._linear_fwd(stack, xb, w.w1, a.g, M=M, N=4 * D, K=D, bias=w.b1, epilogue=ops.EPI_BIAS_GELU, act=act)
         if drop is not None:
             ops.dropout_rows(a.g, a.h if save else None, M=M, N=4 * D, drop=drop)
         if out:

@@ -23,7 +23,7 @@ from .extractors.audio_extractor import Extractor
 from .functions import trunc_normal_
 from .params import FlatParams
 from .pos_embed import get_1d_sincos_pos_embed_from_grid
-from .types import ForwardReturn, TransformerEncoderCFG, TransformerLayerCFG
+from .types import ForwardReturn, TransformerEncoderCFG, TransformerLayerCFG, activation_kind_of
 
 
 def collate_fn(batch: torch.Tensor) -> torch.Tensor:
@@ -71,6 +71,8 @@ class TransformerStack(nn.Module):
     def __init__(self, layer_cfg: Dict[str, Any], num_layers: int):
         super().__init__()
         self.norm_first = bool(layer_cfg.get("norm_first", False))
+        # the feed-forward activation's kind: it runs in linear1's GEMM epilogue (engine._mlp_fwd), the module itself is never called
+        self.activation = activation_kind_of(layer_cfg.get("activation"))
         # dropout: the rate of this stack's layers in a training-mode forward (engine: the _drop kernels; 0 = the launches without it)
         self.dropout = float(layer_cfg.get("dropout", 0.0) or 0.0)
         if not (0.0 <= self.dropout < 1.0):
@@ -399,6 +401,11 @@ class JEPA(_ModuleBase):
             self.hparams["norm_first_encoder"] = True
         if self.decoder.norm_first:
             self.hparams["norm_first_decoder"] = True
+        # the feed-forward activation of the student (and so of its EMA teacher) and of the predictor: the same rule
+        if self.encoder.activation != "gelu":
+            self.hparams["activation_encoder"] = self.encoder.activation
+        if self.decoder.activation != "gelu":
+            self.hparams["activation_decoder"] = self.decoder.activation
         # Dropout in the student and the predictor of a training-mode forward; the TEACHER runs without it (differences
         # by design).  The masks are a function of (dropout_seed, dropout_call or global_step, stack, layer, site, element): nothing is
         # stored, a resumed run continues the same mask sequence.  Recorded only when some rate is set (the rule of norm_first_*).
@@ -530,7 +537,8 @@ class JEPA(_ModuleBase):
                            norm_first_enc=self.encoder.norm_first, norm_first_dec=self.decoder.norm_first,
                            conv_mode=getattr(ext, "mode", "default"), conv_bias=bool(getattr(ext, "conv_bias", False)),
                            loss_kind=self.loss_kind, loss_beta=self.loss_beta, recompute=self.use_gradient_checkpointing,
-                           dropout_enc=self.encoder.dropout, dropout_dec=self.decoder.dropout)
+                           dropout_enc=self.encoder.dropout, dropout_dec=self.decoder.dropout,
+                           act_enc=self.encoder.activation, act_dec=self.decoder.activation)
         self._engine = JepaEngine(cfg, self._flat, self.pos_encoding_encoder.data, self.pos_encoding_decoder.data)
         self._anchor = torch.zeros(1, device=self.device, requires_grad=True)
         self._student_bf16_fresh = False

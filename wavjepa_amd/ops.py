@@ -88,6 +88,7 @@ class TimingEvent:
 _ENTRY_STRUCT = {fn: {**STRUCTS, **_abi.LAB_STRUCTS}[name] for fn, name in _abi.ENTRY_ARGS.items()}
 _ENTRY_STRUCT.update({fn: _abi.DROPOUT_STRUCTS[name] for fn, name in _abi.DROPOUT_ENTRY_ARGS.items()})    # libwavjepa_hip_dropout.so
 _ENTRY_STRUCT.update({fn: _abi.MONITOR_STRUCTS[name] for fn, name in _abi.MONITOR_ENTRY_ARGS.items()})    # libwavjepa_hip_monitor.so
+_ENTRY_STRUCT.update({fn: _abi.ACT_STRUCTS[name] for fn, name in _abi.ACT_ENTRY_ARGS.items()})            # libwavjepa_hip_act.so
 
 
 def _call(fn: str, a, stream: Optional[int], fields) -> None:
@@ -651,5 +652,7 @@ def noise_prepare(noise: Ptr, out: Ptr, workspace: Ptr, *, offsets, lengths, cut
 from .dropout_ops import (DROP_SITE_ATTN, DROP_SITE_FFN, DROP_SITE_RES1, DROP_SITE_RES2, DROP_STACK, attn_stream_bwd_drop,  # noqa: E402,F401
                           attn_stream_fwd_drop, drop_args, dropout_rows, layernorm_bwd_drop, layernorm_fwd_drop)
 # ---------------------------------------------------------------------------------------------------------- collapse monitor
+# likewise libwavjepa_hip_act.so (include/wavjepa_hip_act.h): wavjepa_amd/act_ops.py
+from .act_ops import ACT, gemm_act  # noqa: E402,F401
 # likewise libwavjepa_hip_monitor.so (include/wavjepa_hip_monitor.h): wavjepa_amd/monitor_ops.py
 from .monitor_ops import MOMENTS_COLS, MOMENTS_MAX_GROUPS, MOMENTS_ROWS, masked_moments, merge_moments  # noqa: E402,F401

@@ -17,6 +17,39 @@ class ForwardReturn(TypedDict, total=False):
     loss_denoise_dereverb: torch.Tensor
 
 
+ACTIVATION_KINDS = ("gelu", "relu", "gelu_tanh", "silu")
+
+
+def activation_kind_of(activation) -> str:
+    """The kind of feed-forward activation nn.TransformerEncoderLayer(activation=...) would run, as linear1's GEMM epilogue computes it
+    (include/wavjepa_hip_act.h): None / nn.GELU() / "gelu" / F.gelu -> gelu; nn.ReLU() / "relu" / F.relu -> relu;
+    nn.GELU(approximate="tanh") / "gelu_tanh" -> gelu_tanh; nn.SiLU() / "silu" / F.silu -> silu.  Anything else is refused here instead
+    of being trained as GELU."""
+    import torch.nn.functional as F
+    a = activation
+    if a is None:
+        return "gelu"
+    if isinstance(a, str):
+        if a in ACTIVATION_KINDS:
+            return a
+    elif type(a) is nn.GELU:
+        if a.approximate in ("none", "tanh"):
+            return "gelu" if a.approximate == "none" else "gelu_tanh"
+    elif type(a) is nn.ReLU:
+        return "relu"
+    elif type(a) is nn.SiLU:
+        return "silu"
+    elif a is F.gelu:
+        return "gelu"
+    elif a is F.relu:
+        return "relu"
+    elif a is F.silu:
+        return "silu"
+    what = repr(a) if isinstance(a, str) else (f"{type(a).__name__} ({a!r})" if isinstance(a, nn.Module) else f"{type(a).__name__} {getattr(a, '__name__', a)!r}")
+    raise NotImplementedError(f"activation {what}: linear1's GEMM epilogue computes nn.GELU() (gelu), nn.ReLU() (relu), "
+                              "nn.GELU(approximate='tanh') (gelu_tanh) and nn.SiLU() (silu)")
+
+
 class TransformerLayerCFG(TypedDict):
     d_model: int
     nhead: int
