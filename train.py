@@ -88,7 +88,7 @@ class ComponentFactory:
             if a not in acts:
                 raise ValueError(f"Unknown {key}: {a}. Available activations: {list(acts)}")
         try:
-            return cls(feature_extractor=extractor, transformer_encoder_cfg=TransformerEncoderCFG.create(),
+            return cls(**optimizer_group_settings(cfg), feature_extractor=extractor, transformer_encoder_cfg=TransformerEncoderCFG.create(),
                        transformer_encoder_layers_cfg=TransformerLayerCFG.create(norm_first=norm_first, dropout=drop_enc, activation=acts[act]()),
                        transformer_decoder_cfg=TransformerEncoderCFG.create(),
                        transformer_decoder_layers_cfg=TransformerLayerCFG.create(d_model=384, norm_first=norm_first_dec, dropout=drop_dec,
@@ -103,6 +103,20 @@ class ComponentFactory:
                        use_gradient_checkpointing=bool(cfg.trainer.get("use_gradient_checkpointing", False)))
         except Exception as e:
             raise RuntimeError(f"Failed to create network instance: {str(e)}")
+
+
+def optimizer_group_settings(cfg) -> dict:
+    """The model keywords that give the optimiser parameter groups, only those that are set (so a default run builds the model it always
+    built): optimizer.weight_decay_exclude (`1d`, or a list of fnmatch patterns on parameter names: those go without weight decay) and
+    optimizer.layer_lr_decay (BEiT's layer-wise lr decay; 1.0 = none)."""
+    exclude = cfg.optimizer.get("weight_decay_exclude", None)
+    decay = float(cfg.optimizer.get("layer_lr_decay", 1.0))
+    kw = {}
+    if exclude is not None:
+        kw["weight_decay_exclude"] = exclude if isinstance(exclude, str) else tuple(str(x) for x in exclude)
+    if decay != 1.0:
+        kw["layer_lr_decay"] = decay
+    return kw
 
 
 def monitor_settings(cfg) -> tuple:

@@ -117,11 +117,45 @@ ACT_LIB_PATH = os.path.join(HERE, "lib", "libwavjepa_hip_act.so")
 _ACT = Header(ACT_HEADER, known=_HEADER)
 ACT_STRUCTS, ACT_FUNCTIONS, ACT_ENTRY_ARGS, ACT_ENUMS = _ACT.struct_types, list(_ACT.functions), dict(_ACT.entry_args), _ACT.enums
 
+# libwavjepa_hip_optim.so (wj_adamw_groups_step: the AdamW pass with parameter groups): likewise
+OPTIM_HEADER = os.path.join(os.path.dirname(HERE), "include", "wavjepa_hip_optim.h")
+OPTIM_LIB_PATH = os.path.join(HERE, "lib", "libwavjepa_hip_optim.so")
+_OPT = Header(OPTIM_HEADER, known=_HEADER)
+OPTIM_STRUCTS, OPTIM_FUNCTIONS, OPTIM_ENTRY_ARGS, OPTIM_DEFINES = _OPT.struct_types, list(_OPT.functions), dict(_OPT.entry_args), _OPT.defines
+
 _lib = None
 _lab_lib = None
 _dropout_lib = None
 _monitor_lib = None
 _act_lib = None
+_optim_lib = None
+
+
+def optim_loaded() -> bool:
+    """True once libwavjepa_hip_optim.so is in the process (an optimiser with one parameter group never loads it)."""
+    return _optim_lib is not None
+
+
+def load_optim():
+    """libwavjepa_hip_optim.so (once), its struct sizes cross-checked against its own wj_optim_struct_size.  Loaded behind the release
+    library, as load_dropout() does."""
+    global _optim_lib
+    if _optim_lib is None:
+        load()
+        if not os.path.exists(OPTIM_LIB_PATH):
+            raise WavJepaHipError(f"{OPTIM_LIB_PATH} is missing: run `python -m wavjepa_amd.build` (or __graft_entry__.build())")
+        lib = ctypes.CDLL(OPTIM_LIB_PATH)
+        for fn in OPTIM_FUNCTIONS:
+            if not hasattr(lib, fn):
+                raise WavJepaHipError(f"{OPTIM_LIB_PATH} does not export {fn} (declared in include/wavjepa_hip_optim.h); rebuild it")
+            f = getattr(lib, fn)
+            f.restype, f.argtypes = _OPT.functions[fn]
+        for name, cls in OPTIM_STRUCTS.items():
+            want = lib.wj_optim_struct_size(name.encode())
+            if want != ctypes.sizeof(cls):
+                raise WavJepaHipError(f"struct {name}: header mirror is {ctypes.sizeof(cls)} bytes, library says {want}")
+        _optim_lib = lib
+    return _optim_lib
 
 
 def act_loaded() -> bool:
@@ -253,6 +287,8 @@ def workspace_bytes(fn_name: str, args_struct) -> int:
         n = int(load_monitor().wj_monitor_workspace_bytes(fn_name.encode(), ctypes.byref(args_struct)))
     elif fn_name in ACT_ENTRY_ARGS:
         n = int(load_act().wj_act_workspace_bytes(fn_name.encode(), ctypes.byref(args_struct)))
+    elif fn_name in OPTIM_ENTRY_ARGS:
+        n = int(load_optim().wj_optim_workspace_bytes(fn_name.encode(), ctypes.byref(args_struct)))
     else:
         n = int(load().wj_workspace_bytes(fn_name.encode(), ctypes.byref(args_struct)))
     if n < 0:
@@ -266,6 +302,8 @@ _ERR = {-1: "invalid argument", -2: "kernel launch failed", -3: "unsupported con
 def call(fn_name: str, args_struct, stream: int, lab: bool = False) -> None:
     if fn_name in ACT_ENTRY_ARGS:
         lib = load_act()
+    elif fn_name in OPTIM_ENTRY_ARGS:
+        lib = load_optim()
     else:
         lib = load_dropout() if fn_name in DROPOUT_ENTRY_ARGS else (load_monitor() if fn_name in MONITOR_ENTRY_ARGS else (load_lab() if lab else load()))
     rc = getattr(lib, fn_name)(ctypes.byref(args_struct), stream)

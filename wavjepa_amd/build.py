@@ -30,6 +30,10 @@ MONITOR_FLAGS = ["-fvisibility=hidden"]
 ACT_LIB = os.path.join(LIBDIR, "libwavjepa_hip_act.so")
 ACT_SOURCES = ["gemm.hip", "gemm_persist.hip", "act_abi.hip"]
 ACT_FLAGS = ["-DWJ_ACT_LIB", "-fvisibility=hidden"]
+# libwavjepa_hip_optim.so (include/wavjepa_hip_optim.h): wj_adamw_groups_step, the AdamW pass with parameter groups, and its two query entries
+OPTIM_LIB = os.path.join(LIBDIR, "libwavjepa_hip_optim.so")
+OPTIM_SOURCES = ["optim.hip"]
+OPTIM_FLAGS = ["-fvisibility=hidden"]
 
 
 def _hipcc() -> str:
@@ -46,19 +50,21 @@ def _stale(target: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force: bool = False, verbose: bool = True, lab: bool = False, dropout: bool = False, monitor: bool = False, act: bool = False) -> str:
+def build(force: bool = False, verbose: bool = True, lab: bool = False, dropout: bool = False, monitor: bool = False, act: bool = False,
+          optim: bool = False) -> str:
     """The release library (compute + query entries, production-safe switches only), or with lab=True the laboratory variant
     (libwavjepa_hip_lab.so: -DWJ_LAB, the extra entries of include/wavjepa_hip_lab.h and every A/B / diagnostic environment switch),
-    or with dropout=True libwavjepa_hip_dropout.so, or with monitor=True libwavjepa_hip_monitor.so, or with act=True libwavjepa_hip_act.so."""
+    or with dropout=True libwavjepa_hip_dropout.so, or with monitor=True libwavjepa_hip_monitor.so, or with act=True libwavjepa_hip_act.so,
+    or with optim=True libwavjepa_hip_optim.so."""
     hipcc = _hipcc()
     os.makedirs(LIBDIR, exist_ok=True)
-    objdir = os.path.join(LIBDIR, "obj_act" if act else ("obj_monitor" if monitor else ("obj_dropout" if dropout else ("obj_lab" if lab else "obj"))))
+    objdir = os.path.join(LIBDIR, "obj_optim" if optim else "obj_act" if act else ("obj_monitor" if monitor else ("obj_dropout" if dropout else ("obj_lab" if lab else "obj"))))
     os.makedirs(objdir, exist_ok=True)
     inc = os.path.join(os.path.dirname(HERE), "include")
     headers = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(inc, "*.h"))
-    flags = FLAGS + (ACT_FLAGS if act else (MONITOR_FLAGS if monitor else (DROPOUT_FLAGS if dropout else (["-DWJ_LAB"] if lab else []))))
-    lib = ACT_LIB if act else (MONITOR_LIB if monitor else (DROPOUT_LIB if dropout else (LAB_LIB if lab else LIB)))
-    sources = ACT_SOURCES if act else (MONITOR_SOURCES if monitor else (DROPOUT_SOURCES if dropout else SOURCES))
+    flags = FLAGS + (OPTIM_FLAGS if optim else ACT_FLAGS if act else (MONITOR_FLAGS if monitor else (DROPOUT_FLAGS if dropout else (["-DWJ_LAB"] if lab else []))))
+    lib = OPTIM_LIB if optim else ACT_LIB if act else (MONITOR_LIB if monitor else (DROPOUT_LIB if dropout else (LAB_LIB if lab else LIB)))
+    sources = OPTIM_SOURCES if optim else ACT_SOURCES if act else (MONITOR_SOURCES if monitor else (DROPOUT_SOURCES if dropout else SOURCES))
     jobs = []
     for src in sources:
         s = os.path.join(CSRC, src)
@@ -87,7 +93,7 @@ def build(force: bool = False, verbose: bool = True, lab: bool = False, dropout:
             raise RuntimeError(f"link failed:\n{r.stderr}")
         if verbose:
             print(f"[wavjepa_amd.build] linked {lib}", file=sys.stderr)
-    if not lab and not dropout and not monitor and not act:
+    if not lab and not dropout and not monitor and not act and not optim:
         build_io(force=force, verbose=verbose)
     return lib
 
@@ -98,6 +104,7 @@ def build_all(force: bool = False, verbose: bool = True) -> None:
     build(force=force, verbose=verbose, dropout=True)
     build(force=force, verbose=verbose, monitor=True)
     build(force=force, verbose=verbose, act=True)
+    build(force=force, verbose=verbose, optim=True)
     build(force=force, verbose=verbose, lab=True)
 
 

@@ -82,3 +82,7 @@
 // libwavjepa_hip_monitor.so (include/wavjepa_hip_monitor.h, csrc/monitor.hip): the same two row forms
 #define WJ_MONITOR_ENTRIES(E, W)                                                       \
     W(wj_masked_moments, wj_moments_args, wj_masked_moments_ws_bytes)
+
+// libwavjepa_hip_optim.so (include/wavjepa_hip_optim.h, csrc/optim.hip): the same two row forms
+#define WJ_OPTIM_ENTRIES(E, W)                                                         \
+    E(wj_adamw_groups_step, wj_adamw_groups_args)

@@ -411,29 +411,19 @@ __global__ __launch_bounds__(1024) void sumsq_final_kernel(const float* __restri
 
 __global__ __launch_bounds__(256) void adamw_kernel(wj_adamw_args a) {
     const long n4 = a.n / 4;
-    float coef = a.grad_scale;
-    if (a.max_norm > 0.f && a.sumsq) {
-        const float norm = sqrtf(a.sumsq[0]) * a.grad_scale;
-        coef *= fminf(1.0f, a.max_norm / (norm + 1e-6f));
-    }
-    const float decay = 1.0f - a.lr * a.weight_decay;
-    const float step = a.lr / a.bc1;
+    const float coef = adamw_clip_coef(a.sumsq, a.max_norm, a.grad_scale);
+    float decay, step;
+    adamw_rates(a.lr, a.weight_decay, a.bc1, decay, step);
     const float rbc2 = rsqrtf(a.bc2);
-    // (the plain loop, as in ema_kernel: the moment updates are sums of two products)
+    // (the plain loop, as in ema_kernel: the moment updates are sums of two products; the element update is stream_pieces.h's
+    // adamw_update4, shared with the grouped pass of csrc/optim.hip)
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         f32x4 p = *reinterpret_cast<const f32x4*>(a.p + i * 4);
         const f32x4 g = *reinterpret_cast<const f32x4*>(a.g + i * 4);
         if (a.zero_grad) *reinterpret_cast<f32x4*>(a.g + i * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
         f32x4 m = *reinterpret_cast<const f32x4*>(a.m + i * 4);
         f32x4 v = *reinterpret_cast<const f32x4*>(a.v + i * 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float ge = g[e] * coef;
-            p[e] *= decay;
-            m[e] = a.beta1 * m[e] + (1.0f - a.beta1) * ge;
-            v[e] = a.beta2 * v[e] + (1.0f - a.beta2) * ge * ge;
-            p[e] -= step * m[e] / (sqrtf(v[e]) * rbc2 + a.eps);
-        }
+        adamw_update4(p, g, m, v, coef, decay, step, rbc2, a.beta1, a.beta2, a.eps);
         *reinterpret_cast<f32x4*>(a.p + i * 4) = p;
         *reinterpret_cast<f32x4*>(a.m + i * 4) = m;
         *reinterpret_cast<f32x4*>(a.v + i * 4) = v;

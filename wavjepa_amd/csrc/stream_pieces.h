@@ -3,7 +3,8 @@
 // include this header.
 //   conversions: to_f32x4 / to_bf16x4 -- four bf16 <-> four fp32 (f2bf: RNE)
 //   walkers    : for_each_flat (the 256-thread grid-stride loop), for_each_row_col (the same over [rows][per_row])
-//   bodies     : fill_token (one predictor-input piece: context feature or mask token, plus position), gelu_bwd8
+//   bodies     : fill_token (one predictor-input piece: context feature or mask token, plus position), gelu_bwd8,
+//                adamw_clip_coef / adamw_rates / adamw_update4 (the AdamW element update: misc.hip and optim.hip, a library of its own)
 //   sums       : stage_wave_sum + fold4 (four wave sums, pairwise), fold_partials (a workspace of partials in one workgroup),
 //                mean_sqdev (two-pass mean / centred sum of squares of a view).  fold4 and common.h's block_sum are two different
 //                summation orders; every kernel keeps the one it has (tests/norm_reference.py, tests/optimizer_reference.py)
@@ -55,6 +56,36 @@ __device__ __forceinline__ bf16x8 gelu_bwd8(bf16x8 d, bf16x8 p) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(d[e]) * gelu_grad_f(bf2f(p[e])));
     return o;
+}
+
+// ---- the AdamW element update (adamw_kernel of misc.hip; adamw_groups_kernel of optim.hip, a library of its own) ----------------------
+// Where an expression holds two products the compiler could contract around either (m', v', the clip's and the decay's sums), the
+// multiply-add is written out as the fused operation adamw_kernel has always compiled to, so that the bits do not depend on the choice
+// it makes in a given caller (a uniform factor here, a per-lane one there).  The last line, p * decay - q, holds ONE product: it is
+// left to the compiler, which contracts it to fma(decay, p, -q) in both kernels (checked in the ISA; written as __builtin_fmaf the
+// negation moves into the product -- the same bits, but not the instruction sequence adamw_kernel had).
+// the clip coefficient from the one global sum of squares: grad_scale * min(1, max_norm / (sqrt(sumsq) * grad_scale + 1e-6))
+__device__ __forceinline__ float adamw_clip_coef(const float* sumsq, float max_norm, float grad_scale) {
+    float coef = grad_scale;
+    if (max_norm > 0.f && sumsq) coef *= fminf(1.0f, max_norm / __builtin_fmaf(sqrtf(sumsq[0]), grad_scale, 1e-6f));
+    return coef;
+}
+// what a learning rate and a weight decay become: the factor of p (1 - lr * wd) and the factor of m / den
+__device__ __forceinline__ void adamw_rates(float lr, float weight_decay, float bc1, float& decay, float& step) {
+    decay = __builtin_fmaf(-lr, weight_decay, 1.0f);
+    step = lr / bc1;
+}
+// four elements: m, v the moving averages of the clipped gradient; p = p * decay - step * m / (sqrt(v) * rbc2 + eps)
+__device__ __forceinline__ void adamw_update4(f32x4& p, const f32x4& g, f32x4& m, f32x4& v, float coef, float decay, float step, float rbc2,
+                                              float beta1, float beta2, float eps) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float ge = g[e] * coef;
+        m[e] = __builtin_fmaf(beta1, m[e], (1.0f - beta1) * ge);
+        v[e] = __builtin_fmaf(beta2, v[e], ge * ((1.0f - beta2) * ge));
+        p[e] *= decay;
+        p[e] -= step * m[e] / __builtin_fmaf(rbc2, sqrtf(v[e]), eps);
+    }
 }
 
 // ---- sums ---------------------------------------------------------------------------------------------------------------------------

@@ -147,12 +147,26 @@ _ADAMW_ZERO_GRAD = os.environ.get("WJ_ADAMW_ZERO_GRAD", "1") != "0"
 
 class FusedAdamW(torch.optim.Optimizer):
     """torch.optim.AdamW semantics (reference jepa.py:215-222) as ONE kernel over the flat parameter buffer, with the
-    global-norm clip of Lightning's gradient_clip_val (train.py:177-178) fused in (`max_grad_norm`)."""
+    global-norm clip of Lightning's gradient_clip_val (train.py:177-178) fused in (`max_grad_norm`).
+
+    groups (wavjepa_amd.optim): None -- one group of every trainable parameter, the reference's configure_optimizers, updated by
+    wj_adamw_step; or a list of {"params": [names or Parameters], "lr": ..., "weight_decay": ...} (both default to the constructor's)
+    that puts every trainable parameter into exactly one group, at most 64 of them.  The update is then wj_adamw_groups_step: still
+    one pass over the flat buffers, the group of an element looked up in a byte map (FlatParams.group_map).  step() reads lr and
+    weight_decay of EVERY group from self.param_groups at each call, so LambdaLR and a user's weight-decay schedule both apply;
+    betas, eps and the clip (one global norm) are common to all groups."""
 
     def __init__(self, module: "JEPA", lr: float, betas=(0.9, 0.98), eps: float = 1e-6, weight_decay: float = 0.01,
-                 max_grad_norm: float = 0.0):
-        params = [p for p in module.parameters() if p.requires_grad]
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+                 max_grad_norm: float = 0.0, groups=None):
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self._assignment = None          # {parameter name: group index} of a grouped optimiser
+        self._group_map = None           # its device byte map, made with the flat buffers
+        if groups is None:
+            params = [p for p in module.parameters() if p.requires_grad]
+        else:
+            from .optim import resolve_groups
+            params, self._assignment = resolve_groups(module, groups, defaults)
+        super().__init__(params, defaults)
         self._module = module
         self.max_grad_norm = max_grad_norm
         self._t = 0
@@ -194,12 +208,22 @@ class FusedAdamW(torch.optim.Optimizer):
         if self.max_grad_norm > 0:
             ops.grad_sumsq(flat.g32, self._sumsq, self._ws, flat.n)
         zg = bool(self.fuse_zero_grad) and _ADAMW_ZERO_GRAD
-        kw = dict(lr=float(g["lr"]), beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], weight_decay=g["weight_decay"], step=self._t,
+        kw = dict(beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], step=self._t,
                   max_norm=self.max_grad_norm, sumsq=self._sumsq if self.max_grad_norm > 0 else None)
+        if self._assignment is None:
+            kw.update(lr=float(g["lr"]), weight_decay=g["weight_decay"])
+            adamw = ops.adamw_step
+        else:                            # every group's pair, read now: schedulers and the user write them between steps
+            if self._group_map is None or self._group_map.device != flat.p32.device or self._group_map.numel() * 8 != flat.n:
+                self._group_map = flat.group_map(self._assignment)
+            kw.update(lr=[float(q["lr"]) for q in self.param_groups], weight_decay=[float(q["weight_decay"]) for q in self.param_groups],
+                      group_map=self._group_map)
+            adamw = ops.adamw_groups_step
 
         def update(lo: int, hi: int, workgroups: int = 0) -> None:
-            ops.adamw_step(flat.p32.data_ptr() + 4 * lo, flat.g32.data_ptr() + 4 * lo, flat.adam_m.data_ptr() + 4 * lo,
-                           flat.adam_v.data_ptr() + 4 * lo, hi - lo, p_bf16=flat.p16.data_ptr() + 2 * lo, workgroups=workgroups, zero_grad=zg, **kw)
+            where = {} if self._assignment is None else dict(first=lo)
+            adamw(flat.p32.data_ptr() + 4 * lo, flat.g32.data_ptr() + 4 * lo, flat.adam_m.data_ptr() + 4 * lo,
+                  flat.adam_v.data_ptr() + 4 * lo, hi - lo, p_bf16=flat.p16.data_ptr() + 2 * lo, workgroups=workgroups, zero_grad=zg, **where, **kw)
         eng = m._engine
         front, rest = flat.front_and_rest_ranges()
         if self.overlap_next_forward and eng.use_side and rest and _ADAMW_SIDE:
@@ -232,13 +256,22 @@ class FusedAdamW(torch.optim.Optimizer):
         flat = self._module._flat
         if self._module._engine is not None:
             self._module._engine.wait_optimizer()
-        return dict(step=self._t, lr=self.param_groups[0]["lr"], m=None if flat is None or flat.adam_m is None else flat.adam_m.cpu(),
-                    v=None if flat is None or flat.adam_v is None else flat.adam_v.cpu())
+        sd = dict(step=self._t, lr=self.param_groups[0]["lr"], m=None if flat is None or flat.adam_m is None else flat.adam_m.cpu(),
+                  v=None if flat is None or flat.adam_v is None else flat.adam_v.cpu())
+        if self._assignment is not None:     # a grouped optimiser: every group's pair, for the reason given for lr below
+            sd["group_lr"] = [float(q["lr"]) for q in self.param_groups]
+            sd["group_weight_decay"] = [float(q["weight_decay"]) for q in self.param_groups]
+        return sd
 
     def load_state_dict(self, sd):
         self._t = int(sd["step"])
         if sd.get("lr") is not None:     # LambdaLR.load_state_dict does not write the group lr back: without this the first
             self.param_groups[0]["lr"] = float(sd["lr"])   # resumed step would run at the constructor's lr
+        if self._assignment is not None and sd.get("group_lr") is not None:
+            if len(sd["group_lr"]) != len(self.param_groups) or len(sd["group_weight_decay"]) != len(self.param_groups):
+                raise ValueError(f"the optimiser state holds {len(sd['group_lr'])} parameter groups, this optimiser has {len(self.param_groups)}")
+            for q, lr, wd in zip(self.param_groups, sd["group_lr"], sd["group_weight_decay"]):
+                q["lr"], q["weight_decay"] = float(lr), float(wd)
         self._module._ensure_engine().wait_optimizer()
         flat = self._module._flat
         flat.ensure_adam_state()
@@ -353,6 +386,8 @@ class JEPA(_ModuleBase):
         if HAS_LIGHTNING:        # as the reference does (jepa.py:105-107): hyper-parameters into the checkpoint
             self.save_hyperparameters(ignore=["feature_encoder", "feature_extractor", "loss_fn"])
             self.hparams["adam_betas"] = tuple(adam_betas)
+            self.hparams.pop("weight_decay_exclude", None)     # (recorded below, only when set)
+            self.hparams.pop("layer_lr_decay", None)
         else:
             self.hparams = _AttrDict(lr=lr, adam_betas=tuple(adam_betas), adam_eps=adam_eps, adam_weight_decay=adam_weight_decay,
                                      ema_decay=ema_decay, ema_end_decay=ema_end_decay, ema_anneal_end_step=ema_anneal_end_step,
@@ -364,6 +399,18 @@ class JEPA(_ModuleBase):
                 self.hparams["use_gradient_checkpointing"] = True
             self.global_step = 0
             self.trainer = _NullTrainer()
+        # Parameter groups of the optimiser (wavjepa_amd.optim.param_groups): which parameters go without weight decay (None, "1d" or
+        # fnmatch patterns on names) and BEiT's layer-wise lr decay.  Recorded only when set, the rule of norm_first_encoder below:
+        # a default model keeps its hyper-parameter set and the single group of the reference's configure_optimizers.
+        # Both are keywords taken through **kwargs (weight_decay_exclude=None, layer_lr_decay=1.0): the named parameters stay the reference's.
+        weight_decay_exclude, layer_lr_decay = kwargs.pop("weight_decay_exclude", None), kwargs.pop("layer_lr_decay", 1.0)
+        if weight_decay_exclude is not None and not isinstance(weight_decay_exclude, str):
+            weight_decay_exclude = tuple(weight_decay_exclude)
+        self.weight_decay_exclude, self.layer_lr_decay = weight_decay_exclude, float(layer_lr_decay)
+        if self.weight_decay_exclude is not None:
+            self.hparams["weight_decay_exclude"] = self.weight_decay_exclude
+        if self.layer_lr_decay != 1.0:
+            self.hparams["layer_lr_decay"] = self.layer_lr_decay
         self.extract_audio = feature_extractor
         self.feature_norms = nn.LayerNorm(self.extract_audio.embedding_dim)
         self.loss_fn = loss_fn
@@ -568,8 +615,13 @@ class JEPA(_ModuleBase):
         self._teacher_bf16_fresh = True
 
     def configure_optimizers(self):
+        groups = None
+        if self.weight_decay_exclude is not None or self.layer_lr_decay != 1.0:
+            from .optim import param_groups
+            groups = param_groups(self, weight_decay_exclude=self.weight_decay_exclude, layer_lr_decay=self.layer_lr_decay,
+                                  lr=self.hparams.lr, weight_decay=self.hparams.adam_weight_decay)
         optimizer = FusedAdamW(self, lr=self.hparams.lr, betas=self.hparams.adam_betas, eps=self.hparams.adam_eps,
-                               weight_decay=self.hparams.adam_weight_decay)
+                               weight_decay=self.hparams.adam_weight_decay, groups=groups)
         sched = cosine_schedule_with_warmup(optimizer, num_warmup_steps=int(self.hparams.warmup_steps),
                                             num_training_steps=self._max_steps())
         return {"optimizer": optimizer, "lr_scheduler": {"scheduler": sched, "interval": "step"}}

@@ -89,6 +89,7 @@ _ENTRY_STRUCT = {fn: {**STRUCTS, **_abi.LAB_STRUCTS}[name] for fn, name in _abi.
 _ENTRY_STRUCT.update({fn: _abi.DROPOUT_STRUCTS[name] for fn, name in _abi.DROPOUT_ENTRY_ARGS.items()})    # libwavjepa_hip_dropout.so
 _ENTRY_STRUCT.update({fn: _abi.MONITOR_STRUCTS[name] for fn, name in _abi.MONITOR_ENTRY_ARGS.items()})    # libwavjepa_hip_monitor.so
 _ENTRY_STRUCT.update({fn: _abi.ACT_STRUCTS[name] for fn, name in _abi.ACT_ENTRY_ARGS.items()})            # libwavjepa_hip_act.so
+_ENTRY_STRUCT.update({fn: _abi.OPTIM_STRUCTS[name] for fn, name in _abi.OPTIM_ENTRY_ARGS.items()})        # libwavjepa_hip_optim.so
 
 
 def _call(fn: str, a, stream: Optional[int], fields) -> None:
@@ -656,3 +657,5 @@ from .dropout_ops import (DROP_SITE_ATTN, DROP_SITE_FFN, DROP_SITE_RES1, DROP_SI
 from .act_ops import ACT, gemm_act  # noqa: E402,F401
 # likewise libwavjepa_hip_monitor.so (include/wavjepa_hip_monitor.h): wavjepa_amd/monitor_ops.py
 from .monitor_ops import MOMENTS_COLS, MOMENTS_MAX_GROUPS, MOMENTS_ROWS, masked_moments, merge_moments  # noqa: E402,F401
+# likewise libwavjepa_hip_optim.so (include/wavjepa_hip_optim.h): wavjepa_amd/optim_ops.py
+from .optim_ops import ADAMW_GRANULE, ADAMW_MAX_GROUPS, adamw_groups_step  # noqa: E402,F401

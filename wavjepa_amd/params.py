@@ -95,6 +95,22 @@ class FlatParams:
             self._fr = ([(lo, hi) for lo, hi, f in runs if f], [(lo, hi) for lo, hi, f in runs if not f])
         return self._fr
 
+    def group_map(self, assignment: Dict[str, int]) -> torch.Tensor:
+        """uint8 [n / 8] on the device: the parameter group of every 8-element granule of the flat buffers (wj_adamw_groups_step's
+        group_map), from `assignment` {parameter name: group index < 256}, which must name every slot.  A slot starts on a granule and
+        its padding granule is its own, so the map is valid for any [lo, hi) on slot boundaries (front_and_rest_ranges): element i reads
+        map[i // 8] whatever range the launch covers."""
+        missing = [s.name for s in self.slots if s.name not in assignment]
+        if missing:
+            raise ValueError(f"group_map: no group for parameter {missing[0]!r}" + (f" (and {len(missing) - 1} more)" if len(missing) > 1 else ""))
+        host = torch.empty(self.n // ALIGN, dtype=torch.uint8)
+        for s in self.slots:
+            k = int(assignment[s.name])
+            if not 0 <= k < 256:
+                raise ValueError(f"group_map: group {k} of parameter {s.name!r} does not fit a byte")
+            host[s.offset // ALIGN:(s.offset + s.numel + ALIGN - 1) // ALIGN] = k
+        return host.to(self.device)
+
     def ptr32(self, name: str) -> int:
         return self.p32.data_ptr() + 4 * self.by_name[name].offset
 
