@@ -1,14 +1,14 @@
 /* Laboratory entry points of libwavjepa_hip_lab.so -- NOT part of the drop-in surface.
  *
  * The release library (libwavjepa_hip.so, include/wavjepa_hip.h) exports compute and query entries only and reads the environment
- * switches INTEGRATION.md lists as safe in production.  The same sources built with -DWJ_LAB (wavjepa_amd.build.build(lab=True) ->
+ * switches INTEGRATION.md lists as safe in production.  The same sources built with -DWJ_LAB (wavjepa_amd.build.build("lab") ->
  * wavjepa_amd/lib/libwavjepa_hip_lab.so) additionally
  *   * export the entries below (time stamps of the persistent GEMM; the all-reduce footprint rehearsal),
  *   * honour the result- or schedule-changing diagnostics of csrc/: WJ_PERSIST_DIAG_NOSTORE, WJ_PERSIST_STAMPS, WJ_PERSIST_ACTIVE,
  *     WJ_PERSIST_STAGGER_US / _EPI, WJ_PERSIST_HALF, WJ_PERSIST_WBLOCK, WJ_PERSIST_MIN_TILES, WJ_GEMM_VARIANT, WJ_GEMM_PANEL, WJ_PAIR_MIN_K, WJ_WGRAD_384,
  *     WJ_ATTN_BWD_FRAG, WJ_CONV0_STATS_TCS, WJ_CONV0_APPLY_MFMA, WJ_CONV0_APPLY_OCC, WJ_LN_BWD_ONE_PASS_ROWS
  *     (in the release build each of them is compiled to its default: csrc/common.h wj_lab_env_int).
- * tools/ and the tests that rehearse or dissect a kernel load this library (wavjepa_amd._abi.load_lab(), or WAVJEPA_HIP_LIB=<path>). */
+ * tools/ and the tests that rehearse or dissect a kernel load this library (wavjepa_amd._abi.load("lab"), or WAVJEPA_HIP_LIB=<path>). */
 #ifndef WAVJEPA_HIP_LAB_H
 #define WAVJEPA_HIP_LAB_H
 #include "wavjepa_hip.h"

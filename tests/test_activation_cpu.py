@@ -212,14 +212,14 @@ def test_abi_struct_error_codes_and_workspace_query():
     refusal is answered before any launch, so it can be asked without a GPU (the pointers are never followed)."""
     from wavjepa_amd import _abi, ops
     rel = _abi.load()
-    lib = _abi.load_act()
+    lib = _abi.load("act")
     assert _abi.DEFINES["WJ_ABI_VERSION"] == 17 and rel.wj_abi_version() == 17
-    assert not set(_abi.ACT_FUNCTIONS) & set(_abi.FUNCTIONS) and "wj_gemm_bf16_act" not in _abi.ENTRY_ARGS
+    assert not set(_abi.LIBRARIES["act"].functions) & set(_abi.FUNCTIONS) and "wj_gemm_bf16_act" not in _abi.ENTRY_ARGS
     assert not hasattr(rel, "wj_gemm_bf16_act")
-    T, G = _abi.ACT_STRUCTS["wj_gemm_act_args"], _abi.STRUCTS["wj_gemm_args"]
+    T, G = _abi.LIBRARIES["act"].struct_types["wj_gemm_act_args"], _abi.STRUCTS["wj_gemm_args"]
     assert ctypes.sizeof(T) == ctypes.sizeof(G) + 8 == lib.wj_act_struct_size(b"wj_gemm_act_args") and T.act.offset == ctypes.sizeof(G)
     assert lib.wj_act_struct_size(b"wj_gemm_args") == -1 and lib.wj_act_struct_size(None) == -1
-    assert _abi.ACT_ENUMS == dict(WJ_ACT_GELU=0, WJ_ACT_RELU=1, WJ_ACT_GELU_TANH=2, WJ_ACT_SILU=3)
+    assert _abi.LIBRARIES["act"].enums == dict(WJ_ACT_GELU=0, WJ_ACT_RELU=1, WJ_ACT_GELU_TANH=2, WJ_ACT_SILU=3)
     assert ops.ACT == dict(gelu=0, relu=1, gelu_tanh=2, silu=3)
 
     def args(act=1, **kw):
@@ -238,6 +238,6 @@ def test_abi_struct_error_codes_and_workspace_query():
     assert _abi.workspace_bytes("wj_gemm_bf16_act", args()) == 0
     assert lib.wj_act_workspace_bytes(b"wj_gemm_bf16", ctypes.byref(args())) == -1
     import subprocess
-    syms = subprocess.run(["nm", "-D", "--defined-only", _abi.ACT_LIB_PATH], capture_output=True, text=True, check=True).stdout
+    syms = subprocess.run(["nm", "-D", "--defined-only", _abi.LIBRARIES["act"].path], capture_output=True, text=True, check=True).stdout
     exported = sorted(ln.split()[-1] for ln in syms.splitlines() if " T " in ln)
     assert exported == ["wj_act_struct_size", "wj_act_workspace_bytes", "wj_gemm_bf16_act"], exported

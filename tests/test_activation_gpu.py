@@ -311,7 +311,7 @@ def test_default_model_issues_the_parents_launches_and_never_loads_the_library()
     process that ran them has not loaded libwavjepa_hip_act.so."""
     code = ("import runpy, sys; sys.argv = ['launch_trace.py', '--summary'] + %r; " % (TRACE_CASES,) + ""
             f"runpy.run_path({os.path.join(ROOT, 'tools', 'launch_trace.py')!r}, run_name='__main__'); "
-            "from wavjepa_amd import _abi; print('ACT_LOADED', _abi.act_loaded()); "
+            "from wavjepa_amd import _abi; print('ACT_LOADED', _abi.loaded('act')); "
             "print('ACT_MAPPED', 'libwavjepa_hip_act' in open('/proc/self/maps').read())")
     r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]

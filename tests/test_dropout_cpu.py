@@ -217,20 +217,20 @@ def test_abi_version_is_still_17_and_the_new_structs_append_the_tail():
     import subprocess
     from wavjepa_amd import _abi
     rel = _abi.load()
-    lib = _abi.load_dropout()
-    S = {**_abi.STRUCTS, **_abi.DROPOUT_STRUCTS}
+    lib = _abi.load("dropout")
+    S = {**_abi.STRUCTS, **_abi.LIBRARIES["dropout"].struct_types}
     assert _abi.DEFINES["WJ_ABI_VERSION"] == 17 and rel.wj_abi_version() == 17
-    assert not set(_abi.DROPOUT_FUNCTIONS) & set(_abi.FUNCTIONS) and not set(NEW) & set(_abi.ENTRY_ARGS)
+    assert not set(_abi.LIBRARIES["dropout"].functions) & set(_abi.FUNCTIONS) and not set(NEW) & set(_abi.ENTRY_ARGS)
     assert not any(hasattr(rel, fn) for fn in NEW)
     assert ctypes.sizeof(S["wj_dropout_args"]) == 24 == lib.wj_dropout_struct_size(b"wj_dropout_args")
     assert ctypes.sizeof(S["wj_dropout_rows_args"]) == 56
     assert lib.wj_dropout_struct_size(b"wj_no_such_struct") == -1 and lib.wj_dropout_struct_size(None) == -1
     for fn, name in NEW.items():
-        assert fn in _abi.DROPOUT_FUNCTIONS and hasattr(lib, fn) and _abi.DROPOUT_ENTRY_ARGS[fn] == name
+        assert fn in _abi.LIBRARIES["dropout"].functions and hasattr(lib, fn) and _abi.LIBRARIES["dropout"].entry_args[fn] == name
         assert lib.wj_dropout_struct_size(name.encode()) == ctypes.sizeof(S[name]) > 0
-    out = subprocess.run(["nm", "-D", "--defined-only", _abi.DROPOUT_LIB_PATH], capture_output=True, text=True, check=True).stdout
+    out = subprocess.run(["nm", "-D", "--defined-only", _abi.LIBRARIES["dropout"].path], capture_output=True, text=True, check=True).stdout
     exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
-    assert exported == set(_abi.DROPOUT_FUNCTIONS) == set(NEW) | {"wj_dropout_struct_size", "wj_dropout_workspace_bytes"}, sorted(exported)
+    assert exported == set(_abi.LIBRARIES["dropout"].functions) == set(NEW) | {"wj_dropout_struct_size", "wj_dropout_workspace_bytes"}, sorted(exported)
     for name, parent in (("wj_ln_fwd_drop_args", "wj_ln_fwd_args"), ("wj_ln_bwd_drop_args", "wj_ln_bwd_args"),
                          ("wj_attn_fwd_drop_args", "wj_attn_fwd_args"), ("wj_attn_bwd_drop_args", "wj_attn_bwd_args")):
         assert ctypes.sizeof(S[name]) == ctypes.sizeof(S[parent]) + 24      # the parent's struct, then the tail
@@ -240,13 +240,13 @@ def test_abi_version_is_still_17_and_the_new_structs_append_the_tail():
 
 def _call(fn, a):
     from wavjepa_amd import _abi
-    return int(getattr(_abi.load_dropout(), fn)(ctypes.byref(a), None))
+    return int(getattr(_abi.load("dropout"), fn)(ctypes.byref(a), None))
 
 
 def test_argument_errors_are_answered_before_a_launch():
     from wavjepa_amd import _abi, ops
-    S = {**_abi.STRUCTS, **_abi.DROPOUT_STRUCTS}
-    lib = _abi.load_dropout()
+    S = {**_abi.STRUCTS, **_abi.LIBRARIES["dropout"].struct_types}
+    lib = _abi.load("dropout")
     for fn in NEW:
         assert int(getattr(lib, fn)(None, None)) == -1
     ptr = 4096                                            # never dereferenced: every call below is refused on the host
@@ -302,11 +302,11 @@ def test_dropout_library_kernels_have_no_mfma_result_read_across_a_branch(tmp_pa
 
     def scan(src):
         asm = str(tmp_path / (src + ".s"))
-        r = subprocess.run([hipcc] + [f for f in B.FLAGS if f != "-fPIC"] + B.DROPOUT_FLAGS + ["-S", "--cuda-device-only", "-o", asm,
+        r = subprocess.run([hipcc] + [f for f in B.FLAGS if f != "-fPIC"] + B.LIBRARIES["dropout"].flags + ["-S", "--cuda-device-only", "-o", asm,
                             os.path.join(root, "wavjepa_amd", "csrc", src)], capture_output=True, text=True)
         assert r.returncode == 0, r.stderr[-2000:]
         r = subprocess.run([sys.executable, os.path.join(root, "tools", "mfma_hazard_scan.py"), asm], capture_output=True, text=True)
         return src, r.returncode, r.stdout[-1500:]
     with ThreadPoolExecutor(max_workers=4) as ex:
-        for src, rc, out in ex.map(scan, B.DROPOUT_SOURCES):
+        for src, rc, out in ex.map(scan, B.LIBRARIES["dropout"].sources):
             assert rc == 0, (src, out)

@@ -315,7 +315,7 @@ def test_workspace_query_never_faults_and_knows_every_entry():
     headers is answered in-process with a value >= -1 (an entry the library's table lacks would fail here too: its answer would be the
     -1 of an unknown name where 0 or more is due), and the entries that refuse zero dimensions answer their smallest valid ones."""
     from wavjepa_amd import _abi
-    lab = _abi.load_lab()
+    lab = _abi.load("lab")
     structs = {**_abi.STRUCTS, **_abi.LAB_STRUCTS}
     smallest = {"wj_conv_ln_gelu_bwd": dict(M=1, C=64),
                 "wj_conv0_ln_gelu_bwd": dict(N=3, C_in=1, C=64, k=10, L_out=162),
@@ -352,7 +352,7 @@ def test_derived_prototypes_equal_the_former_hand_table():
                "wj_gemm_release_stream": [p], "wj_ln_bwd_partial_rows": [i, i], "wj_ln_pre_bwd_partial_rows": [i, i],
                "wj_conv_ln_bwd_partial_rows": [i, i], "wj_scatter_fill_bwd_partial_rows": [i, i], "wj_rccl_unique_id": [p],
                "wj_rccl_bucket_allreduce_init": [p], "wj_rccl_bucket_allreduce_finalize": []}
-    lab = _abi.load_lab()
+    lab = _abi.load("lab")
     for fn, argtypes in by_hand.items():
         f = getattr(lab, fn)
         assert list(f.argtypes) == argtypes and f.restype is ctypes.c_int, fn
@@ -770,7 +770,7 @@ def test_release_library_exports_compute_and_query_entries_only():
         assert gone not in rel
     lab = exported(_abi.LAB_LIB_PATH)
     assert lab == rel | set(_abi.LAB_FUNCTIONS) and set(_abi.LAB_FUNCTIONS) == {"wj_debug_persist_stamps", "wj_collective_footprint"}
-    assert _abi.load_lab().wj_abi_version() == _abi.load().wj_abi_version() == _abi.DEFINES["WJ_ABI_VERSION"]
+    assert _abi.load("lab").wj_abi_version() == _abi.load().wj_abi_version() == _abi.DEFINES["WJ_ABI_VERSION"]
 
 
 def test_compiled_kernels_have_no_mfma_result_read_across_a_branch(tmp_path):

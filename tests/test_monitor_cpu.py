@@ -121,18 +121,18 @@ def test_abi_of_the_monitor_entry():
     """The entry lives in a library and a header of its own: what libwavjepa_hip.so exports and declares has not moved."""
     import subprocess
     from wavjepa_amd import _abi, ops
-    rel, lib = _abi.load(), _abi.load_monitor()
+    rel, lib = _abi.load(), _abi.load("monitor")
     assert _abi.DEFINES["WJ_ABI_VERSION"] == 17 == rel.wj_abi_version()
     assert "wj_masked_moments" not in _abi.FUNCTIONS and "wj_masked_moments" not in _abi.ENTRY_ARGS and not hasattr(rel, "wj_masked_moments")
-    assert _abi.MONITOR_ENTRY_ARGS == {"wj_masked_moments": "wj_moments_args"}
-    S = _abi.MONITOR_STRUCTS["wj_moments_args"]
+    assert _abi.LIBRARIES["monitor"].entry_args == {"wj_masked_moments": "wj_moments_args"}
+    S = _abi.LIBRARIES["monitor"].struct_types["wj_moments_args"]
     assert ctypes.sizeof(S) == 7 * 8 + 5 * 4 + 4 == lib.wj_monitor_struct_size(b"wj_moments_args")
     assert [n for n, _ in S._fields_] == ["preds", "targets", "tgt", "rows", "out", "col", "workspace", "B", "G", "T", "D", "n_rows"]
     assert lib.wj_monitor_struct_size(b"wj_mse_args") == -1 and lib.wj_monitor_struct_size(None) == -1
-    out = subprocess.run(["nm", "-D", "--defined-only", _abi.MONITOR_LIB_PATH], capture_output=True, text=True, check=True).stdout
+    out = subprocess.run(["nm", "-D", "--defined-only", _abi.LIBRARIES["monitor"].path], capture_output=True, text=True, check=True).stdout
     exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
-    assert exported == set(_abi.MONITOR_FUNCTIONS) == {"wj_masked_moments", "wj_monitor_struct_size", "wj_monitor_workspace_bytes"}
-    assert ops.MOMENTS_ROWS == _abi.MONITOR_DEFINES["WJ_MOMENTS_ROWS"] > 0 and ops._ENTRY_STRUCT["wj_masked_moments"] is S
+    assert exported == set(_abi.LIBRARIES["monitor"].functions) == {"wj_masked_moments", "wj_monitor_struct_size", "wj_monitor_workspace_bytes"}
+    assert ops.MOMENTS_ROWS == _abi.LIBRARIES["monitor"].defines["WJ_MOMENTS_ROWS"] > 0 and ops._ENTRY_STRUCT["wj_masked_moments"] is S
     # the scratch: a count per row group, then [2][2][D padded to the column slab] doubles per row group, for the longest row list
     R, Dc = ops.MOMENTS_ROWS, ops.MOMENTS_COLS
     for dims, rows, D in ((dict(B=3, G=4, T=50, D=768), 600, 768), (dict(B=1, G=1, T=1, D=8), 1, 8), (dict(B=1, G=1, T=R + 1, D=1000), R + 1, 1000),
@@ -147,8 +147,8 @@ def test_abi_of_the_monitor_entry():
 
 def test_monitor_entry_rejects_bad_arguments_without_a_gpu():
     from wavjepa_amd import _abi, ops
-    lib = _abi.load_monitor()
-    S = _abi.MONITOR_STRUCTS["wj_moments_args"]
+    lib = _abi.load("monitor")
+    S = _abi.LIBRARIES["monitor"].struct_types["wj_moments_args"]
     ptr = 4096                                                  # never dereferenced: every call below is refused on the host
     good = dict(preds=ptr, targets=ptr, tgt=ptr, out=ptr, workspace=ptr, B=2, G=2, T=8, D=64)
     call = lambda **kw: int(lib.wj_masked_moments(ctypes.byref(S(**dict(good, **kw))), None))

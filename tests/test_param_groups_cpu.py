@@ -290,19 +290,19 @@ def test_abi_of_the_optim_entry():
     """The entry lives in a library and a header of its own: what libwavjepa_hip.so exports and declares has not moved."""
     import subprocess
     from wavjepa_amd import _abi, ops
-    rel, lib = _abi.load(), _abi.load_optim()
+    rel, lib = _abi.load(), _abi.load("optim")
     assert _abi.DEFINES["WJ_ABI_VERSION"] == 17 == rel.wj_abi_version()
     assert "wj_adamw_groups_step" not in _abi.FUNCTIONS and "wj_adamw_groups_step" not in _abi.ENTRY_ARGS and not hasattr(rel, "wj_adamw_groups_step")
-    assert _abi.OPTIM_ENTRY_ARGS == {"wj_adamw_groups_step": "wj_adamw_groups_args"}
-    S = _abi.OPTIM_STRUCTS["wj_adamw_groups_args"]
+    assert _abi.LIBRARIES["optim"].entry_args == {"wj_adamw_groups_step": "wj_adamw_groups_args"}
+    S = _abi.LIBRARIES["optim"].struct_types["wj_adamw_groups_args"]
     assert ctypes.sizeof(S) == 6 * 8 + 8 + 7 * 4 + 3 * 4 + 2 * 64 * 4 + 8 + 8 == lib.wj_optim_struct_size(b"wj_adamw_groups_args")
     old = [n for n, _ in _abi.STRUCTS["wj_adamw_args"]._fields_]
     new = [n for n, _ in S._fields_]
     assert new == [n for n in old if n not in ("lr", "weight_decay")] + ["n_groups", "lr", "weight_decay", "group_map", "first"]
     assert lib.wj_optim_struct_size(b"wj_adamw_args") == -1 and lib.wj_optim_struct_size(None) == -1
-    out = subprocess.run(["nm", "-D", "--defined-only", _abi.OPTIM_LIB_PATH], capture_output=True, text=True, check=True).stdout
+    out = subprocess.run(["nm", "-D", "--defined-only", _abi.LIBRARIES["optim"].path], capture_output=True, text=True, check=True).stdout
     exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
-    assert exported == set(_abi.OPTIM_FUNCTIONS) == {"wj_adamw_groups_step", "wj_optim_struct_size", "wj_optim_workspace_bytes"}
+    assert exported == set(_abi.LIBRARIES["optim"].functions) == {"wj_adamw_groups_step", "wj_optim_struct_size", "wj_optim_workspace_bytes"}
     assert ops.ADAMW_MAX_GROUPS == 64 and ops.ADAMW_GRANULE == 8 and ops._ENTRY_STRUCT["wj_adamw_groups_step"] is S
     assert int(lib.wj_optim_workspace_bytes(b"wj_adamw_groups_step", ctypes.byref(S()))) == 0
     assert int(lib.wj_optim_workspace_bytes(b"wj_adamw_step", ctypes.byref(S()))) == -1
@@ -311,8 +311,8 @@ def test_abi_of_the_optim_entry():
 
 def test_optim_entry_rejects_bad_arguments_without_a_gpu():
     from wavjepa_amd import _abi, ops
-    lib = _abi.load_optim()
-    S = _abi.OPTIM_STRUCTS["wj_adamw_groups_args"]
+    lib = _abi.load("optim")
+    S = _abi.LIBRARIES["optim"].struct_types["wj_adamw_groups_args"]
     ptr = 4096                                                  # never dereferenced: every call below is refused on the host
     good = dict(p=ptr, g=ptr, m=ptr, v=ptr, p_bf16=ptr, sumsq=ptr, n=1032, beta1=0.9, beta2=0.98, eps=1e-6, bc1=0.1, bc2=0.02, max_norm=5.0,
                 grad_scale=1.0, n_groups=2, group_map=ptr, first=8)

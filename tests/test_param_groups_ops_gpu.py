@@ -120,14 +120,14 @@ def test_grouped_step_on_a_sub_range(ops, n, start, lay, kind, state, wg, zg, wi
 
 def test_refused_calls_write_nothing(ops):
     from wavjepa_amd import _abi
-    lib = _abi.load_optim()
+    lib = _abi.load("optim")
     stream = torch.cuda.current_stream().cuda_stream
     n, lo = 1032, 8
     bufs = {k: Range(n, lo) for k in ("p", "g", "m", "v")}
     b16 = Range(n, lo, torch.bfloat16)
     ss = torch.ones(1, device=dev())
     gmap = torch.zeros((lo + n) // 8, dtype=torch.uint8, device=dev())
-    S = _abi.OPTIM_STRUCTS["wj_adamw_groups_args"]
+    S = _abi.LIBRARIES["optim"].struct_types["wj_adamw_groups_args"]
     table = ctypes.c_float * 64
     good = dict(p=bufs["p"].ptr, g=bufs["g"].ptr, m=bufs["m"].ptr, v=bufs["v"].ptr, p_bf16=b16.ptr, sumsq=ss.data_ptr(), n=n, beta1=0.9,
                 beta2=0.98, eps=1e-6, bc1=0.1, bc2=0.02, max_norm=5.0, grad_scale=1.0, workgroups=0, zero_grad=1, n_groups=2,

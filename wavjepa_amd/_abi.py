@@ -1,8 +1,8 @@
-"""ctypes binding of libwavjepa_hip.so.
+"""ctypes binding of libwavjepa_hip.so and of the libraries beside it (LIBRARIES: one row each).
 
-The argument structs are generated from `include/wavjepa_hip.h` itself (a tiny parser for its plain-C struct
-syntax), so the Python mirror cannot drift from the header; sizes are cross-checked against the library's own
-`wj_struct_size`.  There is NO fallback: if the shared library is missing or a symbol is absent, importing the
+The argument structs are generated from the headers under `include/` themselves (a tiny parser for their plain-C struct
+syntax), so the Python mirror cannot drift from a header; sizes are cross-checked against each library's own
+struct-size query.  There is NO fallback: if a shared library is missing or a symbol is absent, the first use of the
 product path fails loudly.
 """
 from __future__ import annotations
@@ -15,12 +15,9 @@ from typing import Dict, List, Tuple
 HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(os.path.dirname(HERE), "include", "wavjepa_hip.h")
 LAB_HEADER = os.path.join(os.path.dirname(HERE), "include", "wavjepa_hip_lab.h")
-DROPOUT_HEADER = os.path.join(os.path.dirname(HERE), "include", "wavjepa_hip_dropout.h")
 LIB_PATH = os.environ.get("WAVJEPA_HIP_LIB") or os.path.join(HERE, "lib", "libwavjepa_hip.so")   # override: A/B and ablation builds
-# the laboratory build of the same sources (-DWJ_LAB): extra diagnostic entries + every A/B switch; loaded only by load_lab()
+# the laboratory build of the same sources (-DWJ_LAB): extra diagnostic entries + every A/B switch; loaded only by load("lab")
 LAB_LIB_PATH = os.environ.get("WAVJEPA_HIP_LAB_LIB") or os.path.join(HERE, "lib", "libwavjepa_hip_lab.so")
-# the dropout forms of the LayerNorm / streamed-attention kernels and wj_dropout_rows (include/wavjepa_hip_dropout.h); loaded by load_dropout()
-DROPOUT_LIB_PATH = os.path.join(HERE, "lib", "libwavjepa_hip_dropout.so")
 
 _SCALARS = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "float": ctypes.c_float, "int": ctypes.c_int,
             "uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32}
@@ -41,6 +38,7 @@ class Header:
 
     def __init__(self, path: str, known: "Header" = None):
         """known: the header this one includes (its structs may be embedded by value)"""
+        self.path = path
         text = _strip_comments(open(path).read())
         self.defines = {k: int(v, 0) for k, v in re.findall(r"^\s*#\s*define\s+(WJ_\w+)\s+(-?(?:0x[0-9a-fA-F]+|\d+))\s*$", text, flags=re.M)}
         self.structs: Dict[str, List[Tuple[str, object]]] = {}
@@ -94,166 +92,67 @@ def _param_ctype(param: str):
 
 
 _HEADER, _LAB = Header(HEADER), Header(LAB_HEADER)
+
+
+class Library:
+    """One shared library of the package: what its header(s) declare (several headers: the union, in order), its file, the names of its
+    two query entries and, once load() has bound it, its handle."""
+
+    def __init__(self, headers: List[Header], path: str, struct_size: str = "wj_struct_size", workspace_bytes: str = "wj_workspace_bytes"):
+        self.headers, self.path, self.struct_size, self.workspace_bytes = headers, path, struct_size, workspace_bytes
+        self.handle = None
+        for what in ("struct_types", "functions", "entry_args", "enums", "defines"):
+            setattr(self, what, {k: v for h in headers for k, v in getattr(h, what).items()})
+
+
+def _side(name: str) -> Library:
+    """A side library: include/wavjepa_hip_<name>.h (which may embed the release header's structs), lib/libwavjepa_hip_<name>.so,
+    wj_<name>_struct_size and wj_<name>_workspace_bytes.  It declares no wj_abi_version: a header, a function list and an entry map of
+    its own, and what describes libwavjepa_hip.so is unchanged by it."""
+    return Library([Header(os.path.join(os.path.dirname(HEADER), f"wavjepa_hip_{name}.h"), known=_HEADER)],
+                   os.path.join(HERE, "lib", f"libwavjepa_hip_{name}.so"), f"wj_{name}_struct_size", f"wj_{name}_workspace_bytes")
+
+
+# Every shared library, keyed as in wavjepa_amd.build.LIBRARIES; headers are parsed here, a .so is loaded on first use only.
+LIBRARIES = {
+    "release": Library([_HEADER], LIB_PATH),
+    "dropout": _side("dropout"),     # the dropout forms of the LayerNorm / streamed-attention kernels and wj_dropout_rows
+    "monitor": _side("monitor"),     # wj_masked_moments, the collapse monitor
+    "act": _side("act"),             # wj_gemm_bf16_act: linear1's forward GEMM with the activation chosen per call
+    "optim": _side("optim"),         # wj_adamw_groups_step: the AdamW pass with parameter groups
+    # the release entries plus the diagnostic ones.  Used by tools/, the all-reduce rehearsal (bench.py --emulate-allreduce) and the
+    # tests that dissect a kernel; never by the training / inference path
+    "lab": Library([_HEADER, _LAB], LAB_LIB_PATH),
+}
+_RELEASE, _LAB_LIBRARY = LIBRARIES["release"], LIBRARIES["lab"]
+# stream entry -> the library that has it (an entry of the release header: the release library, not lab)
+_ENTRY_LIBRARY = {fn: library for library in reversed(list(LIBRARIES.values())) for fn in library.entry_args}
+
 _STRUCT_FIELDS, ENUMS, DEFINES = _HEADER.structs, _HEADER.enums, _HEADER.defines
-FUNCTIONS, LAB_FUNCTIONS = list(_HEADER.functions), list(_LAB.functions)
-_PROTOTYPES = {**_HEADER.functions, **_LAB.functions}            # name -> (restype, argtypes)
-ENTRY_ARGS = {**_HEADER.entry_args, **_LAB.entry_args}           # stream entry -> its argument struct
-
-
 STRUCTS, LAB_STRUCTS = _HEADER.struct_types, _LAB.struct_types
-# libwavjepa_hip_dropout.so: a header, a function list and an entry map of its own -- what describes libwavjepa_hip.so above is unchanged
-_DROP = Header(DROPOUT_HEADER, known=_HEADER)
-DROPOUT_STRUCTS, DROPOUT_FUNCTIONS, DROPOUT_ENTRY_ARGS = _DROP.struct_types, list(_DROP.functions), dict(_DROP.entry_args)
-
-# libwavjepa_hip_monitor.so (wj_masked_moments, the collapse monitor): likewise a header, a function list and an entry map of its own
-MONITOR_HEADER = os.path.join(os.path.dirname(HERE), "include", "wavjepa_hip_monitor.h")
-MONITOR_LIB_PATH = os.path.join(HERE, "lib", "libwavjepa_hip_monitor.so")
-_MON = Header(MONITOR_HEADER, known=_HEADER)
-MONITOR_STRUCTS, MONITOR_FUNCTIONS, MONITOR_ENTRY_ARGS, MONITOR_DEFINES = _MON.struct_types, list(_MON.functions), dict(_MON.entry_args), _MON.defines
-
-# libwavjepa_hip_act.so (wj_gemm_bf16_act: linear1's forward GEMM with the activation chosen per call): likewise
-ACT_HEADER = os.path.join(os.path.dirname(HERE), "include", "wavjepa_hip_act.h")
-ACT_LIB_PATH = os.path.join(HERE, "lib", "libwavjepa_hip_act.so")
-_ACT = Header(ACT_HEADER, known=_HEADER)
-ACT_STRUCTS, ACT_FUNCTIONS, ACT_ENTRY_ARGS, ACT_ENUMS = _ACT.struct_types, list(_ACT.functions), dict(_ACT.entry_args), _ACT.enums
-
-# libwavjepa_hip_optim.so (wj_adamw_groups_step: the AdamW pass with parameter groups): likewise
-OPTIM_HEADER = os.path.join(os.path.dirname(HERE), "include", "wavjepa_hip_optim.h")
-OPTIM_LIB_PATH = os.path.join(HERE, "lib", "libwavjepa_hip_optim.so")
-_OPT = Header(OPTIM_HEADER, known=_HEADER)
-OPTIM_STRUCTS, OPTIM_FUNCTIONS, OPTIM_ENTRY_ARGS, OPTIM_DEFINES = _OPT.struct_types, list(_OPT.functions), dict(_OPT.entry_args), _OPT.defines
-
-_lib = None
-_lab_lib = None
-_dropout_lib = None
-_monitor_lib = None
-_act_lib = None
-_optim_lib = None
+FUNCTIONS, LAB_FUNCTIONS = list(_HEADER.functions), list(_LAB.functions)
+ENTRY_ARGS = _LAB_LIBRARY.entry_args                             # stream entry -> its argument struct, release and lab
 
 
-def optim_loaded() -> bool:
-    """True once libwavjepa_hip_optim.so is in the process (an optimiser with one parameter group never loads it)."""
-    return _optim_lib is not None
+def loaded(name: str) -> bool:
+    """True once that library is in the process (a model whose stacks all run GELU never loads "act", an optimiser with one parameter
+    group never loads "optim")."""
+    return LIBRARIES[name].handle is not None
 
 
-def load_optim():
-    """libwavjepa_hip_optim.so (once), its struct sizes cross-checked against its own wj_optim_struct_size.  Loaded behind the release
-    library, as load_dropout() does."""
-    global _optim_lib
-    if _optim_lib is None:
-        load()
-        if not os.path.exists(OPTIM_LIB_PATH):
-            raise WavJepaHipError(f"{OPTIM_LIB_PATH} is missing: run `python -m wavjepa_amd.build` (or __graft_entry__.build())")
-        lib = ctypes.CDLL(OPTIM_LIB_PATH)
-        for fn in OPTIM_FUNCTIONS:
-            if not hasattr(lib, fn):
-                raise WavJepaHipError(f"{OPTIM_LIB_PATH} does not export {fn} (declared in include/wavjepa_hip_optim.h); rebuild it")
-            f = getattr(lib, fn)
-            f.restype, f.argtypes = _OPT.functions[fn]
-        for name, cls in OPTIM_STRUCTS.items():
-            want = lib.wj_optim_struct_size(name.encode())
-            if want != ctypes.sizeof(cls):
-                raise WavJepaHipError(f"struct {name}: header mirror is {ctypes.sizeof(cls)} bytes, library says {want}")
-        _optim_lib = lib
-    return _optim_lib
+def load(name: str = "release"):
+    """The handle of a library of LIBRARIES, loaded and checked on first use.  Raises WavJepaHipError when it is not built."""
+    library = LIBRARIES[name]
+    return library.handle or _bind(library)
 
 
-def act_loaded() -> bool:
-    """True once libwavjepa_hip_act.so is in the process (a model whose stacks all run GELU never loads it)."""
-    return _act_lib is not None
-
-
-def load_act():
-    """libwavjepa_hip_act.so (once), its struct sizes cross-checked against its own wj_act_struct_size.  Loaded behind the release
-    library, as load_dropout() does."""
-    global _act_lib
-    if _act_lib is None:
-        load()
-        if not os.path.exists(ACT_LIB_PATH):
-            raise WavJepaHipError(f"{ACT_LIB_PATH} is missing: run `python -m wavjepa_amd.build` (or __graft_entry__.build())")
-        lib = ctypes.CDLL(ACT_LIB_PATH)
-        for fn in ACT_FUNCTIONS:
-            if not hasattr(lib, fn):
-                raise WavJepaHipError(f"{ACT_LIB_PATH} does not export {fn} (declared in include/wavjepa_hip_act.h); rebuild it")
-            f = getattr(lib, fn)
-            f.restype, f.argtypes = _ACT.functions[fn]
-        for name, cls in ACT_STRUCTS.items():
-            want = lib.wj_act_struct_size(name.encode())
-            if want != ctypes.sizeof(cls):
-                raise WavJepaHipError(f"struct {name}: header mirror is {ctypes.sizeof(cls)} bytes, library says {want}")
-        _act_lib = lib
-    return _act_lib
-
-
-def load_monitor():
-    """libwavjepa_hip_monitor.so (once), its struct sizes cross-checked against its own wj_monitor_struct_size.  Loaded behind the release
-    library, as load_dropout() does."""
-    global _monitor_lib
-    if _monitor_lib is None:
-        load()
-        if not os.path.exists(MONITOR_LIB_PATH):
-            raise WavJepaHipError(f"{MONITOR_LIB_PATH} is missing: run `python -m wavjepa_amd.build` (or __graft_entry__.build())")
-        lib = ctypes.CDLL(MONITOR_LIB_PATH)
-        for fn in MONITOR_FUNCTIONS:
-            if not hasattr(lib, fn):
-                raise WavJepaHipError(f"{MONITOR_LIB_PATH} does not export {fn} (declared in include/wavjepa_hip_monitor.h); rebuild it")
-            f = getattr(lib, fn)
-            f.restype, f.argtypes = _MON.functions[fn]
-        for name, cls in MONITOR_STRUCTS.items():
-            want = lib.wj_monitor_struct_size(name.encode())
-            if want != ctypes.sizeof(cls):
-                raise WavJepaHipError(f"struct {name}: header mirror is {ctypes.sizeof(cls)} bytes, library says {want}")
-        _monitor_lib = lib
-    return _monitor_lib
-
-
-def load_dropout():
-    """libwavjepa_hip_dropout.so (once), its struct sizes cross-checked against its own wj_dropout_struct_size.  Loaded behind the release
-    library, so that both bind to the HIP runtime torch brought."""
-    global _dropout_lib
-    if _dropout_lib is None:
-        load()
-        if not os.path.exists(DROPOUT_LIB_PATH):
-            raise WavJepaHipError(f"{DROPOUT_LIB_PATH} is missing: run `python -m wavjepa_amd.build` (or __graft_entry__.build())")
-        lib = ctypes.CDLL(DROPOUT_LIB_PATH)
-        for fn in DROPOUT_FUNCTIONS:
-            if not hasattr(lib, fn):
-                raise WavJepaHipError(f"{DROPOUT_LIB_PATH} does not export {fn} (declared in include/wavjepa_hip_dropout.h); rebuild it")
-            f = getattr(lib, fn)
-            f.restype, f.argtypes = _DROP.functions[fn]
-        for name, cls in DROPOUT_STRUCTS.items():
-            want = lib.wj_dropout_struct_size(name.encode())
-            if want != ctypes.sizeof(cls):
-                raise WavJepaHipError(f"struct {name}: header mirror is {ctypes.sizeof(cls)} bytes, library says {want}")
-        _dropout_lib = lib
-    return _dropout_lib
-
-
-def lib_path() -> str:
-    return LIB_PATH
-
-
-def load_lab():
-    """The laboratory library (include/wavjepa_hip_lab.h): the release entries plus the diagnostic ones.  Used by tools/, the all-reduce
-    rehearsal (bench.py --emulate-allreduce) and the tests that dissect a kernel; never by the training / inference path."""
-    global _lab_lib
-    if _lab_lib is None:
-        _lab_lib = _load(LAB_LIB_PATH, FUNCTIONS + LAB_FUNCTIONS, {**STRUCTS, **LAB_STRUCTS})
-    return _lab_lib
-
-
-def load():
-    """Load the library (once).  Raises WavJepaHipError when it is not built."""
-    global _lib
-    if _lib is None:
-        _lib = _load(LIB_PATH, FUNCTIONS, STRUCTS)
-    return _lib
-
-
-def _load(LIB_PATH: str, FUNCTIONS, STRUCTS):
-    if not os.path.exists(LIB_PATH):
+def _bind(library: Library):
+    path = library.path
+    if "wj_abi_version" not in library.functions:
+        load()          # a side library goes behind the release library, so that both bind to the HIP runtime torch brought
+    if not os.path.exists(path):
         raise WavJepaHipError(
-            f"{LIB_PATH} is missing: the HIP extension is not built. Run `python -m wavjepa_amd.build` "
+            f"{path} is missing: the HIP extension is not built. Run `python -m wavjepa_amd.build` "
             "(or __graft_entry__.build()). wavjepa_amd has no CPU/PyTorch fallback by design.")
     # PyTorch-ROCm ships its own libamdhip64; the library must bind to THAT runtime (the one that owns the tensors and streams
     # it is handed), so torch is loaded first and the dynamic linker resolves our libamdhip64 dependency to the copy already
@@ -261,36 +160,31 @@ def _load(LIB_PATH: str, FUNCTIONS, STRUCTS):
     # device is detected".
     import torch  # noqa: F401
     try:
-        lib = ctypes.CDLL(LIB_PATH)
+        lib = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover
-        raise WavJepaHipError(f"cannot load {LIB_PATH}: {e}") from e
-    for fn in FUNCTIONS:
-        if not hasattr(lib, fn):
-            raise WavJepaHipError(f"{LIB_PATH} does not export {fn} (declared in include/wavjepa_hip.h); rebuild it")
-        f = getattr(lib, fn)
-        f.restype, f.argtypes = _PROTOTYPES[fn]
-    if lib.wj_abi_version() != DEFINES["WJ_ABI_VERSION"]:
-        raise WavJepaHipError(f"{LIB_PATH} reports ABI version {lib.wj_abi_version()}, include/wavjepa_hip.h declares "
+        raise WavJepaHipError(f"cannot load {path}: {e}") from e
+    for header in library.headers:
+        for fn, prototype in header.functions.items():
+            if not hasattr(lib, fn):
+                raise WavJepaHipError(f"{path} does not export {fn} (declared in include/{os.path.basename(header.path)}); rebuild it")
+            f = getattr(lib, fn)
+            f.restype, f.argtypes = prototype
+    if "wj_abi_version" in library.functions and lib.wj_abi_version() != DEFINES["WJ_ABI_VERSION"]:
+        raise WavJepaHipError(f"{path} reports ABI version {lib.wj_abi_version()}, include/wavjepa_hip.h declares "
                               f"{DEFINES['WJ_ABI_VERSION']}: stale library, rebuild it (python -m wavjepa_amd.build)")
-    for name, cls in STRUCTS.items():
-        want = lib.wj_struct_size(name.encode())
+    struct_size = getattr(lib, library.struct_size)
+    for name, cls in library.struct_types.items():
+        want = struct_size(name.encode())
         if want != ctypes.sizeof(cls):
             raise WavJepaHipError(f"struct {name}: header mirror is {ctypes.sizeof(cls)} bytes, library says {want}")
+    library.handle = lib
     return lib
 
 
 def workspace_bytes(fn_name: str, args_struct) -> int:
-    """Scratch bytes the call `fn_name(args_struct)` needs (pointers in the struct are ignored)."""
-    if fn_name in DROPOUT_ENTRY_ARGS:
-        n = int(load_dropout().wj_dropout_workspace_bytes(fn_name.encode(), ctypes.byref(args_struct)))
-    elif fn_name in MONITOR_ENTRY_ARGS:
-        n = int(load_monitor().wj_monitor_workspace_bytes(fn_name.encode(), ctypes.byref(args_struct)))
-    elif fn_name in ACT_ENTRY_ARGS:
-        n = int(load_act().wj_act_workspace_bytes(fn_name.encode(), ctypes.byref(args_struct)))
-    elif fn_name in OPTIM_ENTRY_ARGS:
-        n = int(load_optim().wj_optim_workspace_bytes(fn_name.encode(), ctypes.byref(args_struct)))
-    else:
-        n = int(load().wj_workspace_bytes(fn_name.encode(), ctypes.byref(args_struct)))
+    """Scratch bytes the call `fn_name(args_struct)` needs (pointers in the struct are ignored), from the library that has the entry."""
+    library = _ENTRY_LIBRARY.get(fn_name, _RELEASE)
+    n = int(getattr(library.handle or _bind(library), library.workspace_bytes)(fn_name.encode(), ctypes.byref(args_struct)))
     if n < 0:
         raise WavJepaHipError(f"wj_workspace_bytes: unknown entry point {fn_name}")
     return n
@@ -300,12 +194,7 @@ _ERR = {-1: "invalid argument", -2: "kernel launch failed", -3: "unsupported con
 
 
 def call(fn_name: str, args_struct, stream: int, lab: bool = False) -> None:
-    if fn_name in ACT_ENTRY_ARGS:
-        lib = load_act()
-    elif fn_name in OPTIM_ENTRY_ARGS:
-        lib = load_optim()
-    else:
-        lib = load_dropout() if fn_name in DROPOUT_ENTRY_ARGS else (load_monitor() if fn_name in MONITOR_ENTRY_ARGS else (load_lab() if lab else load()))
-    rc = getattr(lib, fn_name)(ctypes.byref(args_struct), stream)
+    library = _LAB_LIBRARY if lab else _ENTRY_LIBRARY.get(fn_name, _RELEASE)
+    rc = getattr(library.handle or _bind(library), fn_name)(ctypes.byref(args_struct), stream)
     if rc != 0:
         raise WavJepaHipError(f"{fn_name} failed: {_ERR.get(rc, rc)}")

@@ -4,11 +4,11 @@ from __future__ import annotations
 
 from typing import Optional
 
-from ._abi import ACT_ENUMS, ENUMS, STRUCTS
+from ._abi import ENUMS, LIBRARIES, STRUCTS
 
 Ptr = object
 # feed-forward activation kinds (wj_act)
-ACT = {k[len("WJ_ACT_"):].lower(): v for k, v in ACT_ENUMS.items()}
+ACT = {k[len("WJ_ACT_"):].lower(): v for k, v in LIBRARIES["act"].enums.items()}
 
 
 def gemm_act(A: Ptr, B: Ptr, C: Ptr, *, act: str, M: int, N: int, K: int, lda: int, ldb: int, ldc: int, epilogue: int = ENUMS["WJ_EPI_BIAS_GELU2"],

@@ -7,33 +7,43 @@ import shutil
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
+from typing import NamedTuple
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
-LIB = os.path.join(LIBDIR, "libwavjepa_hip.so")
-LAB_LIB = os.path.join(LIBDIR, "libwavjepa_hip_lab.so")      # the same sources with -DWJ_LAB (include/wavjepa_hip_lab.h): diagnostics + A/B switches
 SOURCES = ["gemm.hip", "gemm_persist.hip", "gemm_pde.hip", "gemm_panel.hip", "norm.hip", "attention.hip", "attention_stream.hip", "conv0.hip", "conv_ln.hip", "misc.hip", "abi.hip", "fp8.hip", "scene.hip", "denoise.hip", "audio_prep.hip", "noise_prep.hip", "rccl_bucket.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-value"]
-# libwavjepa_hip_dropout.so (include/wavjepa_hip_dropout.h): the dropout forms of the LayerNorm and streamed-attention kernels, from the
-# SAME sources with -DWJ_DROPOUT_LIB, and wj_dropout_rows.  -fvisibility=hidden: the parent entries those sources also define stay
-# inside it; it exports what the header declares and nothing else.
-DROPOUT_LIB = os.path.join(LIBDIR, "libwavjepa_hip_dropout.so")
-DROPOUT_SOURCES = ["dropout.hip", "norm.hip", "attention_stream.hip", "dropout_abi.hip"]
-DROPOUT_FLAGS = ["-DWJ_DROPOUT_LIB", "-fvisibility=hidden"]
-# libwavjepa_hip_monitor.so (include/wavjepa_hip_monitor.h): wj_masked_moments, the collapse monitor, and its two query entries
-MONITOR_LIB = os.path.join(LIBDIR, "libwavjepa_hip_monitor.so")
-MONITOR_SOURCES = ["monitor.hip"]
-MONITOR_FLAGS = ["-fvisibility=hidden"]
-# libwavjepa_hip_act.so (include/wavjepa_hip_act.h): wj_gemm_bf16_act, linear1's forward GEMM with the activation chosen per call, from
-# the SAME GEMM sources with -DWJ_ACT_LIB (the one-tile and the persistent kernels; the activation is a template argument there)
-ACT_LIB = os.path.join(LIBDIR, "libwavjepa_hip_act.so")
-ACT_SOURCES = ["gemm.hip", "gemm_persist.hip", "act_abi.hip"]
-ACT_FLAGS = ["-DWJ_ACT_LIB", "-fvisibility=hidden"]
-# libwavjepa_hip_optim.so (include/wavjepa_hip_optim.h): wj_adamw_groups_step, the AdamW pass with parameter groups, and its two query entries
-OPTIM_LIB = os.path.join(LIBDIR, "libwavjepa_hip_optim.so")
-OPTIM_SOURCES = ["optim.hip"]
-OPTIM_FLAGS = ["-fvisibility=hidden"]
+
+
+class Library(NamedTuple):
+    file: str          # under wavjepa_amd/lib
+    sources: list      # under wavjepa_amd/csrc
+    flags: list        # behind FLAGS
+    objdir: str        # under wavjepa_amd/lib
+
+    @property
+    def path(self) -> str:
+        return os.path.join(LIBDIR, self.file)
+
+
+# Every shared library of the package, in build order (the keys are wavjepa_amd._abi.LIBRARIES' too).  A side library exports what its
+# header declares and nothing else: -fvisibility=hidden keeps the release entries that its shared sources also define inside it.
+LIBRARIES = {
+    # compute + query entries, production-safe switches only (include/wavjepa_hip.h)
+    "release": Library("libwavjepa_hip.so", SOURCES, [], "obj"),
+    # the dropout forms of the LayerNorm and streamed-attention kernels, from the SAME sources, and wj_dropout_rows (include/wavjepa_hip_dropout.h)
+    "dropout": Library("libwavjepa_hip_dropout.so", ["dropout.hip", "norm.hip", "attention_stream.hip"], ["-DWJ_DROPOUT_LIB", "-fvisibility=hidden"], "obj_dropout"),
+    # wj_masked_moments, the collapse monitor (include/wavjepa_hip_monitor.h)
+    "monitor": Library("libwavjepa_hip_monitor.so", ["monitor.hip"], ["-fvisibility=hidden"], "obj_monitor"),
+    # wj_gemm_bf16_act, linear1's forward GEMM with the activation chosen per call, from the SAME GEMM sources: the one-tile and the
+    # persistent kernels, the activation a template argument there (include/wavjepa_hip_act.h)
+    "act": Library("libwavjepa_hip_act.so", ["gemm.hip", "gemm_persist.hip"], ["-DWJ_ACT_LIB", "-fvisibility=hidden"], "obj_act"),
+    # wj_adamw_groups_step, the AdamW pass with parameter groups (include/wavjepa_hip_optim.h)
+    "optim": Library("libwavjepa_hip_optim.so", ["optim.hip"], ["-fvisibility=hidden"], "obj_optim"),
+    # the release sources with -DWJ_LAB: the extra entries of include/wavjepa_hip_lab.h and every A/B / diagnostic environment switch
+    "lab": Library("libwavjepa_hip_lab.so", SOURCES, ["-DWJ_LAB"], "obj_lab"),
+}
 
 
 def _hipcc() -> str:
@@ -50,21 +60,15 @@ def _stale(target: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force: bool = False, verbose: bool = True, lab: bool = False, dropout: bool = False, monitor: bool = False, act: bool = False,
-          optim: bool = False) -> str:
-    """The release library (compute + query entries, production-safe switches only), or with lab=True the laboratory variant
-    (libwavjepa_hip_lab.so: -DWJ_LAB, the extra entries of include/wavjepa_hip_lab.h and every A/B / diagnostic environment switch),
-    or with dropout=True libwavjepa_hip_dropout.so, or with monitor=True libwavjepa_hip_monitor.so, or with act=True libwavjepa_hip_act.so,
-    or with optim=True libwavjepa_hip_optim.so."""
+def build(name: str = "release", force: bool = False, verbose: bool = True) -> str:
+    """Compile and link one library of LIBRARIES; with the release library, libwavjepa_io.so too."""
+    library = LIBRARIES[name]
     hipcc = _hipcc()
-    os.makedirs(LIBDIR, exist_ok=True)
-    objdir = os.path.join(LIBDIR, "obj_optim" if optim else "obj_act" if act else ("obj_monitor" if monitor else ("obj_dropout" if dropout else ("obj_lab" if lab else "obj"))))
+    objdir = os.path.join(LIBDIR, library.objdir)
     os.makedirs(objdir, exist_ok=True)
     inc = os.path.join(os.path.dirname(HERE), "include")
     headers = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(inc, "*.h"))
-    flags = FLAGS + (OPTIM_FLAGS if optim else ACT_FLAGS if act else (MONITOR_FLAGS if monitor else (DROPOUT_FLAGS if dropout else (["-DWJ_LAB"] if lab else []))))
-    lib = OPTIM_LIB if optim else ACT_LIB if act else (MONITOR_LIB if monitor else (DROPOUT_LIB if dropout else (LAB_LIB if lab else LIB)))
-    sources = OPTIM_SOURCES if optim else ACT_SOURCES if act else (MONITOR_SOURCES if monitor else (DROPOUT_SOURCES if dropout else SOURCES))
+    flags, lib, sources = FLAGS + library.flags, library.path, library.sources
     jobs = []
     for src in sources:
         s = os.path.join(CSRC, src)
@@ -93,19 +97,15 @@ def build(force: bool = False, verbose: bool = True, lab: bool = False, dropout:
             raise RuntimeError(f"link failed:\n{r.stderr}")
         if verbose:
             print(f"[wavjepa_amd.build] linked {lib}", file=sys.stderr)
-    if not lab and not dropout and not monitor and not act and not optim:
+    if name == "release":
         build_io(force=force, verbose=verbose)
     return lib
 
 
 def build_all(force: bool = False, verbose: bool = True) -> None:
-    """Release + laboratory libraries (what __graft_entry__.build() and the test suite need)."""
-    build(force=force, verbose=verbose)
-    build(force=force, verbose=verbose, dropout=True)
-    build(force=force, verbose=verbose, monitor=True)
-    build(force=force, verbose=verbose, act=True)
-    build(force=force, verbose=verbose, optim=True)
-    build(force=force, verbose=verbose, lab=True)
+    """Every library (what __graft_entry__.build() and the test suite need)."""
+    for name in LIBRARIES:
+        build(name, force=force, verbose=verbose)
 
 
 IO_LIB = os.path.join(LIBDIR, "libwavjepa_io.so")

@@ -1,6 +1,8 @@
-// The entry table of libwavjepa_hip.so: one row per stream entry `int entry(const ARGS*, void* stream)` of include/wavjepa_hip.h
-// (and, under WJ_LAB, of include/wavjepa_hip_lab.h).  csrc/abi.hip generates wj_struct_size, wj_workspace_bytes and a compile-time check
-// of every row against the header's prototype from it; nothing else lists the entries.
+// The entry tables: one row per stream entry `int entry(const ARGS*, void* stream)` of include/wavjepa_hip.h (and, under WJ_LAB, of
+// include/wavjepa_hip_lab.h), then of each side library's header.  WJ_ABI_QUERIES (csrc/abi_queries.h) generates a library's struct-size
+// and workspace queries and a compile-time check of every row against the header's prototype from its table; nothing else lists the
+// entries.  Every library has an <X>_ENTRIES table and an <X>_OTHER_STRUCTS list (the argument structs of its header that no stream
+// entry takes; it may be empty).
 //   E(entry, ARGS)        the entry takes no scratch: the query answers 0
 //   W(entry, ARGS, rule)  `int64_t rule(const ARGS*)`, defined beside the launch that consumes the scratch, answers the bytes for the
 //                         dimensions in ARGS (pointers ignored), -1 for dimensions it refuses; it never faults
@@ -63,10 +65,9 @@
     W(wj_noise_prepare, wj_noise_prepare_args, wj_noise_prepare_ws_bytes)              \
     WJ_LAB_ENTRIES(E, W)
 
-// argument structs of the header that no stream entry takes
 #define WJ_OTHER_STRUCTS(S) S(wj_rccl_init_args)
 
-// libwavjepa_hip_dropout.so (include/wavjepa_hip_dropout.h, csrc/dropout_abi.hip): the same two row forms
+// libwavjepa_hip_dropout.so (include/wavjepa_hip_dropout.h, csrc/dropout.hip)
 #define WJ_DROPOUT_ENTRIES(E, W)                                                       \
     E(wj_dropout_rows, wj_dropout_rows_args)                                           \
     E(wj_layernorm_fwd_drop, wj_ln_fwd_drop_args)                                      \
@@ -75,14 +76,17 @@
     W(wj_attn_stream_bwd_drop, wj_attn_bwd_drop_args, wj_attn_bwd_drop_ws_bytes)
 #define WJ_DROPOUT_OTHER_STRUCTS(S) S(wj_dropout_args)
 
-// libwavjepa_hip_act.so (include/wavjepa_hip_act.h, csrc/act_abi.hip): the same two row forms (the forward GELU forms take no scratch)
+// libwavjepa_hip_act.so (include/wavjepa_hip_act.h, csrc/gemm.hip under WJ_ACT_LIB; the forward GELU forms take no scratch)
 #define WJ_ACT_ENTRIES(E, W)                                                           \
     E(wj_gemm_bf16_act, wj_gemm_act_args)
+#define WJ_ACT_OTHER_STRUCTS(S)
 
-// libwavjepa_hip_monitor.so (include/wavjepa_hip_monitor.h, csrc/monitor.hip): the same two row forms
+// libwavjepa_hip_monitor.so (include/wavjepa_hip_monitor.h, csrc/monitor.hip)
 #define WJ_MONITOR_ENTRIES(E, W)                                                       \
     W(wj_masked_moments, wj_moments_args, wj_masked_moments_ws_bytes)
+#define WJ_MONITOR_OTHER_STRUCTS(S)
 
-// libwavjepa_hip_optim.so (include/wavjepa_hip_optim.h, csrc/optim.hip): the same two row forms
+// libwavjepa_hip_optim.so (include/wavjepa_hip_optim.h, csrc/optim.hip)
 #define WJ_OPTIM_ENTRIES(E, W)                                                         \
     E(wj_adamw_groups_step, wj_adamw_groups_args)
+#define WJ_OPTIM_OTHER_STRUCTS(S)

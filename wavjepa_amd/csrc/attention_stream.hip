@@ -337,7 +337,7 @@ extern "C" int wj_attn_stream_bwd(const wj_attn_bwd_args* a, void* stream) {
 }
 
 #ifdef WJ_DROPOUT_LIB
-extern "C" WJ_DROPOUT_EXPORT int wj_attn_stream_fwd_drop(const wj_attn_fwd_drop_args* ad, void* stream) {
+extern "C" WJ_EXPORT int wj_attn_stream_fwd_drop(const wj_attn_fwd_drop_args* ad, void* stream) {
     WJ_CLEAR_STALE_ERROR();
     if (!ad) return WJ_ERR_ARG;
     const wj_attn_fwd_args* a = &ad->attn;
@@ -357,7 +357,7 @@ extern "C" WJ_DROPOUT_EXPORT int wj_attn_stream_fwd_drop(const wj_attn_fwd_drop_
 
 int64_t wj_attn_bwd_drop_ws_bytes(const wj_attn_bwd_drop_args* a) { return a->attn.B * attn_dbias_row(&a->attn) * 4; }
 
-extern "C" WJ_DROPOUT_EXPORT int wj_attn_stream_bwd_drop(const wj_attn_bwd_drop_args* ad, void* stream) {
+extern "C" WJ_EXPORT int wj_attn_stream_bwd_drop(const wj_attn_bwd_drop_args* ad, void* stream) {
     WJ_CLEAR_STALE_ERROR();
     if (!ad) return WJ_ERR_ARG;
     const wj_attn_bwd_args* a = &ad->attn;

@@ -18,6 +18,10 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 #define WJ_ERR_LAUNCH (-2)
 #define WJ_ERR_UNSUPPORTED (-3)
 
+// What a library built with -fvisibility=hidden exports (the side libraries: the entries of libwavjepa_hip.so that their shared sources
+// also define stay inside them); without the flag it changes nothing.
+#define WJ_EXPORT __attribute__((visibility("default")))
+
 // hipGetLastError() reports the last error of ANY HIP call of this thread -- including benign ones of the host framework (an
 // event query returning hipErrorNotReady) -- so every entry point first discards what it did not cause.
 #define WJ_CLEAR_STALE_ERROR() (void)hipGetLastError()

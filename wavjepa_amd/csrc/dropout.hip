@@ -1,8 +1,9 @@
 // wj_dropout_rows: dropout in place over one or two bf16 [M][N] tensors with the same mask (the FFN site: linear1's gelu and gelu'
 // outputs behind the BIAS_GELU2 GEMM), and the host side of the shared tail wj_dropout_args.  HBM-bound: one 16-byte access = eight
-// elements = one generator call (csrc/dropout_pieces.h) per thread and iteration.
+// elements = one generator call (csrc/dropout_pieces.h) per thread and iteration.  The library's two query entries are at the end.
 #include "common.h"
 #include "dropout_host.h"
+#include "abi_queries.h"
 
 namespace {
 
@@ -30,7 +31,7 @@ __global__ __launch_bounds__(256) void dropout_rows_kernel(bf16_t* __restrict__ 
 
 }  // namespace
 
-extern "C" WJ_DROPOUT_EXPORT int wj_dropout_rows(const wj_dropout_rows_args* a, void* stream) {
+extern "C" WJ_EXPORT int wj_dropout_rows(const wj_dropout_rows_args* a, void* stream) {
     WJ_CLEAR_STALE_ERROR();
     if (!a || !a->x || a->M <= 0 || a->N <= 0 || (a->N & 7) || (a->ldx & 7) || a->ldx < a->N) return WJ_ERR_ARG;
     if (((uintptr_t)a->x & 15) || ((uintptr_t)a->x2 & 15)) return WJ_ERR_ARG;
@@ -44,3 +45,5 @@ extern "C" WJ_DROPOUT_EXPORT int wj_dropout_rows(const wj_dropout_rows_args* a, 
     WJ_CHECK_LAUNCH();
     return WJ_OK;
 }
+
+WJ_ABI_QUERIES(WJ_DROPOUT_ENTRIES, WJ_DROPOUT_OTHER_STRUCTS, wj_dropout_struct_size, wj_dropout_workspace_bytes)

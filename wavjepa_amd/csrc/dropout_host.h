@@ -1,9 +1,8 @@
 // Host side of the shared tail wj_dropout_args: p -> (thr, scale), the checks of every _drop entry.
 // The _drop entries are compiled only into libwavjepa_hip_dropout.so (-DWJ_DROPOUT_LIB -fvisibility=hidden: the parent entries the shared
-// sources also define stay inside that library; WJ_DROPOUT_EXPORT marks what it exports).
+// sources also define stay inside that library; common.h's WJ_EXPORT marks what it exports).
 #pragma once
 #include "../../include/wavjepa_hip_dropout.h"
-#define WJ_DROPOUT_EXPORT __attribute__((visibility("default")))
 #include "dropout_pieces.h"
 
 // false: p outside [0, 1) (or NaN)

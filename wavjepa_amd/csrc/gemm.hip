@@ -1250,6 +1250,7 @@ int dispatch_epi(const wj_gemm_args* a, hipStream_t s) {
 // Built from this file and csrc/gemm_persist.hip with -DWJ_ACT_LIB -fvisibility=hidden; the entries of libwavjepa_hip.so below are
 // not part of it.  The variant comes from pick_variant, so a call takes the schedule wj_gemm_bf16 would give it; the row-panel and
 // deferred-epilogue schedules are not in this library (never picked by themselves in a release build, refused here when forced).
+// The library's two query entries follow the entry.
 #include "../../include/wavjepa_hip_act.h"
 static_assert(WJ_ACT_GELU == ACT_GELU && WJ_ACT_RELU == ACT_RELU && WJ_ACT_GELU_TANH == ACT_GELU_TANH && WJ_ACT_SILU == ACT_SILU &&
               WJ_ACT_SILU + 1 == ACT_KINDS, "wj_act and common.h's ACT_* are one list");
@@ -1270,7 +1271,7 @@ int launch_act(const wj_gemm_args* a, hipStream_t s) {
 }
 }  // namespace
 
-extern "C" __attribute__((visibility("default"))) int wj_gemm_bf16_act(const wj_gemm_act_args* aa, void* stream) {
+extern "C" WJ_EXPORT int wj_gemm_bf16_act(const wj_gemm_act_args* aa, void* stream) {
     WJ_CLEAR_STALE_ERROR();
     if (!aa) return WJ_ERR_ARG;
     const wj_gemm_args* a = &aa->gemm;
@@ -1294,6 +1295,9 @@ extern "C" __attribute__((visibility("default"))) int wj_gemm_bf16_act(const wj_
         default: return launch_act<ACT_GELU>(a, s);
     }
 }
+
+#include "abi_queries.h"
+WJ_ABI_QUERIES(WJ_ACT_ENTRIES, WJ_ACT_OTHER_STRUCTS, wj_act_struct_size, wj_act_workspace_bytes)
 #else
 
 template <int EPI>

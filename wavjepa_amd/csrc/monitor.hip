@@ -13,12 +13,9 @@
 // fp64 throughout because the bound the tests hold this to is about one fp32 ulp of the variance (PARITY.md): fp32 partials of 32
 // rows do not stay inside it, and at 5 fp64 instructions per element the pass is nowhere near the fp64 rate.  Measured
 // (profiles/monitor.txt): pass 1 47 us at the step's shape, pass 2 33 us -- one CU reading the records from the Infinity Cache.
-#include <string.h>
-#include <type_traits>
 #include "stream_pieces.h"
 #include "../../include/wavjepa_hip_monitor.h"
-#include "abi_table.h"
-#define WJ_MONITOR_EXPORT __attribute__((visibility("default")))
+#include "abi_queries.h"
 
 namespace {
 
@@ -212,7 +209,7 @@ int64_t wj_masked_moments_ws_bytes(const wj_moments_args* a) {
     return 8 * (gx + 4 * gx * (int64_t)moments_padded(a->D));
 }
 
-extern "C" WJ_MONITOR_EXPORT int wj_masked_moments(const wj_moments_args* a, void* stream) {
+extern "C" WJ_EXPORT int wj_masked_moments(const wj_moments_args* a, void* stream) {
     const CheckedEntry entry(__func__);
     if (!a || !a->preds || !a->targets || !a->tgt || !a->out || !a->workspace) return WJ_ERR_ARG;
     if (a->B <= 0 || a->G <= 0 || a->T <= 0 || a->D <= 0 || (a->rows && a->n_rows < 0)) return WJ_ERR_ARG;
@@ -229,22 +226,4 @@ extern "C" WJ_MONITOR_EXPORT int wj_masked_moments(const wj_moments_args* a, voi
     return entry.launched();
 }
 
-// ---- the query entries ---------------------------------------------------------------------------------------------------------------
-#define WJ_ROW_CHECK(entry, ARGS, ...) \
-    static_assert(std::is_same_v<decltype(&entry), int (*)(const ARGS*, void*)>, #entry " does not take " #ARGS " in the header");
-WJ_MONITOR_ENTRIES(WJ_ROW_CHECK, WJ_ROW_CHECK)
-
-extern "C" WJ_MONITOR_EXPORT int wj_monitor_struct_size(const char* name) {
-    if (!name) return -1;
-#define WJ_ROW_SZ(entry, ARGS, ...) if (!strcmp(name, #ARGS)) return (int)sizeof(ARGS);
-    WJ_MONITOR_ENTRIES(WJ_ROW_SZ, WJ_ROW_SZ)
-    return -1;
-}
-
-extern "C" WJ_MONITOR_EXPORT int64_t wj_monitor_workspace_bytes(const char* fn, const void* args) {
-    if (!fn || !args) return -1;
-#define WJ_ROW_NONE(entry, ARGS) if (!strcmp(fn, #entry)) return 0;
-#define WJ_ROW_RULE(entry, ARGS, rule) if (!strcmp(fn, #entry)) return rule((const ARGS*)args);
-    WJ_MONITOR_ENTRIES(WJ_ROW_NONE, WJ_ROW_RULE)
-    return -1;
-}
+WJ_ABI_QUERIES(WJ_MONITOR_ENTRIES, WJ_MONITOR_OTHER_STRUCTS, wj_monitor_struct_size, wj_monitor_workspace_bytes)

@@ -726,7 +726,7 @@ extern "C" int wj_layernorm_fwd(const wj_ln_fwd_args* a, void* stream) {
 }
 
 #ifdef WJ_DROPOUT_LIB
-extern "C" WJ_DROPOUT_EXPORT int wj_layernorm_fwd_drop(const wj_ln_fwd_drop_args* ad, void* stream) {
+extern "C" WJ_EXPORT int wj_layernorm_fwd_drop(const wj_ln_fwd_drop_args* ad, void* stream) {
     WJ_CLEAR_STALE_ERROR();
     if (!ad) return WJ_ERR_ARG;
     const wj_ln_fwd_args* a = &ad->ln;
@@ -781,7 +781,7 @@ extern "C" int wj_layernorm_bwd(const wj_ln_bwd_args* a, void* stream) {
 }
 
 #ifdef WJ_DROPOUT_LIB
-extern "C" WJ_DROPOUT_EXPORT int wj_layernorm_bwd_drop(const wj_ln_bwd_drop_args* ad, void* stream) {
+extern "C" WJ_EXPORT int wj_layernorm_bwd_drop(const wj_ln_bwd_drop_args* ad, void* stream) {
     WJ_CLEAR_STALE_ERROR();
     if (!ad) return WJ_ERR_ARG;
     const wj_ln_bwd_args* a = &ad->ln;

@@ -14,13 +14,9 @@
 //   * a workgroup issues its first iteration's loads BEFORE it forms the table: formed in front of them the table cost 9 us of 634 at
 //     the full grid (8192 workgroups of ~13 iterations), formed under their latency the pass takes the parent's time
 //     (profiles/param_groups.txt: 628.4 us against 628.4 us at the full grid, 602.8 against 603.6 at 256 workgroups).
-#include <string.h>
-#include <type_traits>
 #include "stream_pieces.h"
 #include "../../include/wavjepa_hip_optim.h"
-#include "abi_table.h"
-
-#define WJ_OPTIM_EXPORT __attribute__((visibility("default")))
+#include "abi_queries.h"
 
 namespace {
 
@@ -69,7 +65,7 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(wj_adamw_groups_args 
 
 }  // namespace
 
-extern "C" WJ_OPTIM_EXPORT int wj_adamw_groups_step(const wj_adamw_groups_args* a, void* stream) {
+extern "C" WJ_EXPORT int wj_adamw_groups_step(const wj_adamw_groups_args* a, void* stream) {
     const CheckedEntry entry(__func__);
     if (!a || !a->p || !a->g || !a->m || !a->v || !a->group_map) return WJ_ERR_ARG;
     if (a->n <= 0 || (a->n & (WJ_ADAMW_GRANULE - 1)) || a->first < 0 || (a->first & (WJ_ADAMW_GRANULE - 1))) return WJ_ERR_ARG;
@@ -81,22 +77,4 @@ extern "C" WJ_OPTIM_EXPORT int wj_adamw_groups_step(const wj_adamw_groups_args* 
     return entry.launched();
 }
 
-// ---- the query entries ---------------------------------------------------------------------------------------------------------------
-#define WJ_ROW_CHECK(entry, ARGS, ...) \
-    static_assert(std::is_same_v<decltype(&entry), int (*)(const ARGS*, void*)>, #entry " does not take " #ARGS " in the header");
-WJ_OPTIM_ENTRIES(WJ_ROW_CHECK, WJ_ROW_CHECK)
-
-extern "C" WJ_OPTIM_EXPORT int wj_optim_struct_size(const char* name) {
-    if (!name) return -1;
-#define WJ_ROW_SZ(entry, ARGS, ...) if (!strcmp(name, #ARGS)) return (int)sizeof(ARGS);
-    WJ_OPTIM_ENTRIES(WJ_ROW_SZ, WJ_ROW_SZ)
-    return -1;
-}
-
-extern "C" WJ_OPTIM_EXPORT int64_t wj_optim_workspace_bytes(const char* fn, const void* args) {
-    if (!fn || !args) return -1;
-#define WJ_ROW_NONE(entry, ARGS) if (!strcmp(fn, #entry)) return 0;
-#define WJ_ROW_RULE(entry, ARGS, rule) if (!strcmp(fn, #entry)) return rule((const ARGS*)args);
-    WJ_OPTIM_ENTRIES(WJ_ROW_NONE, WJ_ROW_RULE)
-    return -1;
-}
+WJ_ABI_QUERIES(WJ_OPTIM_ENTRIES, WJ_OPTIM_OTHER_STRUCTS, wj_optim_struct_size, wj_optim_workspace_bytes)

@@ -4,7 +4,7 @@ from __future__ import annotations
 
 from typing import Optional
 
-from ._abi import DROPOUT_STRUCTS, STRUCTS
+from ._abi import LIBRARIES, STRUCTS
 
 Ptr = object
 
@@ -25,8 +25,8 @@ DROP_STACK = dict(enc=0, dec=1)
 
 def drop_args(seed: int, call: int, p: float, *, site: int, layer: int = 0, stack: int = 0):
     """The shared tail wj_dropout_args of the _drop entries: stream_id = site | layer << 8 | stack << 16."""
-    return DROPOUT_STRUCTS["wj_dropout_args"](seed=int(seed) & 0xFFFFFFFFFFFFFFFF, call=int(call) & 0xFFFFFFFF,
-                                      stream_id=(site | layer << 8 | stack << 16) & 0xFFFFFFFF, p=float(p))
+    return LIBRARIES["dropout"].struct_types["wj_dropout_args"](seed=int(seed) & 0xFFFFFFFFFFFFFFFF, call=int(call) & 0xFFFFFFFF,
+                                                                   stream_id=(site | layer << 8 | stack << 16) & 0xFFFFFFFF, p=float(p))
 
 
 def dropout_rows(x: Ptr, x2: Ptr = None, *, M: int, N: int, drop, ldx: Optional[int] = None, stream: Optional[int] = None) -> None:

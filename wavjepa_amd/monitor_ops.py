@@ -4,13 +4,14 @@ from __future__ import annotations
 
 from typing import Optional
 
-from ._abi import MONITOR_DEFINES
+from ._abi import LIBRARIES
 
 Ptr = object
 
-MOMENTS_ROWS = MONITOR_DEFINES["WJ_MOMENTS_ROWS"]             # rows per workgroup (one partial record each) of pass 1
-MOMENTS_COLS = MONITOR_DEFINES["WJ_MOMENTS_COLS"]             # columns per workgroup
-MOMENTS_MAX_GROUPS = MONITOR_DEFINES["WJ_MOMENTS_MAX_GROUPS"]
+_DEFINES = LIBRARIES["monitor"].defines
+MOMENTS_ROWS = _DEFINES["WJ_MOMENTS_ROWS"]             # rows per workgroup (one partial record each) of pass 1
+MOMENTS_COLS = _DEFINES["WJ_MOMENTS_COLS"]             # columns per workgroup
+MOMENTS_MAX_GROUPS = _DEFINES["WJ_MOMENTS_MAX_GROUPS"]
 MOMENTS_EPS = 1e-6
 
 

@@ -85,11 +85,7 @@ class TimingEvent:
 
 
 # the argument struct class of every stream entry, from the headers' prototypes
-_ENTRY_STRUCT = {fn: {**STRUCTS, **_abi.LAB_STRUCTS}[name] for fn, name in _abi.ENTRY_ARGS.items()}
-_ENTRY_STRUCT.update({fn: _abi.DROPOUT_STRUCTS[name] for fn, name in _abi.DROPOUT_ENTRY_ARGS.items()})    # libwavjepa_hip_dropout.so
-_ENTRY_STRUCT.update({fn: _abi.MONITOR_STRUCTS[name] for fn, name in _abi.MONITOR_ENTRY_ARGS.items()})    # libwavjepa_hip_monitor.so
-_ENTRY_STRUCT.update({fn: _abi.ACT_STRUCTS[name] for fn, name in _abi.ACT_ENTRY_ARGS.items()})            # libwavjepa_hip_act.so
-_ENTRY_STRUCT.update({fn: _abi.OPTIM_STRUCTS[name] for fn, name in _abi.OPTIM_ENTRY_ARGS.items()})        # libwavjepa_hip_optim.so
+_ENTRY_STRUCT = {fn: library.struct_types[name] for library in _abi.LIBRARIES.values() for fn, name in library.entry_args.items()}
 
 
 def _call(fn: str, a, stream: Optional[int], fields) -> None:

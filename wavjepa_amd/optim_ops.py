@@ -5,12 +5,13 @@ from __future__ import annotations
 import ctypes
 from typing import Optional, Sequence
 
-from ._abi import OPTIM_DEFINES
+from ._abi import LIBRARIES
 
 Ptr = object
 
-ADAMW_MAX_GROUPS = OPTIM_DEFINES["WJ_ADAMW_MAX_GROUPS"]       # groups of one launch
-ADAMW_GRANULE = OPTIM_DEFINES["WJ_ADAMW_GRANULE"]             # elements per byte of the group map (params.ALIGN)
+_DEFINES = LIBRARIES["optim"].defines
+ADAMW_MAX_GROUPS = _DEFINES["WJ_ADAMW_MAX_GROUPS"]       # groups of one launch
+ADAMW_GRANULE = _DEFINES["WJ_ADAMW_GRANULE"]             # elements per byte of the group map (params.ALIGN)
 
 
 def adamw_groups_step(p: Ptr, g: Ptr, m: Ptr, v: Ptr, n: int, *, lr: Sequence[float], weight_decay: Sequence[float], group_map: Ptr,
