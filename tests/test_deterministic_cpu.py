@@ -138,7 +138,7 @@ def test_deterministic_forms_reject_a_missing_or_short_workspace_without_a_gpu()
 
 
 def test_switch_is_read_by_the_engine_and_documented():
-    src = open(os.path.join(ROOT, "wavjepa_amd", "engine.py")).read()
+    src = open(os.path.join(ROOT, "wavjepa_amd", "encoder_engine.py")).read()       # (the base of both step engines reads the switches)
     assert 'environ.get("WJ_DETERMINISTIC", "0")' in src
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     row = [ln for ln in doc.splitlines() if ln.startswith("|") and "`WJ_DETERMINISTIC`" in ln]

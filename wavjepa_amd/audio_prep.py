@@ -29,6 +29,7 @@ import torch
 
 from . import ops
 from .resample import KAISER_BEST, sinc_resample_kernel
+from .upload import _upload_stream
 
 MAX_PHASES, MAX_TAPS = 1024, 4096         # limits of wj_audio_prepare (include/wavjepa_hip.h)
 PCM, PREPARED, FLOAT_RAW = 0, 1, 2        # states of a clip in RawAudioBatch.prepared
@@ -173,7 +174,6 @@ class DevicePrep:
     # ---------------------------------------------------------------------------------------------------------------- API
     def prepare_async(self, raw: RawAudioBatch, normalize: bool = True) -> _Pending:
         dev = self._device()
-        from .engine import _upload_stream
         side = _upload_stream(dev)
         B = len(raw)
         state, rates = raw.prepared.numpy(), raw.rates.numpy()
@@ -300,7 +300,6 @@ class DenoiserDevicePrep:
             raise ValueError(f"the batch was drawn for rows of {raw.out_len} samples, this object prepares {self.out_len}")
         pending = self.clean.prepare_async(raw.clean)         # (raises without a GPU); the side stream now waits for the step two batches ago
         dev = self.clean.device
-        from .engine import _upload_stream
         side = _upload_stream(dev)
         B = len(raw)
         audio = pending._batch[0][:, 0]

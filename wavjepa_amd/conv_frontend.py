@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .upload import pack_upload
 
 
 def _empty(*shape, dtype, device):
@@ -109,12 +110,11 @@ class ConvLayerParams:
 
 class ConvFrontend:
     def __init__(self, spec, in_channels: int, n_samples: int, streams: int, params: Sequence[Sequence[ConvLayerParams]], ln: bool, device,
-                 backward: bool = True, upload=None):
+                 backward: bool = True):
         """params[stack][layer]: one stack (every stream shares it) or one per stream; in_channels: per stream.  ln: mode "layer_norm".
-        backward=False keeps no dgrad layouts and no weight-gradient scratch (a forward-only front-end).  upload: arrays -> device
-        tensors in one copy (the row lists of the sparse backward)."""
+        backward=False keeps no dgrad layouts and no weight-gradient scratch (a forward-only front-end)."""
         self.spec, self.C_in, self.n_samples, self.S = [tuple(x) for x in spec], in_channels, n_samples, streams
-        self.params, self.ln, self.dev, self.upload = params, ln, device, upload
+        self.params, self.ln, self.dev = params, ln, device
         assert len(params) in (1, streams)
         self.C = self.spec[-1][0]
         self.L, self.P = conv_geometry(n_samples, self.spec)
@@ -380,7 +380,7 @@ class ConvFrontend:
             per0_host.append((rows, off))
             host += [np.concatenate([rows, pad]).astype(np.int32), np.concatenate([off, pad]).astype(np.int32)]
             keys += [("rows0", ch), ("off0", ch)]
-        dev = dict(zip(keys, self.upload(host, self.dev)))
+        dev = dict(zip(keys, pack_upload(host, self.dev)))
 
         out = {}
         for l, (act, ext) in lists.items():

@@ -19,7 +19,7 @@ import torch
 from torch import nn
 
 from . import ops, scene
-from .engine import EngineConfig, JepaEngine, _layer_ptrs
+from .encoder_engine import EncoderEngine, EngineConfig
 from .extractors.audio_extractor import Extractor
 from .jepa import HAS_LIGHTNING, FusedAdamW, TransformerStack, _AttrDict, _ModuleBase, _NullTrainer, collate_fn, cosine_schedule_with_warmup
 from .params import FlatParams
@@ -30,14 +30,15 @@ from .types import ForwardReturn, TransformerEncoderCFG, TransformerLayerCFG
 ORIGINAL_SR = 32000
 
 
-class DenoiserEngine(JepaEngine):
-    """Dense student encoder over 2N clips (N clean, then N generated) against given targets; reuses the JEPA engine's front-end,
-    layer forward / backward and front-end backward, without masks, predictor or EMA teacher."""
+class DenoiserEngine(EncoderEngine):
+    """Dense student encoder over 2N clips (N clean, then N generated) against given targets: the encoder base's front-end and
+    stack, forward and backward, and the two-group MSE."""
 
-    def _bind_params(self) -> None:
-        f, c = self.flat, self.cfg
-        self.enc_layers = [_layer_ptrs(f, f"encoder.layers.{i}.", False) for i in range(c.l_enc)]
-        self.dec_layers, self.tea_layers = [], []
+    def __init__(self, cfg: EngineConfig, flat: FlatParams, pos_enc: torch.Tensor):
+        super().__init__(cfg, flat, pos_enc)
+        self.dn_loss = torch.zeros(3, dtype=torch.float32, device=self.dev)      # (loss, loss_clean, loss_generated)
+        self.dn_w = torch.zeros(2, dtype=torch.float32, device=self.dev)
+        self.dn_ws = torch.empty(ops.workspace_bytes("wj_mse_groups", G=2, n=1) // 4, dtype=torch.float32, device=self.dev)
 
     def forward_pair(self, audio: torch.Tensor, targets: torch.Tensor, alpha: float) -> None:
         """audio bf16 [2N, C, L] (clean clips first), targets fp32 [N, T, d_enc] -> self.dn_loss = (loss, loss_clean, loss_generated)."""
@@ -45,14 +46,10 @@ class DenoiserEngine(JepaEngine):
         N2 = audio.shape[0]
         if N2 % 2 or targets.numel() != (N2 // 2) * self.T * c.d_enc:
             raise ValueError("denoiser step: 2N clips (N clean + N generated) and N x T x d_enc targets expected")
-        self.alloc(N2, train=True, G=1)
-        if not hasattr(self, "dn_loss") or self.dn_w.device != self.dev:
-            self.dn_loss = torch.zeros(3, dtype=torch.float32, device=self.dev)
-            self.dn_w = torch.zeros(2, dtype=torch.float32, device=self.dev)
-            self.dn_ws = torch.empty(ops.workspace_bytes("wj_mse_groups", G=2, n=1) // 4, dtype=torch.float32, device=self.dev)
+        self.alloc(N2, train=True)
         self.dn_w.copy_(torch.tensor([alpha, 1.0 - alpha], dtype=torch.float32))
-        self.audio, self.plan, self.ragged_step = audio, None, False
-        self.set_wt_need(self.M, 0)
+        self.audio = audio
+        self.set_wt_need(self.M)
         self.dn_targets = targets.reshape(-1, c.d_enc).float().contiguous()
         self._frontend(audio)
         self._stack_fwd("enc", self.lf, self.lf_b, self.M, N2, None, acts=self.enc_acts, y_f32=self.enc_out, mean=self.enc_fm, rstd=self.enc_fr)
@@ -60,18 +57,11 @@ class DenoiserEngine(JepaEngine):
         ops.mse_groups(self.enc_out, self.dn_targets, self.dn_w, self.dn_loss, self.dn_ws, n=self.dn_n, G=2)
 
     def backward_pair(self, gscale_ptr: int = 0) -> None:
-        self.flat.g32.zero_()
-        if self.deterministic:
-            self._det_ws()
-        self.refresh_wt()
-        bw = self.bw["enc"]
-        ops.mse_groups(self.enc_out, self.dn_targets, self.dn_w, self.dn_loss, self.dn_ws, n=self.dn_n, G=2, dpreds=bw["dx1"],
+        self._backward_open(clear=True)
+        ops.mse_groups(self.enc_out, self.dn_targets, self.dn_w, self.dn_loss, self.dn_ws, n=self.dn_n, G=2, dpreds=self.bw["enc"]["dx1"],
                        gscale=gscale_ptr if gscale_ptr else None)
-        dy = self._stack_bwd("enc", self.lf, self.lf_b, self.M, self.N, None)
-        self._frontend_bwd(dy, False, None)
-        self._flush_folds()
-        self._join_side()
-        bw["used"] = [False] * bw["nbuf"]
+        self._frontend_bwd(self._stack_bwd("enc", self.lf, self.lf_b, self.M, self.N, None))
+        self._backward_close()
 
 
 class _DenoiserLoss(torch.autograd.Function):
@@ -217,9 +207,8 @@ class Denoiser(_ModuleBase):
         self._flat = FlatParams(self, self.device)
         cfg = EngineConfig(conv_spec=ext.conv_layers_spec, in_channels=ext.in_channels, streams=1, conv_prefixes=["extract_audio.cnn."],
                            n_samples=self.target_length, d_enc=self.encoder_embedding_dim, h_enc=self.n_encoder_heads,
-                           l_enc=self.encoder.num_layers, d_dec=64, h_dec=1, l_dec=0, top_k=1, ln_eps=self.encoder.layer_norm_eps)
-        self._engine = DenoiserEngine(cfg, self._flat, self.pos_encoding_encoder.data,
-                                      torch.zeros(self.total_patches, 64, device=self.device))
+                           l_enc=self.encoder.num_layers, ln_eps=self.encoder.layer_norm_eps)
+        self._engine = DenoiserEngine(cfg, self._flat, self.pos_encoding_encoder.data)
         self._anchor = torch.zeros(1, device=self.device, requires_grad=True)
         self._student_bf16_fresh = False
         return self._engine

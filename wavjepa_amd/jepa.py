@@ -18,12 +18,14 @@ import torch
 from torch import nn
 
 from . import ops
-from .engine import EngineConfig, JepaEngine, MaskPlan, make_mask_plan, pack_upload
+from .engine import EngineConfig, JepaEngine
 from .extractors.audio_extractor import Extractor
 from .functions import trunc_normal_
+from .mask_plan import MaskPlan, make_mask_plan
 from .params import FlatParams
 from .pos_embed import get_1d_sincos_pos_embed_from_grid
 from .types import ForwardReturn, TransformerEncoderCFG, TransformerLayerCFG, activation_kind_of
+from .upload import pack_upload
 
 
 def collate_fn(batch: torch.Tensor) -> torch.Tensor:
@@ -246,7 +248,7 @@ class FusedAdamW(torch.optim.Optimizer):
             return None
         # JEPA.accumulate_grads: backward adds into the flat buffer, so this call is the clear (the views stay attached whatever
         # set_to_none says: the buffer IS the gradients).  Nothing to do behind an update that cleared it itself (fuse_zero_grad).
-        if not getattr(m._flat, "g_clean", False):
+        if not m._flat.g_clean:
             m._engine.wait_optimizer()       # an update overlapped on the side stream may still read the buffer
             m._flat.g32.zero_()
             m._flat.g_clean = True

@@ -76,6 +76,7 @@ class FlatParams:
                 assert "teacher_" + s.name == t.name and s.offset - self.enc_offset == t.offset and s.numel == t.numel
         self.enc_numel = self.tn
         self.bf16_fresh = False
+        self.g_clean = False           # the last optimiser update left g32 clear (FusedAdamW.fuse_zero_grad)
 
     # -- pointers -----------------------------------------------------------------------------------------------
     def front_and_rest_ranges(self):
