@@ -88,7 +88,7 @@ class ComponentFactory:
             if a not in acts:
                 raise ValueError(f"Unknown {key}: {a}. Available activations: {list(acts)}")
         try:
-            return cls(**optimizer_group_settings(cfg), feature_extractor=extractor, transformer_encoder_cfg=TransformerEncoderCFG.create(),
+            return cls(**optimizer_group_settings(cfg), **layerdrop_settings(cfg), feature_extractor=extractor, transformer_encoder_cfg=TransformerEncoderCFG.create(),
                        transformer_encoder_layers_cfg=TransformerLayerCFG.create(norm_first=norm_first, dropout=drop_enc, activation=acts[act]()),
                        transformer_decoder_cfg=TransformerEncoderCFG.create(),
                        transformer_decoder_layers_cfg=TransformerLayerCFG.create(d_model=384, norm_first=norm_first_dec, dropout=drop_dec,
@@ -116,6 +116,17 @@ def optimizer_group_settings(cfg) -> dict:
         kw["weight_decay_exclude"] = exclude if isinstance(exclude, str) else tuple(str(x) for x in exclude)
     if decay != 1.0:
         kw["layer_lr_decay"] = decay
+    return kw
+
+
+def layerdrop_settings(cfg) -> dict:
+    """The model keywords of LayerDrop, only those that are set: trainer.encoder_layerdrop / trainer.decoder_layerdrop, the probability
+    with which a training step skips each layer of the student / the predictor (default 0: every layer runs)."""
+    kw = {}
+    for key in ("encoder_layerdrop", "decoder_layerdrop"):
+        p = float(cfg.trainer.get(key, 0.0))
+        if p != 0.0:
+            kw[key] = p
     return kw
 
 

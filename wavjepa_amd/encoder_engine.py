@@ -49,6 +49,8 @@ class EngineConfig:
     dropout_dec: float = 0.0       # ... of the predictor's
     act_enc: str = "gelu"          # feed-forward activation of the student AND the teacher: "gelu" | "relu" | "gelu_tanh" | "silu" (ops.gemm_act)
     act_dec: str = "gelu"          # ... of the predictor
+    layerdrop_enc: float = 0.0     # LayerDrop rate of the student's layers (never the teacher's): the kept lists come with each forward (_kept_now)
+    layerdrop_dec: float = 0.0     # ... of the predictor's
 
 
 class _Layer:
@@ -137,7 +139,14 @@ class EncoderEngine:
             if p > 0 and layers > 0 and hd not in (32, 64):
                 raise NotImplementedError(f"{what}: dropout={p} with {hd}-wide heads: attention dropout runs in the streamed kernels "
                                           "(wj_attn_stream_fwd_drop / _bwd_drop), which take head widths 32 and 64")
+        for s in self.BW_RING:
+            if not (0.0 <= float(getattr(cfg, "layerdrop_" + s)) < 1.0):
+                raise ValueError(f"{self.MODULE[s]} layerdrop must lie in [0, 1), not {getattr(cfg, 'layerdrop_' + s)}")
         self.drop_seed, self.drop_call = 0, 0
+        # LayerDrop: stack -> the sorted indices of the layers that run in the training forward being run and in its backward (a stack
+        # that is not named runs every layer).  Everything positional in the walkers (_stack_fwd, _stack_bwd, _redo_layer) follows the
+        # position in this list, everything that names a layer its entry.
+        self._kept_now: Dict[str, List[int]] = {}
         self._drop_now: Dict[str, float] = {}          # stack -> rate, for the forward being run and its backward ({}: no dropout)
         # the arena (alloc): clips, sequences per stack, whether it holds the training buffers, rows of every stack's buffers
         self.N, self.seqs, self._train_alloc = 0, {}, False
@@ -314,6 +323,10 @@ class EncoderEngine:
         if self.fp8 and (self.cfg.dropout_enc > 0 or self.cfg.dropout_dec > 0):
             raise RuntimeError("fp8 mode (WJ_FP8=1 / engine.fp8) is not combined with dropout > 0: the fp8 producers (LayerNorm and GELU "
                                "epilogues that emit the next GEMM's operand) have no dropout forms")
+        if self.fp8 and (self.cfg.layerdrop_enc > 0 or self.cfg.layerdrop_dec > 0):
+            raise RuntimeError("fp8 mode (WJ_FP8=1 / engine.fp8) is not combined with layerdrop > 0 (encoder_layerdrop / decoder_layerdrop): "
+                               "a layer hands its output to the next one in the stack's fp8 scratch, and nothing pins that hand-over "
+                               "across a skipped layer")
         if self.fp8 and self.recompute:
             # the fp8 forward hands a layer's output to the next layer in the stack's fp8 scratch as well; a second forward that starts
             # from a kept bf16 output would quantise it in another launch order, and nothing pins that to the first pass's bits
@@ -1028,47 +1041,65 @@ class EncoderEngine:
         """Walk a stack's layers forward from the stream x (fp32; xb: its bf16 copy, which only post-norm layers read), then its final
         norm, which writes `out` (y_f32 / y_bf16 / mean / rstd).  mask, seq: as _layer_fwd; sub: the rows that go on behind the last
         layer's attention.  acts: where every layer saves for the backward; None (inference): nothing is saved, every layer runs in
-        self.scratch.  lean: the post-norm final norm may take its capped-grid form (WJ_LN_LEAN names the stack)."""
+        self.scratch.  lean: the post-norm final norm may take its capped-grid form (WJ_LN_LEAN names the stack).
+        LayerDrop: a saving walk runs the layers of _kept(stack) only; the stream passes the others unchanged."""
         c, f = self.cfg, self.flat
         layers, D, H, pre, norm = self._stack(stack)
-        save, top = acts is not None, len(layers) - 1
+        save = acts is not None
+        # LayerDrop: the layers that run, kept[0] < kept[1] < ...; layer kept[j] saves in acts[j] (inference runs every layer)
+        kept = self._kept(stack) if save else range(len(layers))
+        top = len(kept) - 1
         gamma, beta = f.ptr32(norm + ".weight"), f.ptr32(norm + ".bias")
         Mo = M if sub is None else sub[2]                      # rows that leave the stack
+        if top < 0 and sub is not None:                        # no layer runs: the final norm reads the sub-rows of the stack's input
+            ops.mask_gather_rows(x, sub[0], self.tail_x, n_rows=Mo, D=D, elem_bytes=4)
+            x = self.tail_x
         if pre:
             r = None
-            for i, w in enumerate(layers):
-                x, r = self._layer_fwd_pre(w, acts[i] if save else self.scratch, x, r, M, D, H, B, mask, seq, save=save,
-                                           sub=sub if i == top else None, stack=stack)
-            # the final norm also performs the last residual add; the stream it normalises is kept for its backward
-            ops.layernorm_pre_fwd(x, gamma, beta, M=Mo, D=D, eps=c.norm_eps, r=r, s_f32=getattr(self, stack + "_sf") if save else None, **out)
+            for j, i in enumerate(kept):
+                x, r = self._layer_fwd_pre(layers[i], acts[j] if save else self.scratch, x, r, M, D, H, B, mask, seq, save=save,
+                                           sub=sub if j == top else None, stack=stack)
+            # the final norm also performs the last residual add; the stream it normalises is kept for its backward (with no layer
+            # there is no add, and the stream is the stack's input itself)
+            ops.layernorm_pre_fwd(x, gamma, beta, M=Mo, D=D, eps=c.norm_eps, r=r,
+                                  s_f32=getattr(self, stack + "_sf") if save and top >= 0 else None, **out)
             return
         xq = False
-        for i, w in enumerate(layers):
-            a = acts[i] if save else self.scratch
-            xq = self._layer_fwd(w, a, x, xb, M, D, H, B, mask, seq, save=save, sub=sub if i == top else None, stack=stack, xq_ready=xq,
-                                 li=i)
+        for j, i in enumerate(kept):
+            a = acts[j] if save else self.scratch
+            xq = self._layer_fwd(layers[i], a, x, xb, M, D, H, B, mask, seq, save=save, sub=sub if j == top else None, stack=stack,
+                                 xq_ready=xq, li=i)
             x, xb = a.x2, a.x2b
         ops.layernorm_fwd(x, gamma, beta, M=Mo, D=D, eps=c.norm_eps,
                           workgroups=self.ln_lean_wgs if (lean and self._lean_now and stack in self.ln_lean) else 0, **out)
 
-    def _redo_layer(self, stack: str, i: int, x0: torch.Tensor, xb0: torch.Tensor, M: int, B: int, mask: Optional[torch.Tensor],
+    def _kept(self, stack: str) -> Sequence[int]:
+        """The layers of the stack that run in the training forward being run and its backward (LayerDrop), ascending: every layer
+        unless the forward was handed a kept list."""
+        kept = self._kept_now.get(stack)
+        return range(len(self._stack(stack)[0])) if kept is None else kept
+
+    def _redo_layer(self, stack: str, j: int, x0: torch.Tensor, xb0: torch.Tensor, M: int, B: int, mask: Optional[torch.Tensor],
                     seq: Optional[Tuple[torch.Tensor, int]], sub: Optional[Tuple[torch.Tensor, torch.Tensor, int]]) -> None:
-        """Recompute mode: layer i's forward once more, from the kept output of layer i - 1 (or the stack's input) into ring slot
-        i % nbuf, with the masks, offsets and sub-rows of the first pass.  The slot's last readers are the grouped weight gradients of
-        layer i + nbuf on the side stream: the main stream waits for the event that guards the slot before it writes -- once per
-        layer: the layer's backward, which waits for the same event with the flag off, does not wait again."""
+        """Recompute mode: the forward of the j-th layer that ran (layer _kept(stack)[j]; without LayerDrop layer j) once more, from the
+        kept output of the one that ran before it (or the stack's input) into ring slot j % nbuf, with the masks, offsets and sub-rows
+        of the first pass.  The slot's last readers are the grouped weight gradients of position j + nbuf on the side stream: the main
+        stream waits for the event that guards the slot before it writes -- once per layer: the layer's backward, which waits for the
+        same event with the flag off, does not wait again."""
         bw, acts = self.bw[stack], self._acts(stack)
         layers, D, H, pre, _ = self._stack(stack)
-        if not (pre and i < len(layers) - 1):      # (pre-norm: the backward of layer i + 1 waited for this slot to write its dsb2)
-            self._slot_wait(bw, i % bw["nbuf"])
+        kept = self._kept(stack)
+        i = kept[j]
+        if not (pre and j < len(kept) - 1):        # (pre-norm: the backward of the layer above waited for this slot to write its dsb2)
+            self._slot_wait(bw, j % bw["nbuf"])
         lean_was, self._lean_now = self._lean_now, self.use_side      # (WJ_LN_LEAN: the LayerNorm form of the first pass)
         try:
             if pre:
-                x, r = (x0, None) if i == 0 else (acts[i - 1].x2, acts[i - 1].f)
-                self._layer_fwd_pre(layers[i], acts[i], x, r, M, D, H, B, mask, seq, save=True, sub=sub, stack=stack, redo=True)
+                x, r = (x0, None) if j == 0 else (acts[j - 1].x2, acts[j - 1].f)
+                self._layer_fwd_pre(layers[i], acts[j], x, r, M, D, H, B, mask, seq, save=True, sub=sub, stack=stack, redo=True)
             else:
-                x, xb = (x0, xb0) if i == 0 else (acts[i - 1].x2, acts[i - 1].x2b)
-                self._layer_fwd(layers[i], acts[i], x, xb, M, D, H, B, mask, seq, save=True, sub=sub, stack=stack, redo=True, li=i)
+                x, xb = (x0, xb0) if j == 0 else (acts[j - 1].x2, acts[j - 1].x2b)
+                self._layer_fwd(layers[i], acts[j], x, xb, M, D, H, B, mask, seq, save=True, sub=sub, stack=stack, redo=True, li=i)
         finally:
             self._lean_now = lean_was
 
@@ -1078,34 +1109,50 @@ class EncoderEngine:
         """Backward of _stack_fwd: bw["dx1"] holds the fp32 gradient of the final norm's output (nothing bypasses that norm); returns
         the fp32 gradient of the stack's input (x0, xb0).  The weight gradients of bw["group"] consecutive layers share a grouped
         launch; `flushed(i)` is called behind layer i when its launch has been queued.  Recompute mode: every layer's forward is issued
-        again in front of its backward (_redo_layer)."""
+        again in front of its backward (_redo_layer).  LayerDrop: only the layers of _kept(stack) are walked (those the forward ran)."""
         f, bw = self.flat, self.bw[stack]
         layers, D, H, pre, norm = self._stack(stack)
         acts = self._acts(stack)
         fm, fr = getattr(self, stack + "_fm"), getattr(self, stack + "_fr")
-        top, nbuf, group = len(layers) - 1, bw["nbuf"], bw["group"]
+        # LayerDrop: the walk goes over the layers that ran.  Buffers, ring slots, the weight-gradient grouping, "the layer below" and
+        # the bottom follow the position j in `kept`; parameters, dropout masks and the `flushed` report follow the index kept[j].
+        kept = self._kept(stack)
+        top, nbuf, group = len(kept) - 1, bw["nbuf"], bw["group"]
         Mo = M if sub is None else sub[2]                      # rows that left the stack
         grads = dict(dgamma=f.gptr(norm + ".weight"), dbeta=f.gptr(norm + ".bias"))
+        if top < 0:
+            # no layer ran: the final norm read the stack's input (its sub-rows), and its backward's output is the input's gradient
+            x_in = x0 if sub is None else self.tail_x
+            if pre:
+                self._ln_pre_bwd(bw["dx1"], x_in, f.ptr32(norm + ".weight"), fm, fr, M=Mo, D=D, ds_f32=bw["dy"], **grads)
+            else:
+                self._ln_bwd(bw["dx1"], x_in, f.ptr32(norm + ".weight"), fm, fr, M=Mo, D=D, ds_f32=bw["dy"], defer=False,
+                             workspace=self.red_ws, **grads)
+            if sub is None:
+                return bw["dy"]
+            ops.unmask_rows_f32(bw["dy"], sub[1], bw["ds"], M=M, D=D, src_is_f32=True)      # back to all rows: zero where nothing went on
+            return bw["ds"]
         if pre:
             # d(stream) for the top layer -- fp32 in bw["ds"], bf16 in its slot -- and that layer's linear2.bias gradient
             self._ln_pre_bwd(bw["dx1"], getattr(self, stack + "_sf"), f.ptr32(norm + ".weight"), fm, fr, M=Mo, D=D, ds_f32=bw["ds"],
-                             ds_bf16=bw["dsb2"][top % nbuf], dbias=layers[top].gb2, **grads)
+                             ds_bf16=bw["dsb2"][top % nbuf], dbias=layers[kept[top]].gb2, **grads)
         else:
             self._ln_bwd(bw["dx1"], acts[top].x2, f.ptr32(norm + ".weight"), fm, fr, M=Mo, D=D, ds_f32=bw["dy"], defer=False,
                          workspace=self.red_ws, **grads)
         dy, dyb = bw["dy"], None
-        for i in range(top, -1, -1):
-            w, a, sub_i = layers[i], acts[i], sub if i == top else None
-            flush = (top - i) % group == group - 1 or i == 0
+        for j in range(top, -1, -1):
+            i = kept[j]
+            w, a, sub_j = layers[i], acts[j], sub if j == top else None
+            flush = (top - j) % group == group - 1 or j == 0
             if self.recompute:
-                self._redo_layer(stack, i, x0, xb0, M, B, mask, seq, sub_i)
+                self._redo_layer(stack, j, x0, xb0, M, B, mask, seq, sub_j)
             if pre:
-                dy, done = self._layer_bwd_pre(w, a, x0 if i == 0 else a.x1, layers[i - 1] if i > 0 else None, bw["dy"], M, D, H, B, mask,
-                                               bw, i % nbuf, seq, sub=sub_i, flush=flush)
+                dy, done = self._layer_bwd_pre(w, a, x0 if j == 0 else a.x1, layers[kept[j - 1]] if j > 0 else None, bw["dy"], M, D, H, B,
+                                               mask, bw, j % nbuf, seq, sub=sub_j, flush=flush)
             else:
-                x_in, xb_in = (x0, xb0) if i == 0 else (acts[i - 1].x2, acts[i - 1].x2b)
-                dy, dyb, done = self._layer_bwd(w, a, x_in, xb_in, dy, dyb, bw["dy"], M, D, H, B, mask, bw, i % nbuf, seq, sub=sub_i,
-                                                flush=flush, bottom=i == 0, stack=stack, li=i)
+                x_in, xb_in = (x0, xb0) if j == 0 else (acts[j - 1].x2, acts[j - 1].x2b)
+                dy, dyb, done = self._layer_bwd(w, a, x_in, xb_in, dy, dyb, bw["dy"], M, D, H, B, mask, bw, j % nbuf, seq, sub=sub_j,
+                                                flush=flush, bottom=j == 0, stack=stack, li=i)
             if done and flushed is not None:
                 flushed(i)
         return dy

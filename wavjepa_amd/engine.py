@@ -13,7 +13,7 @@ teacher and its targets, the masked loss and the collapse monitor.
 from __future__ import annotations
 
 import os
-from typing import Optional
+from typing import Dict, Optional, Sequence
 
 import torch
 
@@ -100,11 +100,16 @@ class JepaEngine(EncoderEngine):
         self.d_ctx_in = _empty(Me, c.d_enc, dtype=bf, device=dev)
 
     # ------------------------------------------------------------------------------------------------ forward
-    def forward(self, audio: torch.Tensor, plan: MaskPlan, train: bool = True, drop_call: Optional[int] = None, monitor: bool = False) -> None:
+    def forward(self, audio: torch.Tensor, plan: MaskPlan, train: bool = True, drop_call: Optional[int] = None, monitor: bool = False,
+                kept: Optional[Dict[str, Sequence[int]]] = None) -> None:
         """Training forward.  Results: self.loss[0], self.preds, self.targets, self.cf[:n_ctx], self.lf.
         train (module.training): with it, a stack whose EngineConfig rate is > 0 runs under dropout, its masks drawn from
         (self.drop_seed, drop_call); the backward of this forward uses the same.  Without it, or with both rates 0, the launches are
         exactly those of an engine without dropout.
+        kept (LayerDrop, with `train` only): stack -> the sorted distinct indices of its layers that run in this forward and its
+        backward; every other layer of the stack issues no launch, the stream passes it unchanged and its gradients stay the zeros of
+        the cleared gradient buffer.  A stack that is not named runs every layer; the teacher always does.  An empty list is legal:
+        the stack is then its final norm over its input.
         monitor: one wj_masked_moments right behind the loss, over the rows the loss uses; self.moments = (pred_var, target_var, n, 0)
         and self.moments_col (per-column mean and M2, what a data-parallel run merges).  Without it no launch, allocation or pointer
         of the step differs: the monitor's buffers are made by the first forward that asks for it."""
@@ -116,6 +121,16 @@ class JepaEngine(EncoderEngine):
             self._drop_now = {k: float(p) for k, p in (("enc", self.cfg.dropout_enc), ("dec", self.cfg.dropout_dec)) if p > 0}
             if drop_call is not None:
                 self.drop_call = int(drop_call)
+        self._kept_now = {}
+        if train and kept:
+            if self.fp8:
+                self._check_fp8()        # (names the rates; an explicit kept list on an engine whose rates are 0 is refused below)
+                raise RuntimeError("fp8 mode (WJ_FP8=1 / engine.fp8) is not combined with layerdrop (a kept list was handed to the forward)")
+            for s, idx in kept.items():
+                n, idx = len(self._stack(s)[0]), [int(i) for i in idx]
+                if any(i < 0 or i >= n for i in idx) or any(b <= a for a, b in zip(idx, idx[1:])):
+                    raise ValueError(f"kept[{s!r}] = {idx}: sorted distinct indices of the stack's {n} layers")
+                self._kept_now[s] = idx
         if plan.N != N or plan.T != self.T or plan.G < 1:
             raise ValueError(f"mask plan is for {plan.N} clips x {plan.G} groups x {plan.T} tokens; the batch has {N} clips of {self.T} tokens")
         rag = self.ragged and plan.ragged_ok
@@ -350,16 +365,21 @@ class JepaEngine(EncoderEngine):
         else:
             ops.unmask_rows_f32(self.d_ctx_in, plan.inv, bw["dx1"], M=M, D=De)
         enc_ready = set()
+        every = "enc" not in self._kept_now              # no LayerDrop in this step: every layer ran
 
         def flushed(i):
             # the weight gradients of two layers share a grouped launch: a layer's section of the gradient buffer is final (and its
-            # all-reduce bucket may go) once the launch that carries it has been queued
-            for j in range(min(c.l_enc - 1, i + bw["group"] - 1), i - 1, -1):
+            # all-reduce bucket may go) once the launch that carries it has been queued.  LayerDrop: the section of a layer that did
+            # not run is final from the start (the zeros of the cleared buffer, or what earlier micro-batches left); it is reported
+            # with the next layer below it that ran, so the listener still hears every index once, in descending order.
+            for j in range(min(c.l_enc - 1, i + bw["group"] - 1) if every else c.l_enc - 1, i - 1, -1):
                 if j not in enc_ready:
                     enc_ready.add(j)
                     ready(f"enc:{j}")
         first = (self.enc_in, self.enc_in_b) if rag else (self.lf, self.lf_b)
         dy = self._stack_bwd("enc", first[0], first[1], Me, N, plan.ctx_u8, eseq, flushed=flushed)
+        if not every and len(enc_ready) < c.l_enc:
+            flushed(0)                                   # layers below the lowest one that ran (or all of them: none ran)
         self._frontend_bwd(dy, rag, plan)
         self._backward_close()
         if on_grads_ready is not None:

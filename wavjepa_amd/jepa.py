@@ -11,7 +11,7 @@ from __future__ import annotations
 import copy
 import math
 import os
-from typing import Any, Dict, Optional, Tuple
+from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -21,6 +21,7 @@ from . import ops
 from .engine import EngineConfig, JepaEngine
 from .extractors.audio_extractor import Extractor
 from .functions import trunc_normal_
+from .layerdrop import check_keep, check_rate, kept_layers
 from .mask_plan import MaskPlan, make_mask_plan
 from .params import FlatParams
 from .pos_embed import get_1d_sincos_pos_embed_from_grid
@@ -390,6 +391,8 @@ class JEPA(_ModuleBase):
             self.hparams["adam_betas"] = tuple(adam_betas)
             self.hparams.pop("weight_decay_exclude", None)     # (recorded below, only when set)
             self.hparams.pop("layer_lr_decay", None)
+            self.hparams.pop("encoder_layerdrop", None)
+            self.hparams.pop("decoder_layerdrop", None)
         else:
             self.hparams = _AttrDict(lr=lr, adam_betas=tuple(adam_betas), adam_eps=adam_eps, adam_weight_decay=adam_weight_decay,
                                      ema_decay=ema_decay, ema_end_decay=ema_end_decay, ema_anneal_end_step=ema_anneal_end_step,
@@ -413,6 +416,23 @@ class JEPA(_ModuleBase):
             self.hparams["weight_decay_exclude"] = self.weight_decay_exclude
         if self.layer_lr_decay != 1.0:
             self.hparams["layer_lr_decay"] = self.layer_lr_decay
+        # LayerDrop (wavjepa_amd.layerdrop; fairseq's TransformerEncoder, no rescaling): in a training-mode forward every layer of the
+        # student / the predictor is skipped for the whole batch with this probability -- no launch, the stream passes unchanged, the
+        # layer's gradient is the zero of the cleared buffer (the fused AdamW sees that zero: INTEGRATION.md, differences by design).
+        # The teacher, eval mode and inference never drop.  Keywords through **kwargs as well (encoder_layerdrop=0.0,
+        # decoder_layerdrop=0.0), each recorded only when set.
+        self.encoder_layerdrop = check_rate(kwargs.pop("encoder_layerdrop", 0.0), "encoder_layerdrop")
+        self.decoder_layerdrop = check_rate(kwargs.pop("decoder_layerdrop", 0.0), "decoder_layerdrop")
+        if self.encoder_layerdrop > 0:
+            self.hparams["encoder_layerdrop"] = self.encoder_layerdrop
+        if self.decoder_layerdrop > 0:
+            self.hparams["decoder_layerdrop"] = self.decoder_layerdrop
+        # layerdrop_keep: None -- the kept layers are drawn per forward from (dropout_seed, the dropout call counter, stack, layer), the
+        # same on every data-parallel rank; {"enc": [...], "dec": [...]} fixes the kept set of the stacks it names (sorted distinct
+        # layer indices; an empty list is legal) for every training forward until it is reset.  last_kept: the kept lists of the last
+        # training forward that ran under LayerDrop (None before the first).
+        self._layerdrop_keep: Optional[Dict[str, List[int]]] = None
+        self.last_kept: Optional[Dict[str, List[int]]] = None
         self.extract_audio = feature_extractor
         self.feature_norms = nn.LayerNorm(self.extract_audio.embedding_dim)
         self.loss_fn = loss_fn
@@ -463,6 +483,8 @@ class JEPA(_ModuleBase):
         if self.encoder.dropout > 0 or self.decoder.dropout > 0:
             self.hparams["dropout_encoder"] = self.encoder.dropout
             self.hparams["dropout_decoder"] = self.decoder.dropout
+            self.hparams["dropout_seed"] = self._dropout_seed
+        elif self.encoder_layerdrop > 0 or self.decoder_layerdrop > 0:     # LayerDrop draws from the same seed and counter
             self.hparams["dropout_seed"] = self._dropout_seed
         # Collapse monitor (an attribute, no constructor argument: signature and hyper-parameters are what they were).  A training-mode
         # forward at a step with global_step % monitor_every == 0 returns pred_var / target_var (device scalars: the mean over
@@ -587,7 +609,8 @@ class JEPA(_ModuleBase):
                            conv_mode=getattr(ext, "mode", "default"), conv_bias=bool(getattr(ext, "conv_bias", False)),
                            loss_kind=self.loss_kind, loss_beta=self.loss_beta, recompute=self.use_gradient_checkpointing,
                            dropout_enc=self.encoder.dropout, dropout_dec=self.decoder.dropout,
-                           act_enc=self.encoder.activation, act_dec=self.decoder.activation)
+                           act_enc=self.encoder.activation, act_dec=self.decoder.activation,
+                           layerdrop_enc=self.encoder_layerdrop, layerdrop_dec=self.decoder_layerdrop)
         self._engine = JepaEngine(cfg, self._flat, self.pos_encoding_encoder.data, self.pos_encoding_decoder.data)
         self._anchor = torch.zeros(1, device=self.device, requires_grad=True)
         self._student_bf16_fresh = False
@@ -663,7 +686,10 @@ class JEPA(_ModuleBase):
                 self._micro = (0, 1)
         else:
             out = self(audio_input, ctx_masks, target_indices, ctx_and_target_masks)
-        self.log_dict({"train/loss": out["loss"], "ema": self._get_ema_decay()}, prog_bar=True, sync_dist=True)
+        logged = {"train/loss": out["loss"], "ema": self._get_ema_decay()}
+        if self.last_kept is not None and self._layerdrop_on():      # LayerDrop: how many layers of each stack ran in this forward
+            logged.update({"train/kept_encoder": len(self.last_kept["enc"]), "train/kept_decoder": len(self.last_kept["dec"])})
+        self.log_dict(logged, prog_bar=True, sync_dist=True)
         if "pred_var" in out:          # a monitored step (monitor_every)
             self.log_dict({"train/pred_var": out["pred_var"], "train/target_var": out["target_var"]}, prog_bar=False, sync_dist=True)
         self._step_teacher()           # EMA with the pre-update student, before backward (reference jepa.py:330-331)
@@ -686,10 +712,14 @@ class JEPA(_ModuleBase):
         # (a window of k micro-batches: the one that closes it is the monitored forward of its optimiser step)
         monitor = self.training and every > 0 and int(self.global_step) % every == 0 and i == k - 1
         drop_call = dropout_call_of(int(self.global_step), k, i, self.dropout_call)
+        kept = self._layerdrop_kept(drop_call) if self.training else None
+        extra = {} if kept is None else dict(kept=kept)        # (no LayerDrop: the call as it always was)
         if monitor:
-            eng.forward(audio, plan, train=self.training, drop_call=drop_call, monitor=True)
+            eng.forward(audio, plan, train=self.training, drop_call=drop_call, monitor=True, **extra)
         else:
-            eng.forward(audio, plan, train=self.training, drop_call=drop_call)
+            eng.forward(audio, plan, train=self.training, drop_call=drop_call, **extra)
+        if kept is not None:
+            self.last_kept = {s: list(kept.get(s, range(n))) for s, n in (("enc", self.encoder.num_layers), ("dec", self.decoder.num_layers))}
         N, T = audio.shape[0], eng.T
         if torch.is_grad_enabled():
             loss = _EngineLoss.apply(self._anchor, self)
@@ -711,6 +741,31 @@ class JEPA(_ModuleBase):
         self._dropout_seed = int(seed)
         if "dropout_seed" in self.hparams:
             self.hparams["dropout_seed"] = int(seed)
+
+    def _layerdrop_on(self) -> bool:
+        return self.encoder_layerdrop > 0 or self.decoder_layerdrop > 0 or bool(self._layerdrop_keep)
+
+    @property
+    def layerdrop_keep(self) -> Optional[Dict[str, List[int]]]:
+        return self._layerdrop_keep
+
+    @layerdrop_keep.setter
+    def layerdrop_keep(self, keep) -> None:
+        self._layerdrop_keep = check_keep(keep, dict(enc=self.encoder.num_layers, dec=self.decoder.num_layers))
+
+    def _layerdrop_kept(self, call: int) -> Optional[Dict[str, List[int]]]:
+        """stack -> the layers that run in the training forward with dropout call counter `call`: an explicit layerdrop_keep entry, else
+        the draw of a stack whose rate is set.  None when neither is set (the generator is not evaluated and the engine is called as
+        it always was).  The generator's key is dropout_seed itself, without the rank: all ranks skip the same layers."""
+        fixed = self._layerdrop_keep or {}
+        rates = dict(enc=(self.encoder_layerdrop, self.encoder.num_layers), dec=(self.decoder_layerdrop, self.decoder.num_layers))
+        out = {}
+        for s, (p, n) in rates.items():
+            if s in fixed:
+                out[s] = list(fixed[s])
+            elif p > 0:
+                out[s] = kept_layers(self.dropout_seed, call, s, n, p)
+        return out or None
 
     def _dropout_key(self) -> int:
         """The generator's 64-bit key: dropout_seed with the data-parallel rank mixed in (every rank draws its own masks)."""

@@ -310,6 +310,9 @@ class Trainer:
             dt = time.time() - t0
             ema = f"  ema {model._get_ema_decay():.6f}" if hasattr(model, "_get_ema_decay") else ""
             var = f"  pred_var {mon[1]:.5f}  target_var {mon[2]:.5f} (step {mon[0]})" if mon is not None else ""
+            kept = getattr(model, "last_kept", None)          # LayerDrop: layers of the student / the predictor that ran in the last forward
+            if kept is not None:
+                var += f"  kept {len(kept['enc'])}/{len(kept['dec'])}"
             print(f"step {gs}  loss {loss:.5f}  lr {runner.scheduler.get_last_lr()[0]:.3e}{ema}{var}  "
                   f"{dt / self.log_every_n_steps * 1000:.1f} ms/step", flush=True)
             t0 = time.time()
