@@ -17,7 +17,9 @@
 // FFT: 8192 = 16 x 16 x 32, three passes of register FFTs (radix 16 / 16 / 32 per thread, compile-time twiddles) with two trips
 // through LDS (unit-stride or padded rows: no bank conflicts), inter-pass twiddles from one sincospif per thread and pass (the
 // argument 2n/N is exact in fp32) and powers by squaring.  512 threads, 68 KB of LDS, two workgroups per CU.
-// Results agree with an fp64 convolution to ~1e-6 of the output RMS (tests/test_scene_gpu.py).
+// Results agree with an fp64 convolution to ~1e-6 of the output RMS (tests/test_scene_gpu.py), and per element within a bound built
+// from the norms of the signal windows and RIR partitions that feed the sample's own block (tests/test_scene_bounds_gpu.py with
+// tests/scene_reference.py): silence in gives exact silence out, block by block.
 //
 // Segmental-SNR mix: per (b, c) sums of squares of source and noise over the window [start, start + length) are reduced in a
 // fixed order (per-chunk partials, then a serial fold: bit-reproducible), a = sqrt(Ex / (En + 1e-9) * 10^(-snr/10)),
@@ -140,6 +142,18 @@ struct Fft3 {
     }
 };
 
+// Two real sequences share one complex FFT as z = s0 u + i s1 v.  The FFT's rounding noise is ~ u log2 N of |z|, so unscaled the
+// quieter member would carry noise of the louder one's size.  s0, s1: powers of two (exact to apply and to undo) that lift the quieter
+// member to within a factor two of the louder one's amplitude, from their energies e0, e1; both 1 when the two are that close already
+// or one of them is zero (a silent member is the caller's to keep silent).
+__device__ __forceinline__ void pair_scales(float e0, float e1, float& s0, float& s1) {
+    s0 = s1 = 1.f;
+    if (!(e0 > 0.f) || !(e1 > 0.f) || isinf(e0) || isinf(e1)) return;
+    const int k = ((__float_as_int(e0) >> 23) - (__float_as_int(e1) >> 23)) / 2;       // amplitudes: half the exponent gap of the energies
+    if (k > 0) s1 = __int_as_float((127 + min(k, 60)) << 23);
+    else if (k < 0) s0 = __int_as_float((127 + min(-k, 60)) << 23);
+}
+
 // pass 1 of the convolution.  Real input: TWO blocks share one complex FFT (z = u + i v;  U[k] = (Z[k] + conj Z[N-k]) / 2,
 // V[k] = (Z[k] - conj Z[N-k]) / 2i).  One workgroup per pair: blockIdx.x < n_sig = B * ceil(nb / 2): signal blocks (b, 2q), (b, 2q+1);
 // otherwise RIR partitions (b, c, 2q), (b, c, 2q+1).
@@ -174,11 +188,29 @@ __global__ __launch_bounds__(FFT_THREADS) void scene_fwd_fft_kernel(const float*
         const bool ok = threadIdx.x < F::M1 && n < take;
         v[a] = make_float2((ok && i0 >= 0 && i0 < hi) ? src[i0] : 0.f, (ok && second && i1 >= 0 && i1 < hi) ? src[i1] : 0.f);
     }
+    // Split out of the shared FFT, a member carries rounding noise of ~ u log2 N of the LOUDER member.  So a silent member keeps an
+    // exactly zero spectrum (every output block it alone feeds is silence, not that noise), and the quieter of two live members rides
+    // through the FFT lifted to its partner's size (pair_scales: a power of two, exact both ways).
+    bool nz0 = false, nz1 = false;
+    float e0 = 0.f, e1 = 0.f;
+#pragma unroll
+    for (int a = 0; a < R1; ++a) {
+        nz0 |= v[a].x != 0.f; nz1 |= v[a].y != 0.f;
+        e0 = fmaf(v[a].x, v[a].x, e0); e1 = fmaf(v[a].y, v[a].y, e1);
+    }
+    __shared__ float red[FFT_THREADS / 64];
+    const bool live0 = __syncthreads_or(nz0), live1 = __syncthreads_or(nz1);
+    float s0, s1;
+    pair_scales(block_sum(e0, red), block_sum(e1, red), s0, s1);
+#pragma unroll
+    for (int a = 0; a < R1; ++a) { v[a].x *= s0; v[a].y *= s1; }
     F::template run<false>(v, lds);
+    const float2 zero = make_float2(0.f, 0.f);
+    const float h0 = 0.5f / s0, h1 = 0.5f / s1;
     for (int k = threadIdx.x; k < NB; k += FFT_THREADS) {
         const float2 zk = lds[k], zm = lds[(N - k) & (N - 1)];
-        out[k] = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
-        if (second) out[NB + k] = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
+        out[k] = live0 ? make_float2(h0 * (zk.x + zm.x), h0 * (zk.y - zm.y)) : zero;
+        if (second) out[NB + k] = live1 ? make_float2(h1 * (zk.y + zm.y), -h1 * (zk.x - zm.x)) : zero;
     }
 }
 
@@ -229,10 +261,28 @@ __global__ __launch_bounds__(FFT_THREADS) void scene_mac_ifft_kernel(const float
             }
         }
     }
+    // The two blocks share the inverse FFT as the forward pairs do (pair_scales).  A block whose products are all exactly zero
+    // (silent windows or silent partitions only) is silence, not the rounding noise of the other block; the quieter of two live
+    // blocks is lifted to the louder one's size on the way through.
+    bool nz0 = false, nz1 = false;
+    float e0 = 0.f, e1 = 0.f;
+#pragma unroll
+    for (int i = 0; i < KPT; ++i) {
+        nz0 |= a0[i].x != 0.f || a0[i].y != 0.f;
+        nz1 |= a1[i].x != 0.f || a1[i].y != 0.f;
+        if ((int)threadIdx.x + FFT_THREADS * i < NB) {
+            e0 = fmaf(a0[i].x, a0[i].x, fmaf(a0[i].y, a0[i].y, e0));
+            e1 = fmaf(a1[i].x, a1[i].x, fmaf(a1[i].y, a1[i].y, e1));
+        }
+    }
+    __shared__ float red[FFT_THREADS / 64];
+    const bool live0 = __syncthreads_or(nz0), live1 = __syncthreads_or(nz1);
+    float s0, s1;
+    pair_scales(block_sum(e0, red), block_sum(e1, red), s0, s1);
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
         const int k = (int)threadIdx.x + FFT_THREADS * i;
-        if (k < NB) { lds[k] = a0[i]; lds[NB + k] = a1[i]; }
+        if (k < NB) { lds[k] = make_float2(a0[i].x * s0, a0[i].y * s0); lds[NB + k] = make_float2(a1[i].x * s1, a1[i].y * s1); }
     }
     __syncthreads();
     float2 v[R1];
@@ -247,12 +297,12 @@ __global__ __launch_bounds__(FFT_THREADS) void scene_mac_ifft_kernel(const float
     }
     __syncthreads();
     F::template run<true>(v, lds);
-    const float inv = 1.0f / (float)N;
+    const float inv0 = 1.0f / ((float)N * s0), inv1 = 1.0f / ((float)N * s1);
     float* yo = y + ((long)b * C + c) * T + (long)j0 * Bk;
     const int nvalid = min(2 * Bk, T - j0 * Bk);             // block j1 follows j0 in y
     for (int n = threadIdx.x; n < nvalid; n += FFT_THREADS) {
         const float2 z = lds[Bk + (n & (Bk - 1))];
-        const float r = (n < Bk ? z.x : z.y) * inv;
+        const float r = n < Bk ? (live0 ? z.x * inv0 : 0.f) : (live1 ? z.y * inv1 : 0.f);
         yo[n] = accumulate ? yo[n] + r : r;
     }
 }
