@@ -88,7 +88,7 @@ class ComponentFactory:
             if a not in acts:
                 raise ValueError(f"Unknown {key}: {a}. Available activations: {list(acts)}")
         try:
-            return cls(**optimizer_group_settings(cfg), **layerdrop_settings(cfg), feature_extractor=extractor, transformer_encoder_cfg=TransformerEncoderCFG.create(),
+            return cls(**optimizer_group_settings(cfg), **layerdrop_settings(cfg), **freeze_settings(cfg), feature_extractor=extractor, transformer_encoder_cfg=TransformerEncoderCFG.create(),
                        transformer_encoder_layers_cfg=TransformerLayerCFG.create(norm_first=norm_first, dropout=drop_enc, activation=acts[act]()),
                        transformer_decoder_cfg=TransformerEncoderCFG.create(),
                        transformer_decoder_layers_cfg=TransformerLayerCFG.create(d_model=384, norm_first=norm_first_dec, dropout=drop_dec,
@@ -130,6 +130,30 @@ def layerdrop_settings(cfg) -> dict:
     return kw
 
 
+def freeze_settings(cfg) -> dict:
+    """The model keywords of partial training, only those that are set: trainer.feature_grad_mult (fairseq's factor on the gradient that
+    enters the conv stack, in [0, 1]; default 1) and trainer.freeze_feature_extractor_updates (optimiser steps during which
+    extract_audio.* stays frozen; default 0).  trainer.freeze, a list of fnmatch patterns on parameter names, is applied to the built
+    model (build_model) and recorded with them."""
+    kw = {}
+    mult = float(cfg.trainer.get("feature_grad_mult", 1.0))
+    if mult != 1.0:
+        kw["feature_grad_mult"] = mult
+    hold = int(cfg.trainer.get("freeze_feature_extractor_updates", 0) or 0)
+    if hold != 0:
+        kw["freeze_feature_extractor_updates"] = hold
+    return kw
+
+
+def freeze_patterns(cfg) -> tuple:
+    pats = cfg.trainer.get("freeze", None)
+    if pats is None or isinstance(pats, str) and not pats:
+        return ()
+    if isinstance(pats, str) and pats.startswith("[") and pats.endswith("]"):      # trainer.freeze=[extract_audio.*,*.bias] on the command line
+        pats = [p.strip().strip("'\"") for p in pats[1:-1].split(",") if p.strip()]
+    return (pats,) if isinstance(pats, str) else tuple(str(p) for p in pats)
+
+
 def monitor_settings(cfg) -> tuple:
     """(monitor_every, min_pred_var, min_target_var): trainer.monitor_every steps between two collapse monitors (0 = off, the default),
     trainer.min_pred_var / trainer.min_target_var the thresholds below which the run stops (0 = no check; data2vec 2.0: 0.01 / 0.1).
@@ -159,6 +183,10 @@ def build_model(cfg):
     network = ComponentFactory.create_network(cfg, extractor)
     if hasattr(network, "monitor_every"):
         network.monitor_every = monitor_settings(cfg)[0]
+    patterns = freeze_patterns(cfg)
+    if patterns:                 # trainer.freeze: recorded in the checkpoint's hyper-parameters, only when set
+        network.freeze(*patterns)
+        network.hparams["freeze"] = patterns
     return network, extractor.total_patches(int(cfg.data.sr * cfg.data.process_seconds))
 
 

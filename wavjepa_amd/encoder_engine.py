@@ -58,7 +58,11 @@ class _Layer:
     __slots__ = ("wqkv", "bqkv", "wo", "bo", "w1", "b1", "w2", "b2", "g1", "be1", "g2", "be2",
                  "gwqkv", "gbqkv", "gwo", "gbo", "gw1", "gb1", "gw2", "gb2", "gg1", "gbe1", "gg2", "gbe2",
                  "wqkv_name", "wo_name", "w1_name", "w2_name",      # parameter names of the weights (student stacks)
-                 "wqkvT", "woT", "w1T", "w2T")                      # bf16 W^T shadows (row-form dgrads), when the engine keeps them
+                 "wqkvT", "woT", "w1T", "w2T",                      # bf16 W^T shadows (row-form dgrads), when the engine keeps them
+                 "skip", "g_all")       # every parameter of the layer is frozen: the g* pointers read 0 (g_all keeps them, in _G_FIELDS' order)
+
+
+_G_FIELDS = ("gwqkv", "gbqkv", "gwo", "gbo", "gw1", "gb1", "gw2", "gb2", "gg1", "gbe1", "gg2", "gbe2")
 
 
 def _layer_ptrs(flat: FlatParams, prefix: str, teacher: bool) -> _Layer:
@@ -77,6 +81,7 @@ def _layer_ptrs(flat: FlatParams, prefix: str, teacher: bool) -> _Layer:
             setattr(L, "g" + k, flat.gptr(full))
             if is_w:
                 setattr(L, k + "_name", full)
+    L.skip, L.g_all = False, tuple(getattr(L, k) for k in _G_FIELDS)
     return L
 
 
@@ -206,6 +211,15 @@ class EncoderEngine:
         self.ln_lean_wgs = int(os.environ.get("WJ_LN_LEAN_WGS", "256"))
         self._lean_now = False                 # set inside the training forward only: inference runs one stream, nothing to stream under
         self._folds = []
+        # partial training (freeze.py; set_frozen): the frozen parameter names the step was last told of, the units all of whose
+        # parameters are frozen (no parameter-gradient launch), per backward section the elements of partly frozen units that are
+        # cleared behind it, and whether an accumulation window has been opened by a backward since the buffer was last clear
+        self._frozen: frozenset = frozenset()
+        self._skip: frozenset = frozenset()
+        self._clear_ranges: Dict[str, List[Tuple[int, int]]] = {}
+        self._frozen_memo: Dict[frozenset, tuple] = {}
+        self._accum_open = False
+        self.grad_mult = 1.0             # feature_grad_mult in (0, 1]: the factor on d(post[-1]) in front of the conv backward (0: frozen)
         self._bind_params()
         self._bind_wt()
 
@@ -271,6 +285,44 @@ class EncoderEngine:
             ptr, gptr = (lambda n: None if n is None else f.ptr32(n)), (lambda n: None if n is None else f.gptr(n))
             return ConvLayerParams(f.ptr16(w) if l == 0 else f.ptr32(w), ptr(b), ptr(g), ptr(be), gptr(w), gptr(b), gptr(g), gptr(be))
         return [[layer(pre, l) for l in range(len(c.conv_spec))] for pre in self.stacks]
+
+    def set_frozen(self, frozen) -> None:
+        """The frozen parameter names of the step about to run (a training-mode forward and its backward).  A layer all of whose
+        parameters are frozen hands 0 for every gradient pointer -- the norm and attention backwards then fold nothing, the dgrad
+        epilogue sums no columns -- and queues no weight gradient; the other units are asked through _skipped().  The frozen names of
+        a partly frozen unit are cleared behind their section of the backward (_clear_frozen).  An open accumulation window holds
+        sums made under the old set: ValueError."""
+        frozen = frozenset(frozen)
+        if frozen == self._frozen:
+            return
+        if self._accum_open and not self.flat.g_clean:
+            raise ValueError("the frozen set changed inside an open gradient-accumulation window: freeze / unfreeze between optimiser steps")
+        if frozen not in self._frozen_memo:          # (a schedule or a loop that alternates sets pays the name arithmetic once per set)
+            from . import freeze
+            names = [s.name for s in self.flat.slots]
+            by_tag: Dict[str, set] = {}
+            for name in freeze.partly_frozen(names, frozen):
+                by_tag.setdefault(freeze.section_of(name, self.cfg.l_enc), set()).add(name)
+            self._frozen_memo[frozen] = (freeze.skipped_units(names, frozen), {tag: self.flat.ranges_of(part) for tag, part in by_tag.items()})
+        self._frozen = frozen
+        self._skip, self._clear_ranges = self._frozen_memo[frozen]
+        for s, module in self.MODULE.items():
+            for i, w in enumerate(self._stack(s)[0]):
+                w.skip = f"{module}.layers.{i}" in self._skip
+                for k, g in zip(_G_FIELDS, w.g_all):
+                    setattr(w, k, 0 if w.skip else g)
+        self.flat.set_frozen(frozen)
+
+    def _skipped(self, unit: str) -> bool:
+        return unit in self._skip
+
+    def _clear_frozen(self, tag: Optional[str]) -> None:
+        """Zero the frozen elements of partly frozen units whose gradients section `tag` of the backward made final (None: all of
+        them), on the calling stream: one fill per merged range.  No launch when nothing is partly frozen."""
+        for t, ranges in self._clear_ranges.items():
+            if tag is None or t == tag:
+                for lo, hi in ranges:
+                    self.flat.g32[lo:hi].zero_()
 
     def _bind_wt(self) -> None:
         """W^T shadows: one more bf16 buffer with the parameter layout, every 2-D transformer weight stored transposed at its own offset."""
@@ -819,13 +871,14 @@ class EncoderEngine:
         """wj_layernorm_bwd; its dgamma / dbeta / dbias partials are folded later, together with the neighbours' (see _flush_folds), or
         in deterministic mode at once -- never by the kernel's own atomics then.  workspace: what an undeferred caller hands the
         kernel's own reduction (a deferring one: red_ws)."""
-        form, ws = self._fold_form(3 * D, bool(dgamma or dbeta or dbias), defer)
+        wanted = bool(dgamma or dbeta or dbias)      # (none: a skipped unit -- no partial rows, no fold slot)
+        form, ws = self._fold_form(3 * D, wanted, defer)
         ln_bwd = ops.layernorm_bwd
         if drop is not None:         # the addend r went through dropout: wj_layernorm_bwd_drop, the same partial rows
             ln_bwd, kw = ops.layernorm_bwd_drop, dict(kw, drop=drop)
         if form == "own":
             ln_bwd(dy, x, gamma, mean, rstd, M=M, D=D, dgamma=dgamma, dbeta=dbeta, dbias=dbias,
-                   workspace=self.red_ws if defer else workspace, **kw)
+                   workspace=(self.red_ws if defer else workspace) if wanted else None, **kw)
         else:
             ln_bwd(dy, x, gamma, mean, rstd, M=M, D=D, workspace=ws, **kw)
             self._fold(form, ws, 3 * D, ops.ln_bwd_partial_rows(M, D), dgamma, dbeta, dbias, D)
@@ -915,8 +968,9 @@ class EncoderEngine:
         The two weight gradients are queued (_wgrads)."""
         dsb2, dh = bw["dsb2"][parity], bw["dh"][parity]
         self._dgrad(dsb2, w, "w2", dh, M=M, N=4 * D, K=D, epilogue=ops.EPI_MUL_GELU_GRAD, aux=a.h,
-                    colsum=w.gb1)        # linear1.bias gradient = column sums of dh, fused into the producing epilogue
-        bw["pending"] += [(dsb2, a.g, w.gw2, D, 4 * D, M), (dh, xb, w.gw1, 4 * D, D, M)]
+                    colsum=w.gb1 or None)        # linear1.bias gradient = column sums of dh, fused into the producing epilogue
+        if not w.skip:                   # (a layer all of whose parameters are frozen: no weight gradient)
+            bw["pending"] += [(dsb2, a.g, w.gw2, D, 4 * D, M), (dh, xb, w.gw1, 4 * D, D, M)]
         self._dgrad(dh, w, "w1", bw["dgb"], M=M, N=D, K=4 * D)
 
     def _attn_block_bwd(self, w: _Layer, a: _Acts, xb: torch.Tensor, bw: dict, parity: int, M: int, D: int, H: int, B: int,
@@ -938,7 +992,8 @@ class EncoderEngine:
             self._attn_bwd(a.qkv, a.o, do, a.lse, dqkv, B=B, T=seq[1], H=H, hd=D // H, seq_off=seq[0], dbias=w.gbqkv, drop=drop)
         else:
             self._attn_bwd(a.qkv, a.o, do, a.lse, dqkv, B=B, T=self.T, H=H, hd=D // H, key_mask=mask, dbias=w.gbqkv, drop=drop)
-        bw["pending"] += [(dsb1, o_in, w.gwo, D, D, Ms), (dqkv, xb, w.gwqkv, 3 * D, D, M)]
+        if not w.skip:
+            bw["pending"] += [(dsb1, o_in, w.gwo, D, D, Ms), (dqkv, xb, w.gwqkv, 3 * D, D, M)]
         return ds_all
 
     def _wgrads(self, bw: dict, parity: int, flush: bool) -> None:
@@ -967,7 +1022,7 @@ class EncoderEngine:
                    dx_out: torch.Tensor, M: int, D: int, H: int, B: int, mask: Optional[torch.Tensor], bw: dict, parity: int,
                    seq: Optional[Tuple[torch.Tensor, int]] = None,
                    sub: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None, flush: bool = True, bottom: bool = False,
-                   stack: str = "enc", li: int = 0):
+                   stack: str = "enc", li: int = 0, floor: bool = False):
         """d(x2) = dy (fp32) + dyb (bf16 or None) -> d(x_in), returned as (fp32 part, bf16 part or None, flushed); parameter gradients
         accumulated into the flat gradient buffer.
         The grad_input of linear1 and in_proj is what a bf16 linear returns under autocast -- a bf16 tensor (`dgb` / `dxb`) -- and the
@@ -977,7 +1032,8 @@ class EncoderEngine:
         Returns flushed = True when the weight-gradient queue went out (_wgrads: the queued layers' gradients are then final in
         side-stream order).
         stack, li: which layer this is -- under dropout the two LayerNorm backwards and the attention backward regenerate the forward's
-        masks from them (the FFN site needs nothing: a.g and a.h were stored masked)."""
+        masks from them (the FFN site needs nothing: a.g and a.h were stored masked).
+        floor: nothing trainable lies below this layer (freeze.py): its own parameter gradients, no in_proj dgrad."""
         ds, dxb, dqkv = bw["ds"], bw["dxb"], bw["dqkv"][parity]
         if not self.recompute:             # (recompute mode: _redo_layer waited for the slot before it wrote the activations)
             self._slot_wait(bw, parity)
@@ -991,6 +1047,8 @@ class EncoderEngine:
                      dgamma=w.gg1, dbeta=w.gbe1, dbias=w.gbo, drop=self._drop(stack, li, ops.DROP_SITE_RES1))      # ds updated in place
         ds_all = self._attn_block_bwd(w, a, xb_in, bw, parity, M, D, H, B, mask, seq, sub, drop=self._drop(stack, li, ops.DROP_SITE_ATTN))
         self._wgrads(bw, parity, flush)
+        if floor:
+            return None, None, flush
         if bottom:
             self._dgrad(dqkv, w, "wqkv", dx_out, M=M, N=D, K=3 * D, epilogue=ops.EPI_ADD_F32, aux=ds_all)
             return dx_out, None, flush
@@ -1105,11 +1163,13 @@ class EncoderEngine:
 
     def _stack_bwd(self, stack: str, x0: torch.Tensor, xb0: torch.Tensor, M: int, B: int, mask: Optional[torch.Tensor],
                    seq: Optional[Tuple[torch.Tensor, int]] = None, *, sub: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None,
-                   flushed=None) -> torch.Tensor:
+                   flushed=None, layers_run: bool = True, stop: Optional[int] = None) -> Optional[torch.Tensor]:
         """Backward of _stack_fwd: bw["dx1"] holds the fp32 gradient of the final norm's output (nothing bypasses that norm); returns
         the fp32 gradient of the stack's input (x0, xb0).  The weight gradients of bw["group"] consecutive layers share a grouped
         launch; `flushed(i)` is called behind layer i when its launch has been queued.  Recompute mode: every layer's forward is issued
-        again in front of its backward (_redo_layer).  LayerDrop: only the layers of _kept(stack) are walked (those the forward ran)."""
+        again in front of its backward (_redo_layer).  LayerDrop: only the layers of _kept(stack) are walked (those the forward ran).
+        Partial training (freeze.BackwardPlan.stack_walk): layers_run=False -- the final norm's own gradients only; stop = j -- the walk
+        ends with the j-th kept layer, which computes no data gradient into its input.  Either way nothing is returned."""
         f, bw = self.flat, self.bw[stack]
         layers, D, H, pre, norm = self._stack(stack)
         acts = self._acts(stack)
@@ -1119,7 +1179,15 @@ class EncoderEngine:
         kept = self._kept(stack)
         top, nbuf, group = len(kept) - 1, bw["nbuf"], bw["group"]
         Mo = M if sub is None else sub[2]                      # rows that left the stack
-        grads = dict(dgamma=f.gptr(norm + ".weight"), dbeta=f.gptr(norm + ".bias"))
+        grads = {} if self._skipped(norm) else dict(dgamma=f.gptr(norm + ".weight"), dbeta=f.gptr(norm + ".bias"))
+        if not layers_run and top >= 0:
+            # the floor is the final norm: its dgamma / dbeta only (the norm's input gradient goes to bw["dy"] and is not read)
+            if pre:
+                self._ln_pre_bwd(bw["dx1"], getattr(self, stack + "_sf"), f.ptr32(norm + ".weight"), fm, fr, M=Mo, D=D, ds_f32=bw["dy"], **grads)
+            else:
+                self._ln_bwd(bw["dx1"], acts[top].x2, f.ptr32(norm + ".weight"), fm, fr, M=Mo, D=D, ds_f32=bw["dy"], defer=False,
+                             workspace=self.red_ws, **grads)
+            return None
         if top < 0:
             # no layer ran: the final norm read the stack's input (its sub-rows), and its backward's output is the input's gradient
             x_in = x0 if sub is None else self.tail_x
@@ -1140,22 +1208,26 @@ class EncoderEngine:
             self._ln_bwd(bw["dx1"], acts[top].x2, f.ptr32(norm + ".weight"), fm, fr, M=Mo, D=D, ds_f32=bw["dy"], defer=False,
                          workspace=self.red_ws, **grads)
         dy, dyb = bw["dy"], None
-        for j in range(top, -1, -1):
+        last = 0 if stop is None else stop     # the lowest position whose backward runs
+        for j in range(top, last - 1, -1):
             i = kept[j]
             w, a, sub_j = layers[i], acts[j], sub if j == top else None
-            flush = (top - j) % group == group - 1 or j == 0
+            flush = (top - j) % group == group - 1 or j == last
+            floor = stop is not None and j == stop
             if self.recompute:
                 self._redo_layer(stack, j, x0, xb0, M, B, mask, seq, sub_j)
             if pre:
-                dy, done = self._layer_bwd_pre(w, a, x0 if j == 0 else a.x1, layers[kept[j - 1]] if j > 0 else None, bw["dy"], M, D, H, B,
-                                               mask, bw, j % nbuf, seq, sub=sub_j, flush=flush)
+                # (the floor of a pre-norm stack still runs its own norm1 backward, for that norm's parameters; the stream gradient
+                # it writes to bw["dy"] is not read, and the layer below gets nothing)
+                dy, done = self._layer_bwd_pre(w, a, x0 if j == 0 else a.x1, layers[kept[j - 1]] if j > 0 and not floor else None, bw["dy"],
+                                               M, D, H, B, mask, bw, j % nbuf, seq, sub=sub_j, flush=flush)
             else:
                 x_in, xb_in = (x0, xb0) if j == 0 else (acts[j - 1].x2, acts[j - 1].x2b)
                 dy, dyb, done = self._layer_bwd(w, a, x_in, xb_in, dy, dyb, bw["dy"], M, D, H, B, mask, bw, j % nbuf, seq, sub=sub_j,
-                                                flush=flush, bottom=j == 0, stack=stack, li=i)
+                                                flush=flush, bottom=j == 0, stack=stack, li=i, **(dict(floor=True) if floor else {}))
             if done and flushed is not None:
                 flushed(i)
-        return dy
+        return None if stop is not None else dy
 
     # ------------------------------------------------------------------------------------------------ front-end
     def _frontend(self, audio: torch.Tensor) -> None:
@@ -1189,6 +1261,7 @@ class EncoderEngine:
         if clear or (not accumulate and not f.g_clean):      # (FusedAdamW.fuse_zero_grad: the last update left the buffer clear)
             f.g32.zero_()
         f.g_clean = False
+        self._accum_open = bool(accumulate)      # (set_frozen: the buffer holds sums made under the current frozen set)
         if self.deterministic:
             self._det_ws()              # (the slabs exist before the first launch; allocated once)
         self.refresh_wt()               # (a step that did it beside its forward: a no-op then)
@@ -1205,6 +1278,9 @@ class EncoderEngine:
         detached, jepa.py:408), and the conv backward may run over the plan's active rows only."""
         c, f = self.cfg, self.flat
         M, C, De = self.M, self.C, c.d_enc
+        front, conv = not self._skipped("front"), not self._skipped("extract_audio")
+        if not (front or conv):
+            return
         if rag:
             ops.unmask_rows_f32(dy, plan.inv, self.d_lf_b, M=M, D=De, src_is_f32=True, dst_is_bf16=True)
             if not self.has_mapper:
@@ -1213,17 +1289,28 @@ class EncoderEngine:
         else:
             ops.cast_f32_to_bf16(dy, self.d_lf_b, M * De)
         if self.has_mapper:
-            self._colsum_bf16(self.d_lf_b, f.gptr("post_extraction_mapper.bias"), M=M, N=De, ldx=De)
-            self._wgrad(self.d_lf_b, self.fn_b, f.gptr("post_extraction_mapper.weight"), De, C, M)
+            if front:
+                self._colsum_bf16(self.d_lf_b, f.gptr("post_extraction_mapper.bias"), M=M, N=De, ldx=De)
+                self._wgrad(self.d_lf_b, self.fn_b, f.gptr("post_extraction_mapper.weight"), De, C, M)
             ops.gemm(self.d_lf_b, f.ptr16("post_extraction_mapper.weight"), self.d_fn, M=M, N=C, K=De, lda=De, ldb=C, ldc=C,
                      b_trans=1, epilogue=ops.EPI_ADD_F32)
             d_fn = self.d_fn
         else:
             d_fn = dy
         S, Tc = self.S, self.Tc
+        # (a frozen conv stack: the backward stops here -- feature_norms' own gradients, no d(post[-1]); a frozen front above a
+        # trainable conv stack: the data gradient only)
+        grads = dict(dgamma=f.gptr("feature_norms.weight"), dbeta=f.gptr("feature_norms.bias")) if front else {}
         self._ln_bwd(d_fn, self.front.post_ptr[-1], f.ptr32("feature_norms.weight"), self.fn_mean, self.fn_rstd, M=M, D=C, defer=False,
-                     ds_bf16=self.front.dpost_ptr[-1], dgamma=f.gptr("feature_norms.weight"), dbeta=f.gptr("feature_norms.bias"),
+                     ds_bf16=self.front.dpost_ptr[-1] if conv else None, **grads,
                      x_is_bf16=True, in_seg=self.P[-1], in_valid=Tc, out_seg=self.P[-1], out_valid=Tc, chan=S if S > 1 else 0)
+        if not conv:
+            return
+        if self.grad_mult != 1.0:
+            # feature_grad_mult (fairseq's GradMultiply on the conv output): one in-place pass over the bf16 d(post[-1]), rounded where
+            # bf16 autocast rounds it; feature_norms and everything above saw the unscaled gradient.  (The C ABI has no scaling entry
+            # for a bf16 tensor: this is torch's elementwise kernel.  Zero rows of a sparse step stay zero.)
+            self.front.dpost[-1].mul_(self.grad_mult)
         # conv backward over the active rows only on a ragged step (sparse_conv), over every row otherwise
         self.front.backward(self, self.audio, plan if rag and self.sparse_conv else None)
 

@@ -20,6 +20,7 @@ import torch
 from . import ops
 from .conv_frontend import ConvFrontend, ConvLayerParams, _empty, conv_active_rows, conv_geometry  # noqa: F401  (re-exported)
 from .encoder_engine import EncoderEngine, EngineConfig, _layer_ptrs  # noqa: F401  (re-exported)
+from .freeze import BackwardPlan
 from .mask_plan import MaskPlan, make_mask_plan  # noqa: F401  (re-exported)
 from .params import FlatParams
 from .upload import _UPLOAD_STREAMS, _upload_stream, pack_upload  # noqa: F401  (re-exported)
@@ -313,21 +314,46 @@ class JepaEngine(EncoderEngine):
         `on_grads_ready(tag)` is called (host side, stream-ordered) as sections of the flat gradient buffer become
         final: "dec" (predictor + both mappers), "enc:<i>" after encoder layer i, "front" at the end -- the hook the
         data-parallel wrapper uses to launch bucketed RCCL all-reduces that overlap the rest of the backward."""
+        # partial training (freeze.py): the parameter-gradient work of a skipped unit is not launched, and the backward ends at the
+        # floor, the lowest unit that is trainable and ran.  Nothing frozen: every test below passes, the launches are the parent's.
+        c, f, plan = self.cfg, self.flat, self.plan
+        fz = BackwardPlan(self._skip, c.l_enc, c.l_dec, self._kept_now)
         if on_grads_ready is None:
             ready = lambda tag: None
         elif self.use_side:
             # a section is final once BOTH streams are past this point: issue the hook (the bucket's all-reduce) from the
             # side stream after it has waited for the main stream, so that the main dgrad chain never stalls on it
-            ready = lambda tag: self._on_side(lambda: on_grads_ready(tag))
+            ready = lambda tag: self._on_side(lambda: (self._clear_frozen(tag), on_grads_ready(tag)))
         else:
-            ready = on_grads_ready
+            ready = lambda tag: (self._clear_frozen(tag), on_grads_ready(tag))
         section_final = ready
 
         def ready(tag):                  # a section is final only once the pending parameter-gradient folds have been queued
             if on_grads_ready is not None:       # (no consumer of sections: the folds go out in full groups and at the end)
                 self._flush_folds()
             section_final(tag)
-        c, f, plan = self.cfg, self.flat, self.plan
+        enc_ready = set()
+
+        def rest_ready():
+            # the student layers nobody has reported yet (LayerDrop: those below the lowest one that ran; partial training: those
+            # below the floor): final from the start, reported in descending order so that the listener hears every index once
+            for j in range(c.l_enc - 1, -1, -1):
+                if j not in enc_ready:
+                    enc_ready.add(j)
+                    ready(f"enc:{j}")
+        if fz.floor is None:
+            # everything is frozen: no launch.  The sections are reported all the same (the collectives of a data-parallel step are
+            # the same on every rank and every step); the buffer reads zero, as behind any backward's clear
+            self._folds = []             # (what _backward_open resets: entries an earlier backward that raised may have left)
+            self._accum_open = bool(accumulate)
+            if not accumulate and not f.g_clean:
+                f.g32.zero_()
+                f.g_clean = True
+            if on_grads_ready is not None:
+                ready("dec")
+                rest_ready()
+                on_grads_ready("front")
+            return
         N, M, Mp, T, G = self.N, self.M, self.Mp, self.T, self.G
         De, Dd = c.d_enc, c.d_dec
         self._backward_open(accumulate)
@@ -338,51 +364,70 @@ class JepaEngine(EncoderEngine):
         bw = self.bw["dec"]
         # decoder_to_encoder_mapper
         Mo = plan.n_tgt if (rag and self.tail is not None) else Md       # rows that left the predictor
-        self._colsum_bf16(self.dpreds, f.gptr("decoder_to_encoder_mapper.bias"), M=Mo, N=De, ldx=De)
-        self._wgrad(self.dpreds, self.dec_out_b, f.gptr("decoder_to_encoder_mapper.weight"), De, Dd, Mo)
-        ops.gemm(self.dpreds, f.ptr16("decoder_to_encoder_mapper.weight"), bw["dx1"], M=Mo, N=Dd, K=De, lda=De, ldb=Dd, ldc=Dd,
-                 b_trans=1, epilogue=ops.EPI_ADD_F32)
-        dy = self._stack_bwd("dec", self.dec_in, self.dec_in_b, Md, N * G, plan.vis_u8, dseq, sub=self.tail if rag else None)
+        if not fz.skipped("decoder_to_encoder_mapper"):
+            self._colsum_bf16(self.dpreds, f.gptr("decoder_to_encoder_mapper.bias"), M=Mo, N=De, ldx=De)
+            self._wgrad(self.dpreds, self.dec_out_b, f.gptr("decoder_to_encoder_mapper.weight"), De, Dd, Mo)
+        dy = None
+        if fz.below("decoder_to_encoder_mapper"):
+            ops.gemm(self.dpreds, f.ptr16("decoder_to_encoder_mapper.weight"), bw["dx1"], M=Mo, N=Dd, K=De, lda=De, ldb=Dd, ldc=Dd,
+                     b_trans=1, epilogue=ops.EPI_ADD_F32)
+            run, stop = fz.stack_walk("decoder", self._kept("dec"))
+            walk = {} if (run and stop is None) else dict(layers_run=run, stop=stop)
+            if run or not fz.skipped("decoder.norm"):
+                dy = self._stack_bwd("dec", self.dec_in, self.dec_in_b, Md, N * G, plan.vis_u8, dseq, sub=self.tail if rag else None, **walk)
         n_ctx = plan.n_ctx
-        # the mask-token gradient leaves the kernel as one partial row per workgroup, folded with the other deferred folds (round 4:
-        # 384 global float atomics per workgroup into the same 384 addresses); deterministic mode: never the kernel's own atomics
-        sf_rows = ops.scatter_fill_bwd_partial_rows(N, T)
-        form, ws = self._fold_form(Dd, True, fits=sf_rows * Dd * 4 <= self._red_bytes)
-        if form == "now" and sf_rows * Dd * 4 > self.red_ws.numel() * 4:
-            raise RuntimeError("deterministic mode: the mask-token partial rows do not fit the reduction scratch")
-        ops.mask_scatter_fill_pos_bwd(dy, plan.inv, self.d_cf, f.gptr("mask_token"), B=N, T=T, D=Dd, G=G,
-                                      rowmap=plan.dec_map if rag else None, partials=ws)
-        self._fold(form, ws, Dd, sf_rows, f.gptr("mask_token"), None, None, Dd)
-        # encoder_to_decoder_mapper (rows = gathered context tokens)
-        self._colsum_bf16(self.d_cf, f.gptr("encoder_to_decoder_mapper.bias"), M=n_ctx, N=Dd, ldx=Dd)
-        self._wgrad(self.d_cf, self.ctx_in, f.gptr("encoder_to_decoder_mapper.weight"), Dd, De, n_ctx)
-        ops.gemm(self.d_cf, f.ptr16("encoder_to_decoder_mapper.weight"), self.d_ctx_in, M=n_ctx, N=De, K=Dd, lda=Dd, ldb=De,
-                 ldc=De, b_trans=1)
+        if fz.reaches("mask_token"):
+            # the mask-token gradient leaves the kernel as one partial row per workgroup, folded with the other deferred folds (round 4:
+            # 384 global float atomics per workgroup into the same 384 addresses); deterministic mode: never the kernel's own atomics
+            if fz.skipped("mask_token"):         # (the data gradient only)
+                ops.mask_scatter_fill_pos_bwd(dy, plan.inv, self.d_cf, None, B=N, T=T, D=Dd, G=G, rowmap=plan.dec_map if rag else None)
+            else:
+                sf_rows = ops.scatter_fill_bwd_partial_rows(N, T)
+                form, ws = self._fold_form(Dd, True, fits=sf_rows * Dd * 4 <= self._red_bytes)
+                if form == "now" and sf_rows * Dd * 4 > self.red_ws.numel() * 4:
+                    raise RuntimeError("deterministic mode: the mask-token partial rows do not fit the reduction scratch")
+                ops.mask_scatter_fill_pos_bwd(dy, plan.inv, self.d_cf, f.gptr("mask_token"), B=N, T=T, D=Dd, G=G,
+                                              rowmap=plan.dec_map if rag else None, partials=ws)
+                self._fold(form, ws, Dd, sf_rows, f.gptr("mask_token"), None, None, Dd)
+        if fz.reaches("encoder_to_decoder_mapper"):
+            # encoder_to_decoder_mapper (rows = gathered context tokens)
+            if not fz.skipped("encoder_to_decoder_mapper"):
+                self._colsum_bf16(self.d_cf, f.gptr("encoder_to_decoder_mapper.bias"), M=n_ctx, N=Dd, ldx=Dd)
+                self._wgrad(self.d_cf, self.ctx_in, f.gptr("encoder_to_decoder_mapper.weight"), Dd, De, n_ctx)
+            if fz.below("encoder_to_decoder_mapper"):
+                ops.gemm(self.d_cf, f.ptr16("encoder_to_decoder_mapper.weight"), self.d_ctx_in, M=n_ctx, N=De, K=Dd, lda=Dd, ldb=De,
+                         ldc=De, b_trans=1)
         ready("dec")
-        bw = self.bw["enc"]
-        if rag:
-            ops.unmask_rows_f32(self.d_ctx_in, None, bw["dx1"], M=Me, D=De)      # packed rows: a widening copy
-        else:
-            ops.unmask_rows_f32(self.d_ctx_in, plan.inv, bw["dx1"], M=M, D=De)
-        enc_ready = set()
-        every = "enc" not in self._kept_now              # no LayerDrop in this step: every layer ran
+        if fz.below("encoder_to_decoder_mapper"):
+            bw = self.bw["enc"]
+            if rag:
+                ops.unmask_rows_f32(self.d_ctx_in, None, bw["dx1"], M=Me, D=De)      # packed rows: a widening copy
+            else:
+                ops.unmask_rows_f32(self.d_ctx_in, plan.inv, bw["dx1"], M=M, D=De)
+            every = "enc" not in self._kept_now              # no LayerDrop in this step: every layer ran
 
-        def flushed(i):
-            # the weight gradients of two layers share a grouped launch: a layer's section of the gradient buffer is final (and its
-            # all-reduce bucket may go) once the launch that carries it has been queued.  LayerDrop: the section of a layer that did
-            # not run is final from the start (the zeros of the cleared buffer, or what earlier micro-batches left); it is reported
-            # with the next layer below it that ran, so the listener still hears every index once, in descending order.
-            for j in range(min(c.l_enc - 1, i + bw["group"] - 1) if every else c.l_enc - 1, i - 1, -1):
-                if j not in enc_ready:
-                    enc_ready.add(j)
-                    ready(f"enc:{j}")
-        first = (self.enc_in, self.enc_in_b) if rag else (self.lf, self.lf_b)
-        dy = self._stack_bwd("enc", first[0], first[1], Me, N, plan.ctx_u8, eseq, flushed=flushed)
-        if not every and len(enc_ready) < c.l_enc:
-            flushed(0)                                   # layers below the lowest one that ran (or all of them: none ran)
-        self._frontend_bwd(dy, rag, plan)
+            def flushed(i):
+                # the weight gradients of two layers share a grouped launch: a layer's section of the gradient buffer is final (and its
+                # all-reduce bucket may go) once the launch that carries it has been queued.  LayerDrop: the section of a layer that did
+                # not run is final from the start (the zeros of the cleared buffer, or what earlier micro-batches left); it is reported
+                # with the next layer below it that ran, so the listener still hears every index once, in descending order.
+                for j in range(min(c.l_enc - 1, i + bw["group"] - 1) if every else c.l_enc - 1, i - 1, -1):
+                    if j not in enc_ready:
+                        enc_ready.add(j)
+                        ready(f"enc:{j}")
+            first = (self.enc_in, self.enc_in_b) if rag else (self.lf, self.lf_b)
+            run, stop = fz.stack_walk("encoder", self._kept("enc"))
+            walk = {} if (run and stop is None) else dict(layers_run=run, stop=stop)
+            dy = self._stack_bwd("enc", first[0], first[1], Me, N, plan.ctx_u8, eseq, flushed=flushed, **walk)
+        if len(enc_ready) < c.l_enc:
+            rest_ready()                                 # layers below the lowest one that ran (or all of them: none ran)
+        if fz.reaches("front"):
+            self._frontend_bwd(dy, rag, plan)
         self._backward_close()
-        if on_grads_ready is not None:
+        if on_grads_ready is None:
+            self._clear_frozen(None)
+        else:
+            self._clear_frozen("front")
             on_grads_ready("front")
 
     # ------------------------------------------------------------------------------------------------ EMA

@@ -20,9 +20,11 @@ from torch import nn
 from . import ops
 from .engine import EngineConfig, JepaEngine
 from .extractors.audio_extractor import Extractor
+from .freeze import check_grad_mult, is_student, match
 from .functions import trunc_normal_
 from .layerdrop import check_keep, check_rate, kept_layers
 from .mask_plan import MaskPlan, make_mask_plan
+from .optim import MAX_GROUPS, resolve_groups, trainable
 from .params import FlatParams
 from .pos_embed import get_1d_sincos_pos_embed_from_grid
 from .types import ForwardReturn, TransformerEncoderCFG, TransformerLayerCFG, activation_kind_of
@@ -165,12 +167,21 @@ class FusedAdamW(torch.optim.Optimizer):
         self._assignment = None          # {parameter name: group index} of a grouped optimiser
         self._group_map = None           # its device byte map, made with the flat buffers
         if groups is None:
-            params = [p for p in module.parameters() if p.requires_grad]
+            params = [p for _, p in trainable(module)]
         else:
-            from .optim import resolve_groups
             params, self._assignment = resolve_groups(module, groups, defaults)
         super().__init__(params, defaults)
         self._module = module
+        # Partial training: the parameters the module holds frozen (JEPA.freeze, requires_grad_(False), feature_grad_mult = 0, the
+        # freeze_feature_extractor_updates schedule) move into ONE extra group with lr = 0 and weight_decay = 0 -- p - 0 * x is p
+        # exactly, in the fp32 master and its bf16 shadow -- which exists only while something is frozen; step() reads the set again
+        # at every call.  _home: every group's full parameter list, to which a released parameter returns.
+        self._home = [list(q["params"]) for q in self.param_groups]
+        self._names = {id(p): n for n, p in trainable(module)}
+        self._frozen_seen: frozenset = frozenset()
+        self._frozen_assignment = None
+        self._map_memo: Dict[frozenset, torch.Tensor] = {}       # frozen set -> its device byte map (a few: a schedule has two)
+        self._sync_frozen_group()
         self.max_grad_norm = max_grad_norm
         self._t = 0
         self._sumsq = None
@@ -190,6 +201,28 @@ class FusedAdamW(torch.optim.Optimizer):
         # p.grad then reads 0 after step() -- what zero_grad() leaves; a caller that inspects gradients after step() keeps it off.
         self.fuse_zero_grad = False
 
+    def _sync_frozen_group(self) -> None:
+        """Follow the module's frozen set: the lr = 0 group holds exactly the frozen parameters (and is absent when there are none),
+        every other group what is left of its own."""
+        names_of = getattr(self._module, "_frozen_for_update", None)
+        frozen = names_of() if names_of is not None else frozenset()
+        if frozen == self._frozen_seen:
+            return
+        base = [q for q in self.param_groups if not q.get("frozen")]
+        if frozen and len(base) + 1 > MAX_GROUPS:
+            raise ValueError(f"{len(base)} parameter groups and the group of frozen parameters: FusedAdamW takes at most {MAX_GROUPS}")
+        for q, home in zip(base, self._home):
+            q["params"] = [p for p in home if self._names[id(p)] not in frozen]
+        self.param_groups[:] = base
+        self._frozen_assignment = None
+        if frozen:
+            held = [p for home in self._home for p in home if self._names[id(p)] in frozen]
+            self.param_groups.append(dict(self.defaults, params=held, lr=0.0, weight_decay=0.0, frozen=True))
+            own = self._assignment or {}
+            self._frozen_assignment = {n: (len(base) if n in frozen else own.get(n, 0)) for n in self._names.values()}
+        self._frozen_seen = frozen
+        self._group_map = self._map_memo.get(frozen)         # (the byte map of a set seen before, while the flat buffers are the same)
+
     def _ensure_scratch(self, flat) -> None:
         if self._sumsq is None:
             self._sumsq = torch.zeros(1, dtype=torch.float32, device=flat.device)
@@ -206,6 +239,7 @@ class FusedAdamW(torch.optim.Optimizer):
         flat = m._flat
         flat.ensure_adam_state()
         self._ensure_scratch(flat)
+        self._sync_frozen_group()
         g = self.param_groups[0]
         self._t += 1
         if self.max_grad_norm > 0:
@@ -213,18 +247,24 @@ class FusedAdamW(torch.optim.Optimizer):
         zg = bool(self.fuse_zero_grad) and _ADAMW_ZERO_GRAD
         kw = dict(beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], step=self._t,
                   max_norm=self.max_grad_norm, sumsq=self._sumsq if self.max_grad_norm > 0 else None)
-        if self._assignment is None:
+        assignment = self._frozen_assignment or self._assignment      # (with something frozen: the groups and the lr = 0 group behind them)
+        if assignment is None:
             kw.update(lr=float(g["lr"]), weight_decay=g["weight_decay"])
             adamw = ops.adamw_step
         else:                            # every group's pair, read now: schedulers and the user write them between steps
             if self._group_map is None or self._group_map.device != flat.p32.device or self._group_map.numel() * 8 != flat.n:
-                self._group_map = flat.group_map(self._assignment)
-            kw.update(lr=[float(q["lr"]) for q in self.param_groups], weight_decay=[float(q["weight_decay"]) for q in self.param_groups],
+                self._group_map = flat.group_map(assignment)
+                if self._frozen_assignment is not None:
+                    if len(self._map_memo) >= 4:
+                        self._map_memo.clear()
+                    self._map_memo[self._frozen_seen] = self._group_map
+            live = lambda q, key: 0.0 if q.get("frozen") else float(q[key])      # (whatever a scheduler wrote into the frozen group)
+            kw.update(lr=[live(q, "lr") for q in self.param_groups], weight_decay=[live(q, "weight_decay") for q in self.param_groups],
                       group_map=self._group_map)
             adamw = ops.adamw_groups_step
 
         def update(lo: int, hi: int, workgroups: int = 0) -> None:
-            where = {} if self._assignment is None else dict(first=lo)
+            where = {} if assignment is None else dict(first=lo)
             adamw(flat.p32.data_ptr() + 4 * lo, flat.g32.data_ptr() + 4 * lo, flat.adam_m.data_ptr() + 4 * lo,
                   flat.adam_v.data_ptr() + 4 * lo, hi - lo, p_bf16=flat.p16.data_ptr() + 2 * lo, workgroups=workgroups, zero_grad=zg, **where, **kw)
         eng = m._engine
@@ -262,8 +302,9 @@ class FusedAdamW(torch.optim.Optimizer):
         sd = dict(step=self._t, lr=self.param_groups[0]["lr"], m=None if flat is None or flat.adam_m is None else flat.adam_m.cpu(),
                   v=None if flat is None or flat.adam_v is None else flat.adam_v.cpu())
         if self._assignment is not None:     # a grouped optimiser: every group's pair, for the reason given for lr below
-            sd["group_lr"] = [float(q["lr"]) for q in self.param_groups]
-            sd["group_weight_decay"] = [float(q["weight_decay"]) for q in self.param_groups]
+            own = [q for q in self.param_groups if not q.get("frozen")]      # (the lr = 0 group of frozen parameters follows the module)
+            sd["group_lr"] = [float(q["lr"]) for q in own]
+            sd["group_weight_decay"] = [float(q["weight_decay"]) for q in own]
         return sd
 
     def load_state_dict(self, sd):
@@ -271,9 +312,10 @@ class FusedAdamW(torch.optim.Optimizer):
         if sd.get("lr") is not None:     # LambdaLR.load_state_dict does not write the group lr back: without this the first
             self.param_groups[0]["lr"] = float(sd["lr"])   # resumed step would run at the constructor's lr
         if self._assignment is not None and sd.get("group_lr") is not None:
-            if len(sd["group_lr"]) != len(self.param_groups) or len(sd["group_weight_decay"]) != len(self.param_groups):
-                raise ValueError(f"the optimiser state holds {len(sd['group_lr'])} parameter groups, this optimiser has {len(self.param_groups)}")
-            for q, lr, wd in zip(self.param_groups, sd["group_lr"], sd["group_weight_decay"]):
+            own = [q for q in self.param_groups if not q.get("frozen")]
+            if len(sd["group_lr"]) != len(own) or len(sd["group_weight_decay"]) != len(own):
+                raise ValueError(f"the optimiser state holds {len(sd['group_lr'])} parameter groups, this optimiser has {len(own)}")
+            for q, lr, wd in zip(own, sd["group_lr"], sd["group_weight_decay"]):
                 q["lr"], q["weight_decay"] = float(lr), float(wd)
         self._module._ensure_engine().wait_optimizer()
         flat = self._module._flat
@@ -291,7 +333,17 @@ def cosine_schedule_with_warmup(optimizer, num_warmup_steps: int, num_training_s
         progress = float(step - num_warmup_steps) / float(max(1, num_training_steps - num_warmup_steps))
         return max(0.0, 0.5 * (1.0 + math.cos(math.pi * progress)))
 
-    return torch.optim.lr_scheduler.LambdaLR(optimizer, lr_lambda)
+    return _GroupLambdaLR(optimizer, lr_lambda)
+
+
+class _GroupLambdaLR(torch.optim.lr_scheduler.LambdaLR):
+    """LambdaLR over the groups the optimiser has NOW: FusedAdamW's lr = 0 group of frozen parameters comes and goes with the frozen set
+    (LambdaLR itself pairs the groups with the learning rates of the groups it was built with).  That group keeps lr 0; every other
+    group gets initial_lr * lambda(step), LambdaLR's own value."""
+
+    def get_lr(self):
+        factor = self.lr_lambdas[0](self.last_epoch)
+        return [0.0 if g.get("frozen") else g["initial_lr"] * factor for g in self.optimizer.param_groups]
 
 
 def accumulate_window(module) -> int:
@@ -366,6 +418,7 @@ def loss_kind_of(loss_fn: Optional[nn.Module]) -> Tuple[str, float]:
 
 class JEPA(_ModuleBase):
     """Joint-Embedding Predictive Architecture for waveforms (student encoder + predictor vs EMA teacher)."""
+    student_layout = True        # FlatParams / the optimiser hold every student parameter, frozen or not (freeze.is_student)
 
     def __init__(self, feature_extractor: Extractor, transformer_encoder_layers_cfg: TransformerLayerCFG,
                  transformer_encoder_cfg: TransformerEncoderCFG, transformer_decoder_layers_cfg: TransformerLayerCFG,
@@ -393,6 +446,8 @@ class JEPA(_ModuleBase):
             self.hparams.pop("layer_lr_decay", None)
             self.hparams.pop("encoder_layerdrop", None)
             self.hparams.pop("decoder_layerdrop", None)
+            self.hparams.pop("feature_grad_mult", None)
+            self.hparams.pop("freeze_feature_extractor_updates", None)
         else:
             self.hparams = _AttrDict(lr=lr, adam_betas=tuple(adam_betas), adam_eps=adam_eps, adam_weight_decay=adam_weight_decay,
                                      ema_decay=ema_decay, ema_end_decay=ema_end_decay, ema_anneal_end_step=ema_anneal_end_step,
@@ -427,6 +482,23 @@ class JEPA(_ModuleBase):
             self.hparams["encoder_layerdrop"] = self.encoder_layerdrop
         if self.decoder_layerdrop > 0:
             self.hparams["decoder_layerdrop"] = self.decoder_layerdrop
+        # Partial training (wavjepa_amd.freeze).  A student parameter with requires_grad=False -- by freeze(), or by hand -- is not trained:
+        # no gradient, no update, no weight decay; its unit's parameter-gradient launches are not issued and the backward ends at the
+        # lowest trainable unit.  feature_grad_mult (fairseq's GradMultiply on the conv output, in [0, 1]): the factor on the gradient
+        # that enters the conv stack; 0 freezes extract_audio.*.  freeze_feature_extractor_updates = n: extract_audio.* is frozen while
+        # global_step < n.  Keywords through **kwargs (feature_grad_mult=1.0, freeze_feature_extractor_updates=0), each recorded only when set.
+        self.feature_grad_mult = check_grad_mult(kwargs.pop("feature_grad_mult", 1.0))
+        self.freeze_feature_extractor_updates = int(kwargs.pop("freeze_feature_extractor_updates", 0) or 0)
+        if self.freeze_feature_extractor_updates < 0:
+            raise ValueError(f"freeze_feature_extractor_updates={self.freeze_feature_extractor_updates} must not be negative")
+        if self.feature_grad_mult != 1.0:
+            self.hparams["feature_grad_mult"] = self.feature_grad_mult
+        if self.freeze_feature_extractor_updates > 0:
+            self.hparams["freeze_feature_extractor_updates"] = self.freeze_feature_extractor_updates
+        self._student_named: Optional[List[Tuple[str, nn.Parameter]]] = None     # cached (name, Parameter) of the student, layout order
+        self._frozen_key, self._frozen_set = None, frozenset()
+        self._frozen_memo: Dict[tuple, frozenset] = {}
+        self._frozen_step: Optional[frozenset] = None          # the frozen set of the last training forward (the optimiser's)
         # layerdrop_keep: None -- the kept layers are drawn per forward from (dropout_seed, the dropout call counter, stack, layer), the
         # same on every data-parallel rank; {"enc": [...], "dec": [...]} fixes the kept set of the stacks it names (sorted distinct
         # layer indices; an empty list is legal) for every training forward until it is reset.  last_kept: the kept lists of the last
@@ -561,6 +633,7 @@ class JEPA(_ModuleBase):
         if self._flat is not None and self._flat.adam_m is not None:
             self._adam_carry = (self._flat.adam_m, self._flat.adam_v, self._flat.n)   # optimiser moments survive .to() / .cuda()
         self._flat = None          # parameters were re-created: re-flatten lazily
+        self._student_named, self._frozen_key, self._frozen_memo = None, None, {}
         self._engine = None
         return out
 
@@ -594,7 +667,7 @@ class JEPA(_ModuleBase):
         else:
             streams, conv_in, prefixes = 1, ext.in_channels, ["extract_audio.cnn."]
         self._audio_channels = ext.in_channels
-        self._flat = FlatParams(self, self.device)
+        self._flat = FlatParams(self, self.device, student=is_student)
         carry = getattr(self, "_adam_carry", None)
         if carry is not None:
             if carry[2] != self._flat.n:
@@ -706,6 +779,10 @@ class JEPA(_ModuleBase):
             raise ValueError(f"expected {self.extract_audio.in_channels} audio channel(s), got {audio.shape[1]}")
         plan = ctx_masks if isinstance(ctx_masks, MaskPlan) else make_mask_plan(ctx_masks, target_indices, ctx_and_target_masks, self.device)
         self._prepare_weights()
+        if self.training and torch.is_grad_enabled():      # the frozen set of this step: read again at every training forward
+            self._frozen_step = self._frozen_names()
+            eng.set_frozen(self._frozen_step)
+            eng.grad_mult = self.feature_grad_mult if self.feature_grad_mult > 0 else 1.0
         eng.drop_seed = self._dropout_key()
         every = int(self.monitor_every)
         i, k = self._micro
@@ -731,6 +808,54 @@ class JEPA(_ModuleBase):
             stats = eng.moments.clone()
             out["pred_var"], out["target_var"] = stats[0], stats[1]
         return out
+
+    # ------------------------------------------------------------------------------------------------ partial training
+    def _student(self) -> List[Tuple[str, nn.Parameter]]:
+        if self._student_named is None:      # (built once: named_parameters() walks every tensor, FlatParams.owns says what that costs)
+            self._student_named = [(n, p) for n, p in self.named_parameters() if is_student(n)]
+        return self._student_named
+
+    def freeze(self, *patterns: str) -> List[str]:
+        """requires_grad_(False) on the student parameters the fnmatch `patterns` select ("extract_audio.*", "encoder.layers.[0-2].*",
+        "*.bias"); returns their names.  A pattern that selects nothing: ValueError.  The teacher is never selected."""
+        return self._set_trainable(patterns, False)
+
+    def unfreeze(self, *patterns: str) -> List[str]:
+        """requires_grad_(True) on the student parameters the patterns select; returns their names."""
+        return self._set_trainable(patterns, True)
+
+    def _set_trainable(self, patterns, flag: bool) -> List[str]:
+        named = self._student()
+        names = match([n for n, _ in named], patterns)
+        hit = set(names)
+        for n, p in named:
+            if n in hit:
+                p.requires_grad_(flag)
+                if flag and self._flat is not None and self._flat.owns(self):
+                    p.grad = self._flat.g32[self._flat.by_name[n].offset:self._flat.by_name[n].offset + p.numel()].view(p.shape)
+                elif not flag:
+                    p.grad = None
+        if self._flat is not None:           # attach_grads() between now and the next forward must not re-expose a frozen gradient
+            self._flat.frozen = (self._flat.frozen - hit) if flag else (self._flat.frozen | hit)
+        return names
+
+    def _extractor_held(self) -> bool:
+        """extract_audio.* is frozen by an option: feature_grad_mult = 0, or the freeze_feature_extractor_updates schedule"""
+        return self.feature_grad_mult == 0.0 or int(self.global_step) < self.freeze_feature_extractor_updates
+
+    def _frozen_names(self) -> frozenset:
+        """The frozen student parameters as things stand: requires_grad=False, and extract_audio.* while an option holds it."""
+        named = self._student()
+        key = (tuple(p.requires_grad for _, p in named), self._extractor_held())
+        if key != self._frozen_key:
+            if key not in self._frozen_memo:         # (one object per set: the engine and the optimiser key their own tables by it)
+                self._frozen_memo[key] = frozenset(n for (n, _), on in zip(named, key[0]) if not on or (key[1] and n.startswith("extract_audio.")))
+            self._frozen_key, self._frozen_set = key, self._frozen_memo[key]
+        return self._frozen_set
+
+    def _frozen_for_update(self) -> frozenset:
+        """What the optimiser holds still: the frozen set of the step whose gradients it applies (before any: as things stand)"""
+        return self._frozen_step if self._frozen_step is not None else self._frozen_names()
 
     @property
     def dropout_seed(self) -> int:

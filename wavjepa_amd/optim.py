@@ -19,7 +19,11 @@ _LAYER = re.compile(r"encoder\.layers\.(\d+)\.")
 
 
 def trainable(module: nn.Module) -> List[Tuple[str, nn.Parameter]]:
-    """the parameters the optimiser owns, in the order of the flat layout"""
+    """the parameters the optimiser owns, in the order of the flat layout: for a module that lays out its whole student
+    (JEPA.student_layout: freezing never moves a parameter) every student parameter, frozen or not; otherwise those with requires_grad"""
+    if getattr(module, "student_layout", False):
+        from .freeze import is_student
+        return [(n, p) for n, p in module.named_parameters() if is_student(n)]
     return [(n, p) for n, p in module.named_parameters() if p.requires_grad]
 
 

@@ -34,9 +34,12 @@ def _layout(named: Iterable[Tuple[str, torch.Tensor]]) -> Tuple[List[Slot], int]
 class FlatParams:
     """Owns the flat buffers and the name -> slot maps for one JEPA module."""
 
-    def __init__(self, module: nn.Module, device: torch.device):
+    def __init__(self, module: nn.Module, device: torch.device, student=None):
+        """student: None -- the layout holds the parameters with requires_grad (the denoiser stage, whose module holds a frozen JEPA);
+        a predicate on names (freeze.is_student) -- it holds every parameter the predicate selects whether or not it is trainable,
+        so that freezing never moves a parameter; the frozen ones are recorded in `frozen` (set_frozen)."""
         self.device = device
-        trainable = [(n, p) for n, p in module.named_parameters() if p.requires_grad]
+        trainable = [(n, p) for n, p in module.named_parameters() if (p.requires_grad if student is None else student(n))]
         teacher = [(n, p) for n, p in module.named_parameters() if n.startswith("teacher_encoder.")]
         self.slots, self.n = _layout(trainable)
         self.tslots, self.tn = _layout(teacher)
@@ -53,6 +56,7 @@ class FlatParams:
 
         params = dict(module.named_parameters())
         self._grad_views: List[Tuple[nn.Parameter, torch.Tensor]] = []
+        self.frozen: frozenset = frozenset()      # the frozen names the step was last told of (set_frozen): they expose no .grad
         with torch.no_grad():
             for s in self.slots:
                 p = params[s.name]
@@ -60,7 +64,7 @@ class FlatParams:
                 view.copy_(p.data.to(device=device, dtype=torch.float32))
                 p.data = view
                 gview = self.g32[s.offset:s.offset + s.numel].view(s.shape)
-                p.grad = gview
+                p.grad = gview if p.requires_grad else None
                 self._grad_views.append((p, gview))
             for s in self.tslots:
                 p = params[s.name]
@@ -140,8 +144,27 @@ class FlatParams:
 
     def attach_grads(self) -> None:
         """(Re-)expose the flat gradient buffer as every parameter's .grad (zero_grad(set_to_none) drops them)."""
-        for p, g in self._grad_views:
-            p.grad = g
+        if not self.frozen:
+            for p, g in self._grad_views:
+                p.grad = g
+            return
+        for s, (p, g) in zip(self.slots, self._grad_views):       # a frozen parameter has no gradient, as under autograd
+            p.grad = None if s.name in self.frozen else g
+
+    def set_frozen(self, frozen) -> None:
+        self.frozen = frozenset(frozen)
+        self.attach_grads()
+
+    def ranges_of(self, names) -> List[Tuple[int, int]]:
+        """[lo, hi) element ranges of the named slots, neighbours merged"""
+        runs: List[List[int]] = []
+        for s in self.slots:
+            if s.name in names:
+                if runs and runs[-1][1] == s.offset:
+                    runs[-1][1] = s.offset + s.numel
+                else:
+                    runs.append([s.offset, s.offset + s.numel])
+        return [(lo, hi) for lo, hi in runs]
 
     def ensure_adam_state(self) -> None:
         if self.adam_m is None:
